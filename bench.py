@@ -6,15 +6,18 @@ One "step" = one training-iteration pass of the hot path behind the reference's 
 LBVH refit), raytrace (forward + in-kernel loss gradient + backward), gradient all-reduce over ranks, gradient
 import). A "ray" = one (pixel, bounce-step) traversal; rays/step come from the kernels' own counters.
 
-  python bench.py                       # config C, 1 GPU: the literal dense-init cloud (`value`) and the trained-like cloud (`value_trained_like`)
+  python bench.py                       # config C, 1 GPU: the literal dense-init cloud (`value`), nothing but the timed steps
+  python bench.py --full                # the same, plus the trained-like cloud (`value_trained_like`), primary-only and team-help-off legs,
+                                        # CPU baseline, per-kernel profile pass and roofline
   python bench.py --config B            # BASELINE config 2: 100k Gaussians, 1080p, forward only (measure_fps.py protocol)
+  python bench.py --dump-outputs DIR    # also writes what the last timed step returned to its caller as DIR/<name>.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 Multi-GPU: the image is split into 16x16-pixel tiles dealt round-robin along a Z-curve to the ranks (the scene and the BVH are
 replicated), THIS launch's gradients are summed with ONE RCCL all-reduce of a flat [22N] buffer -> "scaling": "strong".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full it also holds the `roofline` and `cpu_baseline` objects.
 """
 import argparse
 import importlib
@@ -28,24 +31,30 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 ROUND = "r6"  # profiles/<ROUND>/pmc_summary.json holds this round's rocprofv3 --pmc passes of this command (tools/profile.sh), one entry per workload
+DUMP_PIXEL_ROWS = 1 << 20  # --dump-outputs: at most this many (step, pixel) rows of the render (12.6 MB) ...
+DUMP_GAUSSIAN_ROWS = 1 << 18  # ... and this many gaussians of each gradient tensor (22 MB for all eight): a fixed, seeded sample of larger outputs
 
 
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=100)
+    p.add_argument("--steps", type=int, default=100, help="timed steps; `ms_per_step` is their mean")
     p.add_argument("--warmup", type=int, default=50)  # ~1.5 s of load: the core clock needs about that long to ramp (measured)
+    p.add_argument("--full", action="store_true", help="after the timed steps also run the legs that take runs of their own: the other opacity variant, "
+                                                       "primary-only and team-help-off legs, the CPU baseline, the per-kernel profile pass (roofline, kernel_ms, multi_gpu)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step returned to its caller (training: the parameter gradients; forward only: "
+                                                                      "the render) as DIR/<name>.npy, float32; larger outputs as a fixed seeded sample of rows")
     p.add_argument("--config", default="C", choices=["B", "C"], help="BASELINE.json config: C = 1M Gaussians forward+backward (metric), B = 100k forward only")
     p.add_argument("--width", type=int, default=1920)
     p.add_argument("--height", type=int, default=1080)
     p.add_argument("--gaussians", type=int, default=None)
     p.add_argument("--variant", default=None, choices=["trained", "init"], help="opacity of the synthetic cloud: trained-like 0.8 (bounces happen) or the literal dense-init 0.1 (config.py:44)")
-    p.add_argument("--no-second-variant", action="store_true", help="config C at N=1 also times the other opacity variant (reported in `other_variant`); skip it")
+    p.add_argument("--no-second-variant", action="store_true", help="--full: config C at N=1 also times the other opacity variant (reported in `other_variant`); skip it")
     p.add_argument("--bounces", type=int, default=2)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--cpu-sample", default="480x270")
-    p.add_argument("--primary-steps", type=int, default=30, help="timed iterations of the primary-only (num_bounces = 0) leg; 0 skips it")
-    p.add_argument("--profile-steps", type=int, default=9, help="extra untimed launches with per-kernel HIP events")
+    p.add_argument("--primary-steps", type=int, default=30, help="--full: timed iterations of the primary-only (num_bounces = 0) and team-help-off legs; 0 skips them")
+    p.add_argument("--profile-steps", type=int, default=9, help="--full: extra untimed launches with per-kernel HIP events")
     p.add_argument("--strands", type=int, default=0, help="tile slices traced on separate HIP streams (0 = library default: 1); the per-kernel profile pass always uses 1")
     p.add_argument("--emulate-world", type=int, default=0, help="diagnostic: trace only rank 0's tiles of an N-rank partition on this one GPU (no collective)")
     p.add_argument("--emulate-rank", type=int, default=0, help="which rank's tiles --emulate-world traces")
@@ -55,6 +64,8 @@ def parse():
     p.add_argument("--ppll-backward", type=int, default=300_000_000, help="backward capacity (reference default 120M)")
     p.add_argument("--forward-only", action="store_true", help="no-grad render instead of a training iteration (implied by --config B)")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     if a.config == "B":
         a.forward_only = True
     if a.gaussians is None:
@@ -75,6 +86,34 @@ def algorithmic_bytes(kind, step, rays, hc, kc, pixels):
     if kind == "backward":
         return (260.0 if step == 0 else 176.0) * kc + (56.0 * pixels if step == 0 else 0.0)
     raise ValueError(kind)
+
+
+def dump_sample(x, limit, seed=0):
+    """`x` (host array, last axis = channels) unchanged when it has at most `limit` rows, else `limit` rows drawn without replacement
+    with a fixed seed, in ascending order: the same rows in every run of the same size."""
+    rows = x.reshape(-1, x.shape[-1])
+    if rows.shape[0] <= limit:
+        return x
+    return rows[np.sort(np.random.default_rng(seed).choice(rows.shape[0], limit, replace=False))]
+
+
+def step_outputs(ret, m, forward_only):
+    """What the caller of one step receives, on the host. A no-grad render: the image the tracer returns ([3 steps, H, W, 3]). A training
+    step: the gradients it adds to the eight parameters' .grad (named after the reference's GaussianModel attributes; the same gaussians
+    in every tensor) - its launch writes no framebuffer outputs (no-grad launches only), so the image it returns is not computed by it."""
+    if forward_only:
+        return {"render": dump_sample(ret["render"].float().cpu().numpy(), DUMP_PIXEL_ROWS)}
+    g = m.get_gaussians()
+    return {"grad_" + name: dump_sample(t.grad.float().cpu().numpy(), DUMP_GAUSSIAN_ROWS)
+            for name, t in (("xyz", g.mean), ("opacity", g.opacity), ("scaling", g.scale), ("rotation", g.rotation), ("diffuse", g.rgb),
+                            ("normal", g.normal), ("roughness", g.roughness), ("f0", g.f0))}
+
+
+def write_outputs(d, outputs):
+    os.makedirs(d, exist_ok=True)
+    for name, x in outputs.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(x, dtype=np.float32))
+    return sorted(outputs)
 
 
 def main():
@@ -132,8 +171,9 @@ def main():
             torch.cuda.synchronize()
         del xw
 
-    def run_variant(variant, with_profile, with_cpu):
-        """Times `steps` passes of the hot path on the `variant` cloud; returns the pieces of the JSON line."""
+    def run_variant(variant, with_profile, with_cpu, with_legs, dump=False):
+        """Times `steps` passes of the hot path on the `variant` cloud; returns the pieces of the JSON line. `with_legs`: the primary-only
+        and team-help-off legs after the timed steps; `dump`: the outputs of the last timed step (rank 0) in res["outputs"]."""
         g = syn.make_scene(N, variant, seed=0)
         pc = ren.GaussianParams(g)
         # capacities: same meaning as the reference's ppll sizes (entries of 36 B); its own test uses 300M/200M at 1536x1024
@@ -151,11 +191,10 @@ def main():
         def one_step():
             if a.forward_only:
                 with torch.no_grad():
-                    rt(camera)  # measure_fps.py:27-52: render under no_grad, no BVH update between frames
-            else:
-                rt.zero_grad()
-                rt(camera, target_diffuse=images["diffuse_image"], target_specular=images["specular_image"], target_depth=images["depth_image"],
-                   target_normal=images["normal_image"], target_roughness=images["roughness_image"], target_f0=images["f0_image"])
+                    return rt(camera)  # measure_fps.py:27-52: render under no_grad, no BVH update between frames
+            rt.zero_grad()
+            return rt(camera, target_diffuse=images["diffuse_image"], target_specular=images["specular_image"], target_depth=images["depth_image"],
+                      target_normal=images["normal_image"], target_roughness=images["roughness_image"], target_f0=images["f0_image"])
 
         dbg("setup done", variant)
         for _ in range(a.warmup):
@@ -165,7 +204,7 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            one_step()
+            ret = one_step()
         barrier()
         dt = time.perf_counter() - t0
         c = m.get_counters()
@@ -173,8 +212,11 @@ def main():
         dt, total_rays = reduce_pair(dt, float(c[9]))
         res["ms_per_step"] = dt / a.steps * 1e3
         res["value"] = total_rays / dt / 1e6
+        if dump and rank == 0:  # before anything else runs on this tracer (the next step clears the gradients)
+            res["outputs"] = step_outputs(ret, m, a.forward_only)
+        del ret
         # "report also primary-only (num_bounces = 0: exactly P rays), because bounce termination is scene dependent"
-        if a.bounces > 0 and a.primary_steps > 0:
+        if with_legs and a.bounces > 0 and a.primary_steps > 0:
             m.get_config().num_bounces.fill_(0)
             for _ in range(10):
                 one_step()
@@ -195,7 +237,7 @@ def main():
 
         # the same iteration with team help OFF (egr_set_team_help(0): single-wave workgroups, every launch reproducible bit for bit - with help, the
         # product's default, the order of exact depth ties of bounce rays is timing): what the default is worth on the same box in the same process
-        if world == 1 and a.emulate_world <= 1 and a.team_help < 0 and a.primary_steps > 0 and not a.forward_only:
+        if with_legs and world == 1 and a.emulate_world <= 1 and a.team_help < 0 and a.primary_steps > 0 and not a.forward_only:
             m.set_team_help(False)
             for _ in range(15):
                 one_step()
@@ -354,11 +396,11 @@ def main():
         "one training iteration: export + update_bvh + forward + backward + grad import"
     label = {"trained": "trained-like opacity 0.8: reflection bounces happen, three steps per pixel", "init": "literal dense-init opacity 0.1 (config.py:44): Kc ~ 22 per ray, bounces mostly die"}
     vkey = {"trained": "value_trained_like", "init": "value_dense_init"}
-    main_res = run_variant(a.variant, True, not a.no_cpu_baseline)
+    main_res = run_variant(a.variant, a.full, a.full and not a.no_cpu_baseline, a.full, dump=a.dump_outputs is not None)
     other = None
-    if a.config == "C" and world == 1 and not a.no_second_variant and a.emulate_world <= 1 and not a.forward_only:
+    if a.full and a.config == "C" and world == 1 and not a.no_second_variant and a.emulate_world <= 1 and not a.forward_only:
         ov = "init" if a.variant == "trained" else "trained"
-        r2 = run_variant(ov, True, False)
+        r2 = run_variant(ov, True, False, True)
         other = {"variant": ov, "value": round(r2["value"], 3), "unit": "Mrays/s", "ms_per_step": round(r2["ms_per_step"], 4), "status": r2["status"],
                  "roofline": r2["roofline"], "kernel_ms": r2["kernel_ms"], "device_bytes": r2.get("device_bytes"), "primary_only": r2.get("primary_only"), "team_help_off": r2.get("team_help_off")}
     if rank == 0:
@@ -366,18 +408,28 @@ def main():
             "metric": "Mrays/s fwd+bwd @1080p, 1M Gaussians" if a.config == "C" and not a.forward_only else "Mrays/s fwd-only @1080p",
             "value": round(main_res["value"], 3), "unit": "Mrays/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(main_res["ms_per_step"], 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"BASELINE config {a.config}: synthetic dense-init room+spheres cloud, HEADLINE variant = {a.variant} ({label[a.variant]}; "
-                                   f"the other variant is in `other_variant`), N={N}, {W}x{H}, {what}, num_bounces={a.bounces}, jitter on, reference default config",
+            "dtype": "f32", "data": "synthetic", "full": a.full,
+            "config": {"workload": f"BASELINE config {a.config}: synthetic dense-init room+spheres cloud, HEADLINE variant = {a.variant} ({label[a.variant]}"
+                                   f"{'; the other variant is in `other_variant`' if a.full else ''}), N={N}, {W}x{H}, {what}, num_bounces={a.bounces}, jitter on, reference default config",
                        "variant": a.variant, "gaussians": N, "width": W, "height": H, "parallelism": f"image tiles x{world} + 1 all-reduce of the launch's [22N] gradients", "team_help": "product default (on)" if a.team_help < 0 else bool(a.team_help == 1)},
-            "roofline": main_res["roofline"], "cpu_baseline": main_res["cpu_baseline"], "kernel_ms": main_res["kernel_ms"],
-            "value_primary_only": (main_res.get("primary_only") or {}).get("value"), "primary_only": main_res.get("primary_only"),
-            "value_team_help_off": (main_res.get("team_help_off") or {}).get("value"), "team_help_off": main_res.get("team_help_off"),
-            "multi_gpu": main_res.get("multi_gpu"), "other_variant": other, "status": main_res["status"], "psnr_vs_optix": None, "device_bytes": main_res.get("device_bytes"),
-            vkey[a.variant]: round(main_res["value"], 3), vkey["init" if a.variant == "trained" else "trained"]: (other or {}).get("value"),
-            "note": "vs_baseline null: the reference publishes no throughput number; PSNR vs OptiX is unmeasurable here (no NVIDIA "
-                    "hardware), parity is against the CPU oracle (tests/).",
+            "status": main_res["status"], "psnr_vs_optix": None, vkey[a.variant]: round(main_res["value"], 3),
         }
+        if a.full:
+            line.update({
+                "roofline": main_res["roofline"], "cpu_baseline": main_res["cpu_baseline"], "kernel_ms": main_res["kernel_ms"],
+                "value_primary_only": (main_res.get("primary_only") or {}).get("value"), "primary_only": main_res.get("primary_only"),
+                "value_team_help_off": (main_res.get("team_help_off") or {}).get("value"), "team_help_off": main_res.get("team_help_off"),
+                "multi_gpu": main_res.get("multi_gpu"), "other_variant": other, "device_bytes": main_res.get("device_bytes"),
+                vkey["init" if a.variant == "trained" else "trained"]: (other or {}).get("value"),
+            })
+        if a.dump_outputs is not None:
+            line["outputs"] = {"dir": a.dump_outputs, "names": write_outputs(a.dump_outputs, main_res["outputs"]),
+                               "note": "the last timed step as its caller receives it (training: grad_* = what the step adds to each parameter's .grad; forward only: "
+                                       "render [3 steps, H, W, 3]), float32; "
+                                       f"more than {DUMP_PIXEL_ROWS} (step, pixel) rows / {DUMP_GAUSSIAN_ROWS} gaussians: that many rows drawn with seed 0, ascending"}
+        line["note"] = ("vs_baseline null: the reference publishes no throughput number; PSNR vs OptiX is unmeasurable here (no NVIDIA "
+                        "hardware), parity is against the CPU oracle (tests/)." + ("" if a.full else " --full adds the other opacity variant, the "
+                        "primary-only and team-help-off legs, the CPU baseline and the per-kernel profile pass (roofline, kernel_ms)."))
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

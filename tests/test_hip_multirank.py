@@ -44,11 +44,13 @@ def test_exchange_step_through_rccl_at_world_size_1():
 
 @pytest.mark.timeout(900)
 def test_bench_two_ranks_prints_one_line():
-    """bench.py under torch.distributed.run exactly as the driver launches it (reduced sizes, gloo because both ranks sit on cuda:0)."""
+    """bench.py under torch.distributed.run as the driver launches it (reduced sizes, gloo because both ranks sit on cuda:0), with --full so that the
+    per-kernel profile pass and its all-reduce timing run on both ranks too."""
     r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--width", "480", "--height", "272",
-                 "--gaussians", "30000", "--profile-steps", "1", "--no-cpu-baseline"], 29533, env_extra={"EGR_DIST_BACKEND": "gloo", "EGR_TEAM_HELP": "1"})  # (the product's default for such ranks: help on)
+                 "--gaussians", "30000", "--full", "--profile-steps", "1", "--no-cpu-baseline"], 29533, env_extra={"EGR_DIST_BACKEND": "gloo", "EGR_TEAM_HELP": "1"})  # (the product's default for such ranks: help on)
     assert r.returncode == 0, r.stdout[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["status"] == 0 and d["config"]["width"] == 480
+    assert d["full"] and d["multi_gpu"]["allreduce_ms"] is not None

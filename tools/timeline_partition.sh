@@ -1,8 +1,9 @@
-cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/tl8 -o t -- python bench.py --steps 12 --warmup 30 --no-cpu-baseline --profile-steps 0 --emulate-world 8 > gpurun_out/tl8.log 2>&1
+export TMPDIR=/tmp; cd "$(dirname "$0")/.."  # the repository root
+RUNS=${EGR_RUNS_DIR:-runs}  # results go to $RUNS/<tag> (runs/ is kept out of git)
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $RUNS/tl8 -o t -- python bench.py --full --steps 12 --warmup 30 --no-cpu-baseline --profile-steps 0 --emulate-world 8 > $RUNS/tl8.log 2>&1
 python - <<PY
 import csv,glob
-f=glob.glob("gpurun_out/tl8/**/*kernel_trace.csv",recursive=True)[0]
+f=glob.glob("$RUNS/tl8/**/*kernel_trace.csv",recursive=True)[0]
 rows=[r for r in csv.DictReader(open(f))]
 rows.sort(key=lambda r:int(r["Start_Timestamp"]))
 pro=[i for i,r in enumerate(rows) if "k_prologue" in r["Kernel_Name"]]
@@ -23,4 +24,4 @@ for r in it:
     print(f'{n[:40]:40s} q={r.get("Queue_Id","?"):>3s} start={(s-t0)/1e6:8.3f} dur={(e-s)/1e6:7.3f} gap_before={(s-prev_end)/1e6:7.3f}')
     prev_end=max(prev_end,e)
 PY
-rm -rf gpurun_out/tl8
+rm -rf $RUNS/tl8
