@@ -56,7 +56,7 @@ template <class F> int guarded(egr_context *c, F &&f) {
 
 extern "C" {
 
-const char *egr_version(void) { return "egr-hip 0.6 (gfx950)"; } // 0.6: egr_grad_delta_consumed (round 5); 0.4: egr_counters grew (round 3), egr_get_counters_ex, egr_set_rays_per_task; 0.5: egr_set_team_help
+const char *egr_version(void) { return "egr-hip 0.7 (gfx950)"; } // 0.7: strands removed, egr_set_strands accepts only 1; 0.6: egr_grad_delta_consumed (round 5); 0.4: egr_counters grew (round 3), egr_get_counters_ex, egr_set_rays_per_task; 0.5: egr_set_team_help
 
 int egr_create(egr_context **out, int device, int width, int height, int64_t ppll_forward_size, int64_t ppll_backward_size) {
     if (!out || width <= 0 || height <= 0) return 1;
@@ -70,7 +70,6 @@ int egr_create(egr_context **out, int device, int width, int height, int64_t ppl
     c->fwd_capacity = ppll_forward_size > 0 ? ppll_forward_size : 1, c->bwd_capacity = ppll_backward_size > 0 ? ppll_backward_size : 1;
     if (const char *e = getenv("EGR_DENOISE")) c->denoise_mode = atoi(e);
     if (const char *e = getenv("EGR_TEAM_HELP")) c->team_help = atoi(e) != 0 ? 1 : 0;
-    if (const char *e = getenv("EGR_STRANDS")) c->strands = std::max(1, std::min(EGR_MAX_STRANDS, atoi(e)));
     int rc = guarded(c, [&] {
         egr_trace_alloc(c);
         EGR_HIP(hipEventCreate(&c->ev_rt0)), EGR_HIP(hipEventCreate(&c->ev_rt1));
@@ -151,11 +150,7 @@ int egr_set_team_help(egr_context *c, int on) {
     return 0;
 }
 
-int egr_set_strands(egr_context *c, int strands) {
-    if (!c || strands < 1 || strands > c->strands) return 1;
-    c->strands_active = strands;
-    return 0;
-}
+int egr_set_strands(egr_context *c, int strands) { return c && strands == 1 ? 0 : 1; }
 
 static int require_ready(egr_context *c, bool need_bvh) {
     if (!c->bound || !c->have_gaussians) {

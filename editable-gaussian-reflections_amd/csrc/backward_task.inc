@@ -1,7 +1,7 @@
 // k_backward_chain: the backward of ONE step of ONE tile (B1 output gradients, B2 per-hit chain newest first, gradient table
 // flush). Included into the task loop of the kernel; expects `step`, `tq`, PRIMARY, `records`, the LDS table (gt_keys, gt_vals,
 // stage) and the launch constants. A `continue` ends this step of this tile.
-        const uint32_t task = v.bwd_order ? v.bwd_order[v.task_begin + tq] : v.task_begin + tq; // (costliest tasks of the queue's chunk first: k_order_backward)
+        const uint32_t task = v.bwd_order[tq]; // (costliest tasks of the queue's chunk first: k_order_backward)
         uint32_t blk = v.task_last_block[(size_t)step * v.num_tasks + task]; // the tile's arena chain of this step (wave-uniform)
         if (blk == 0xFFFFFFFFu) continue;
         const TaskGeom tg = task_geom(v, task, lane);

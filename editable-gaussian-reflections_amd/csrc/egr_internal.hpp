@@ -17,11 +17,10 @@
 #define EGR_LEAF_FLAG 0x80000000u  // child slot link: leaf -> EGR_LEAF_FLAG | record index, internal -> child node index
 #define EGR_EMPTY_SLOT 0xFFFFFFFFu // unused child slot (checked before the leaf flag)
 #define EGR_WIDTH 8                // children per wide node: 8 x 16 B = one 128-B cache line
-#define EGR_MAX_STRANDS 4
 #ifndef EGR_QUEUE_STRIDE
 #define EGR_QUEUE_STRIDE 32u         // words between two task queue heads: every head on a 128-B line of its own (eight heads on ONE line = eight queues behind one atomic unit)
 #endif
-#define EGR_QUEUE_WORDS (16u * EGR_QUEUE_STRIDE) // task queue heads per strand: 2 kernels (forward chain, backward chain) x 8 XCD heads
+#define EGR_QUEUE_WORDS (16u * EGR_QUEUE_STRIDE) // task queue heads: 2 kernels (forward chain, backward chain) x 8 XCD heads
 #define EGR_GSTK 232               // x 64 = entries of a resident wave's global spill column for its (ray, node) pair stack (the first EGR_PSTK live in LDS)
 #define EGR_EXT_BLOCK 16384u // entries of one candidate-list extension block
 #define EGR_EXT_NONE 0xFFFFFFFFu
@@ -102,9 +101,7 @@ struct DeviceView { // everything a kernel needs, passed by value
     float *state;          // internal per-ray state, SoA by task-linear index (see trace.hip)
     uint32_t state_stride; // = padded number of task-linear rays
     uint32_t *control;     // device counters (see ControlWord)
-    uint32_t task_begin, task_count; // this strand's slice of the rank's task order (see egr_trace_launch)
-    uint32_t *queues;      // [strands][2 kernels][8 XCD heads] task queue heads; this view's strand starts at `queues`
-    uint32_t num_strands;
+    uint32_t *queues;      // [2 kernels][8 XCD heads] task queue heads, EGR_QUEUE_STRIDE words apart
     int grad_overwrite;    // k_grad_gather stores this launch's sums (per-launch buffer, egr_set_grad_overwrite) instead of adding them
     int team_help;         // forward chain: waves without tiles (or waiting for their own helpers) walk pairs their team mates offer (trace.hip: teams)
     const uint8_t *pixel_mask; // debug (egr_debug_set_pixel_mask): [H*W], a pixel with mask 0 is treated like a pixel outside the image; null = every pixel
@@ -113,8 +110,8 @@ struct DeviceView { // everything a kernel needs, passed by value
 
 enum ControlWord : int {
     CW_ACCEPTED = 0,    // per-step 64-bit counters: accepted candidates = what the reference inserts into its forward list
-    CW_HIT_BUMP = 128,  // arena block bump allocator: a returning atomic on the path of every eighth compositing batch - ON A CACHE LINE OF ITS OWN (words 128 .. 159;
-                        // it used to be word 8, on the line every wave adds its twelve per-step counters to when it leaves the kernel)
+    CW_HIT_BUMP = 128,  // arena block bump allocator: a returning atomic on the path of every eighth compositing batch - ON A CACHE LINE OF ITS OWN (words 128 .. 159,
+                        // after the diagnostic words; it used to be word 8, on the line every wave adds its twelve per-step counters to when it leaves the kernel)
     CW_STATUS = 9,
     CW_BUCKET_RECORDS = 7, // 64-B gradient records (wide adds) the backward chain sent to the gradient rows in this launch
     CW_EXT_BUMP = 160,     // candidate-list extension blocks handed out in this launch (its own line too: words 160 .. 191)
@@ -125,10 +122,10 @@ enum ControlWord : int {
     CW_LIFE_RAYS = 28,  // lifetime totals (since egr_create / egr_reset_lifetime_counters), 64-bit
     CW_LIFE_LAUNCHES = 30,
 
-    CW_DBG = 32,        // optional traversal statistics (EGR_TRAVERSAL_STATS builds): 8 x 64-bit
+    CW_DBG = 32,        // diagnostic words [CW_DBG, CW_HIT_BUMP): optional traversal statistics (EGR_TRAVERSAL_STATS builds): 8 x 64-bit
     CW_DBG2 = 48,       // per-phase s_memtime sums: [primary traversal, primary composite, bounce traversal, bounce composite]
     CW_DBG3 = 112,      // per forward step: min / max wave exit time (s_memrealtime)
-    CW_COUNT = 192      // (words from CW_DBG on are zeroed by every launch's prologue)
+    CW_COUNT = 192      // (k_prologue zeroes [CW_DBG, CW_COUNT) in every launch: the diagnostic words and the lines of the two bump counters)
 };
 
 struct KernelStamp {
@@ -187,12 +184,6 @@ struct egr_context {
     float2 *ext_vals = nullptr;
     uint32_t ext_blocks_cap = 0;
     float *denoise_tmp = nullptr; // two W*H*3 ping-pong images, allocated on first use
-    // strands: the rank's tiles are cut into `strands` slices whose kernel sequences run on separate HIP streams, so one
-    // slice's persistent-wave tail (few long tiles left) is filled by the other slice's next kernel
-    int strands = 3;        // allocated (scratch, streams); 3 strands + the caller's stream = the 4 HW queues of the runtime
-    int strands_active = 0; // used by the next launch (0 = all allocated)
-    hipStream_t strand_stream[EGR_MAX_STRANDS] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[EGR_MAX_STRANDS] = {};
     uint32_t *queues = nullptr;
     uint32_t cand_cap = 0, num_slots = 0;
     int team_waves_per_cu = 0; // resident waves per CU of the forward chain's team build (whole teams)

@@ -1,7 +1,7 @@
 // k_forward_chain: ONE bounce step of ONE tile (R1 ray, R2 traversal + candidate evaluation, R3 compositing, raw step results).
 // Included into the task loop of the kernel; expects `step`, `tq`, `near_plane`, GRADS, CUBE and forward_decl.inc.
 // A `continue` ends this step of this tile.
-        const uint32_t task = v.task_begin + tq;
+        const uint32_t task = tq;
         const TaskGeom tg = task_geom(v, task, lane);
         const StateRef S = state_of(v, task, lane);
         const size_t chain_head = (size_t)step * v.num_tasks + task;

@@ -634,8 +634,10 @@ __global__ void k_prologue(DeviceView v, int grads) {
     int t = threadIdx.x;
     if (t < CW_RESET_END) v.control[t] = 0;
     for (int w = CW_DBG + t; w < CW_COUNT; w += (int)blockDim.x) v.control[w] = 0; // (diagnostic words: per launch)
+    static_assert(CW_DBG <= CW_HIT_BUMP && CW_HIT_BUMP < CW_COUNT && CW_DBG <= CW_EXT_BUMP && CW_EXT_BUMP < CW_COUNT, "the bump counters lie in the control block's per-launch words");
+    if (t == 0) v.control[CW_HIT_BUMP] = 0, v.control[CW_EXT_BUMP] = 0;
     if (t < 16) v.control[CW_DBG2 + t] = 0;
-    for (uint32_t q = t; q < EGR_QUEUE_WORDS * v.num_strands; q += blockDim.x) v.queues[q] = 0;
+    for (uint32_t q = t; q < EGR_QUEUE_WORDS; q += blockDim.x) v.queues[q] = 0;
     if (t < 12) v.control[CW_DBG3 + t] = ((t & 3) < 2) ? 0xFFFFFFFFu : 0u;
     if (t == 0) {
         *v.meta.grads_enabled = grads ? 1 : 0;   // metadata.h:29
@@ -701,7 +703,7 @@ template <bool GRADS, bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR
     uint32_t arena_next = 0u, arena_end = 0u; // this wave's run of hit-arena blocks (forward_task.inc)
 
     for (;;) {
-        const uint32_t tq = slot < v.num_slots ? wave_next_task(v.queues, v.task_count, cur_q, lane) : 0xFFFFFFFFu;
+        const uint32_t tq = slot < v.num_slots ? wave_next_task(v.queues, v.num_tasks, cur_q, lane) : 0xFFFFFFFFu;
         if (tq == 0xFFFFFFFFu) break;
 #if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 9 // diagnostic build: stamps of the WHOLE chain of a task (start, end of every step) in its first pixels
         unsigned long long chain_t[EGR_NSTEPS + 1] = {__builtin_amdgcn_s_memrealtime(), 0ull, 0ull, 0ull};
@@ -725,12 +727,11 @@ template <bool GRADS, bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR
                 }
             } while (false);
             // R4 / R5 of this step for the tile's rays
-            const uint32_t etask = v.task_begin + tq;
-            const TaskGeom etg = task_geom(v, etask, lane);
+            const TaskGeom etg = task_geom(v, tq, lane);
 #ifdef EGR_TRAVERSAL_STATS
             const unsigned long long tepi0 = __builtin_amdgcn_s_memtime();
 #endif
-            if (etg.inside) step_epilogue_lane(v, step, GRADS, num_bounces, etg, state_of(v, etask, lane));
+            if (etg.inside) step_epilogue_lane(v, step, GRADS, num_bounces, etg, state_of(v, tq, lane));
 #ifdef EGR_TRAVERSAL_STATS
             tepi += __builtin_amdgcn_s_memtime() - tepi0;
 #endif
@@ -738,7 +739,7 @@ template <bool GRADS, bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR
             chain_t[step + 1] = __builtin_amdgcn_s_memrealtime();
 #endif
         }
-        if (GRADS && lane == 0) v.task_cost[v.task_begin + tq] = bwd_cost;
+        if (GRADS && lane == 0) v.task_cost[tq] = bwd_cost;
 #ifdef EGR_TRAVERSAL_STATS
         if (lane == 0) { // CW_DBG2 + 8: step epilogues, + 12: whole chains (task pull to task end)
             atomicAdd(reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 8), tepi);
@@ -747,7 +748,7 @@ template <bool GRADS, bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR
 #endif
 #if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 9
         {
-            const TaskGeom ctg = task_geom(v, v.task_begin + tq, lane);
+            const TaskGeom ctg = task_geom(v, tq, lane);
             if (lane <= EGR_NSTEPS && ctg.inside) v.stats.num_traversed_per_pixel[ctg.pixel_id] = (int32_t)(chain_t[lane] & 0x7FFFFFFFull);
             if (lane == 4 && ctg.inside) v.stats.num_traversed_per_pixel[ctg.pixel_id] = (int32_t)chain_leaves;
         }
@@ -1028,7 +1029,7 @@ template <int TEAM> struct BwdTeamShared {
 #ifndef EGR_BWD_WAVES
 #define EGR_BWD_WAVES 3
 #endif
-// Between the two chains of a grad launch: the order in which the backward chain takes this strand's tasks. The forward chain knows what a
+// Between the two chains of a grad launch: the order in which the backward chain takes this rank's tasks. The forward chain knows what a
 // tile's backward will cost (its hit rows and hits), and a persistent-wave kernel ends with a tail as long as the tiles that START LATE and
 // RUN LONG: per-task stamps of the whole image put the backward chain at 2807 us where a longest-first list schedule of the same task times
 // needs 2289 us (dense-init; by this proxy 2323 us). One workgroup per queue chunk (wave_next_task: 8 chunks = compact image blocks, one
@@ -1042,14 +1043,14 @@ template <int TEAM> struct BwdTeamShared {
 __global__ void __launch_bounds__(256) k_order_backward(DeviceView v) {
     // STABLE: inside a cost class the tiles keep the order of the chunk (a Z-curve over a compact image block: neighbours in time touch neighbouring records)
     __shared__ uint32_t cnt[EGR_ORDER_BUCKETS][256 + 1];
-    const uint32_t chunk = ((v.task_count + 7u) / 8u + 3u) & ~3u, q = blockIdx.x;
-    const uint32_t beg = q * chunk, end = min(beg + chunk, v.task_count);
+    const uint32_t chunk = ((v.num_tasks + 7u) / 8u + 3u) & ~3u, q = blockIdx.x;
+    const uint32_t beg = q * chunk, end = min(beg + chunk, v.num_tasks);
     if (beg >= end) return;
     const uint32_t t = threadIdx.x, n = end - beg, per = (n + 255u) / 256u;
     const uint32_t i0 = min(t * per, n), i1 = min(i0 + per, n); // thread t owns the contiguous items [i0, i1) of the chunk
     auto bucket = [](uint32_t cost) { return (uint32_t)EGR_ORDER_BUCKETS - 1u - min(cost >> EGR_ORDER_SHIFT, (uint32_t)EGR_ORDER_BUCKETS - 1u); }; // (descending: costliest first)
     for (int b = 0; b < EGR_ORDER_BUCKETS; b++) cnt[b][t] = 0u;
-    for (uint32_t i = i0; i < i1; i++) cnt[bucket(v.task_cost[v.task_begin + beg + i])][t]++;
+    for (uint32_t i = i0; i < i1; i++) cnt[bucket(v.task_cost[beg + i])][t]++;
     __syncthreads();
     if (t < (uint32_t)EGR_ORDER_BUCKETS) { // exclusive scan over the threads, one cost class per thread
         uint32_t acc = 0u;
@@ -1065,12 +1066,12 @@ __global__ void __launch_bounds__(256) k_order_backward(DeviceView v) {
 #pragma unroll
     for (int b = 0; b < EGR_ORDER_BUCKETS; b++) start[b] = acc + cnt[b][t], acc += cnt[b][256];
     for (uint32_t i = i0; i < i1; i++) {
-        const uint32_t bk = bucket(v.task_cost[v.task_begin + beg + i]);
+        const uint32_t bk = bucket(v.task_cost[beg + i]);
         uint32_t at = 0u;
 #pragma unroll
         for (int b = 0; b < EGR_ORDER_BUCKETS; b++)
             if ((uint32_t)b == bk) at = start[b]++;
-        v.bwd_order[v.task_begin + beg + at] = v.task_begin + beg + i;
+        v.bwd_order[beg + at] = beg + i;
     }
 }
 
@@ -1133,7 +1134,7 @@ template <int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribu
     uint32_t records = 0u; // 64-B gradient records this wave sent: bounce hits, primary hits without a table slot (two each), flushed table slots (two each) (egr_counters::bucket_records)
 
     for (;;) {
-        const uint32_t tq = wave_next_task(v.queues + 8 * EGR_QUEUE_STRIDE, v.task_count, cur_q, lane);
+        const uint32_t tq = wave_next_task(v.queues + 8 * EGR_QUEUE_STRIDE, v.num_tasks, cur_q, lane);
         if (tq == 0xFFFFFFFFu) break;
 #if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 8 // diagnostic build: stamps of a task's BACKWARD chain in its first pixels (tools/bwd_times.py)
         const unsigned long long bw_t0 = __builtin_amdgcn_s_memrealtime();
@@ -1168,7 +1169,7 @@ template <int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribu
 #if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 8
         {
             const unsigned long long bw_t2 = __builtin_amdgcn_s_memrealtime();
-            const TaskGeom btg = task_geom(v, v.bwd_order ? v.bwd_order[v.task_begin + tq] : v.task_begin + tq, lane);
+            const TaskGeom btg = task_geom(v, v.bwd_order[tq], lane);
             if (btg.inside) {
                 if (lane == 0) v.stats.num_traversed_per_pixel[btg.pixel_id] = (int32_t)(bw_t0 & 0x7FFFFFFFull), v.stats.num_accumulated_per_pixel[btg.pixel_id] = (int32_t)(bw_t2 & 0x7FFFFFFFull);
                 if (lane == 1) v.stats.num_traversed_per_pixel[btg.pixel_id] = (int32_t)(bw_t1 & 0x7FFFFFFFull), v.stats.num_accumulated_per_pixel[btg.pixel_id] = (int32_t)bw_rows0;
@@ -1230,7 +1231,7 @@ __global__ void __launch_bounds__(EGR_WAVE) k_finish(DeviceView v) {
     const bool accumulate = *v.cfg.accumulate_samples != 0;
     const float cnt = accumulate ? (float)(*v.fb.accumulated_sample_count + 1) : 1.0f;
     const size_t P = v.num_pixels;
-    for (uint32_t task = v.task_begin + blockIdx.x; task < v.task_begin + v.task_count; task += gridDim.x) {
+    for (uint32_t task = blockIdx.x; task < v.num_tasks; task += gridDim.x) {
         const TaskGeom tg = task_geom(v, task, lane);
         if (!tg.inside) continue;
         const StateRef S = state_of(v, task, lane);
@@ -1455,13 +1456,6 @@ void egr_trace_free(egr_context *c) {
     for (auto &o : c->task_orders) egr_dev_free(c, o.table);
     c->task_orders.clear(), c->task_macro = nullptr;
     egr_dev_free(c, c->stack_spill), egr_dev_free(c, c->cand_keys), egr_dev_free(c, c->cand_vals), egr_dev_free(c, c->hit_arena), egr_dev_free(c, c->task_last_block), egr_dev_free(c, c->task_cost), egr_dev_free(c, c->bwd_order), egr_dev_free(c, c->state), egr_dev_free(c, c->control), egr_dev_free(c, c->queues), egr_dev_free(c, c->denoise_tmp), egr_dev_free(c, c->ext_keys), egr_dev_free(c, c->ext_vals);
-    for (int i = 0; i < EGR_MAX_STRANDS; i++) {
-        if (c->strand_stream[i]) (void)hipStreamDestroy(c->strand_stream[i]);
-        if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]);
-        c->strand_stream[i] = nullptr, c->ev_join[i] = nullptr;
-    }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    c->ev_fork = nullptr;
     if (c->control_host) (void)hipHostFree(c->control_host);
     c->control_host = nullptr;
 }
@@ -1490,16 +1484,15 @@ void egr_trace_alloc(egr_context *c) {
     // forward budget: the reference's ppll_forward_size entries x 36 B, spent on (key 4 B + value 8 B) x 64 lanes x cap per slot
     // (the leaf pairs awaiting evaluation live in LDS since the pair walk: no queue in global memory)
     double fwd_bytes = (double)c->fwd_capacity * 36.0;
-    const size_t S = (size_t)c->strands; // every strand owns a full set of resident-wave scratch slots
-    uint64_t cap = (uint64_t)(fwd_bytes / ((double)c->num_slots * (double)S * EGR_WAVE * 12.0)); // key 4 + value 8 bytes
+    uint64_t cap = (uint64_t)(fwd_bytes / ((double)c->num_slots * EGR_WAVE * 12.0)); // key 4 + value 8 bytes
     c->cand_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cap, 64), 16384) & ~7u;
-    egr_dev_alloc_raw(c, (void **)&c->cand_keys, S * c->num_slots * c->cand_cap * EGR_WAVE * sizeof(float));
-    egr_dev_alloc_raw(c, (void **)&c->cand_vals, S * c->num_slots * c->cand_cap * EGR_WAVE * sizeof(float2));
+    egr_dev_alloc_raw(c, (void **)&c->cand_keys, (size_t)c->num_slots * c->cand_cap * EGR_WAVE * sizeof(float));
+    egr_dev_alloc_raw(c, (void **)&c->cand_vals, (size_t)c->num_slots * c->cand_cap * EGR_WAVE * sizeof(float2));
     // extension blocks: 1/8 of the forward byte budget on top (12 B per entry), at least 64 blocks
     c->ext_blocks_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((uint64_t)(fwd_bytes / 8.0 / (12.0 * EGR_EXT_BLOCK)), 64), 65536);
     egr_dev_alloc_raw(c, (void **)&c->ext_keys, (size_t)c->ext_blocks_cap * EGR_EXT_BLOCK * sizeof(float));
     egr_dev_alloc_raw(c, (void **)&c->ext_vals, (size_t)c->ext_blocks_cap * EGR_EXT_BLOCK * sizeof(float2));
-    egr_dev_alloc_raw(c, (void **)&c->stack_spill, S * c->num_slots * EGR_GSTK * EGR_WAVE * sizeof(uint32_t));
+    egr_dev_alloc_raw(c, (void **)&c->stack_spill, (size_t)c->num_slots * EGR_GSTK * EGR_WAVE * sizeof(uint32_t));
     const double bwd_bytes = (double)c->bwd_capacity * 36.0; // the reference's ppll_backward_size entries x 36 B: all of it is arena
     uint64_t blocks = (uint64_t)(bwd_bytes / ((EGR_HIT_BLOCK_ROWS + 1) * EGR_WAVE * sizeof(float4)));
     c->hit_blocks_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(blocks, 64), 0x7FFFFFFFull);
@@ -1514,15 +1507,8 @@ void egr_trace_alloc(egr_context *c) {
     egr_dev_alloc_raw(c, (void **)&c->control, CW_COUNT * sizeof(uint32_t));
     EGR_HIP(hipMemset(c->control, 0, CW_COUNT * sizeof(uint32_t)));
     EGR_HIP(hipHostMalloc((void **)&c->control_host, CW_COUNT * sizeof(uint32_t)));
-    egr_dev_alloc_raw(c, (void **)&c->queues, EGR_QUEUE_WORDS * S * sizeof(uint32_t));
-    EGR_HIP(hipMemset(c->queues, 0, EGR_QUEUE_WORDS * S * sizeof(uint32_t)));
-    if (c->strands > 1) {
-        EGR_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        for (int i = 0; i < c->strands; i++) {
-            EGR_HIP(hipStreamCreateWithFlags(&c->strand_stream[i], hipStreamNonBlocking));
-            EGR_HIP(hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming));
-        }
-    }
+    egr_dev_alloc_raw(c, (void **)&c->queues, EGR_QUEUE_WORDS * sizeof(uint32_t));
+    EGR_HIP(hipMemset(c->queues, 0, EGR_QUEUE_WORDS * sizeof(uint32_t)));
     egr_build_task_order(c);
 }
 
@@ -1553,7 +1539,7 @@ DeviceView egr_make_view(const egr_context *c) {
                    : (c->world > 1 && tiles < 2u * c->num_slots && !egr_team_help_on(c) ? 32u : 64u); // (with team help the heavy tile's walk is shared anyway, and whole 8x8 tiles keep all lanes busy in the per-ray phases: 3.08-3.12 against 3.17-3.21 ms trained-like, 3.50-3.55 against 3.48-3.51 ms dense-init per iteration of rank 0 of 8)
     v.rays_per_task = rpt, v.task_shift = rpt == 64u ? 2u : rpt == 32u ? 3u : 4u;
     v.num_tasks = tiles << (v.task_shift - 2u);
-    v.task_begin = 0, v.task_count = v.num_tasks, v.queues = c->queues, v.num_strands = (uint32_t)c->strands;
+    v.queues = c->queues;
     v.task_macro = c->task_macro;
     // (help changes the ORDER in which a ray's candidates enter its list, never the set; egr_team_help_on)
     v.team_help = egr_team_help_on(c) ? 1 : 0;
@@ -1580,68 +1566,37 @@ void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s
     if (v.n && !live_fresh) hipLaunchKernelGGL(k_live, dim3((v.n + 255) / 256), dim3(256), 0, s, v, grads ? 1 : 0);
     egr_stamp_end(c, s);
     if (v.num_tasks) {
-        // Strands: slices of the task order (whole macro tiles), each with its own queues and scratch slots, each running its
-        // two chain kernels in order on its own stream. Tiles only depend on their own earlier steps, so strands never
-        // synchronise with each other until the join; while one strand's kernel drains its last long tiles the next kernel of
-        // another strand takes the freed wave slots.
-        // (no explicit egr_set_strands: all strands when the rank has at least four tiles per wave slot; with fewer - a rank of a
-        // multi-GPU partition - concurrent chains only delay each other's heaviest tiles: 4.66 / 4.85 / 4.97 ms with 1 / 2 / 3
-        // strands for rank 0 of an 8-way partition, 18.7 / 18.3 / 18.0 ms for the whole image)
-        // (round 5: ONE strand unless egr_set_strands asks for more. Strands paid while the chains ended in long tails; with the backward tasks costliest
-        // first and today's forward chain, interleaved same-box runs of the whole image give 6.73-6.90 / 11.13 ms per iteration with one strand against
-        // 6.94-6.97 / 11.33-11.38 with three - concurrent chains delay each other's tiles more than they fill tails)
-        const int want = c->strands_active > 0 ? std::min(c->strands_active, c->strands) : 1;
-        const int S = (v.num_tasks >= 8u * (uint32_t)want) ? want : 1;
-        static const int bwd_team_env = getenv("EGR_BWD_TEAM_HELP") ? atoi(getenv("EGR_BWD_TEAM_HELP")) : -1; // (experiments: 0 / 1 force the choice)
-        const bool backward_teams = bwd_team_env >= 0 ? bwd_team_env != 0 : (v.team_help == 1 || (c->world > 1 && (uint64_t)(v.num_tasks >> (v.task_shift - 2u)) < 2ull * c->num_slots)); // (egr_set_team_help(1) takes the teams of both chains: tests/test_hip_parity.py)
-        if (S > 1) EGR_HIP(hipEventRecord(c->ev_fork, s));
-        for (int st = 0; st < S; st++) {
-            hipStream_t ls = S > 1 ? c->strand_stream[st] : s;
-            if (S > 1) EGR_HIP(hipStreamWaitEvent(ls, c->ev_fork, 0));
-            DeviceView w = v;
-            const uint32_t groups = v.num_tasks >> v.task_shift; // tasks come in groups (one macro tile)
-            w.task_begin = (uint32_t)(((uint64_t)groups * (uint64_t)st) / (uint64_t)S) << v.task_shift;
-            w.task_count = ((uint32_t)(((uint64_t)groups * (uint64_t)(st + 1)) / (uint64_t)S) << v.task_shift) - w.task_begin;
-            w.queues = c->queues + EGR_QUEUE_WORDS * st;
-            const size_t slot0 = (size_t)st * c->num_slots;
-            w.cand_keys += slot0 * c->cand_cap * EGR_WAVE, w.cand_vals += slot0 * c->cand_cap * EGR_WAVE;
-            w.stack_spill += slot0 * EGR_GSTK * EGR_WAVE;
-            const dim3 sgrid(std::max(1u, std::min(c->num_slots, w.task_count)));
-            egr_stamp_begin(c, "forward_chain", ls);
-            // (the chain exists as single-wave workgroups and as teams of EGR_TEAM waves: launches with egr_set_team_help(1) take the teams)
-            auto launch_forward = [&](auto team_tag) {
-                constexpr uint32_t T = (uint32_t) decltype(team_tag)::value;
-                const dim3 fgrid((sgrid.x + T - 1u) / T), fblock(EGR_WAVE * T); // (num_slots is a multiple of EGR_TEAM: every wave of a team has its scratch)
-                if (grads) {
-                    if (v.cube_mode) hipLaunchKernelGGL((k_forward_chain<true, true, (int)T>), fgrid, fblock, 0, ls, w);
-                    else hipLaunchKernelGGL((k_forward_chain<true, false, (int)T>), fgrid, fblock, 0, ls, w);
-                } else {
-                    if (v.cube_mode) hipLaunchKernelGGL((k_forward_chain<false, true, (int)T>), fgrid, fblock, 0, ls, w);
-                    else hipLaunchKernelGGL((k_forward_chain<false, false, (int)T>), fgrid, fblock, 0, ls, w);
-                }
-            };
-            if (v.team_help) launch_forward(std::integral_constant<int, EGR_TEAM>{});
-            else launch_forward(std::integral_constant<int, 1>{});
-            egr_stamp_end(c, ls);
+        const dim3 sgrid(std::max(1u, std::min(c->num_slots, v.num_tasks)));
+        egr_stamp_begin(c, "forward_chain", s);
+        // (the chain exists as single-wave workgroups and as teams of EGR_TEAM waves: launches with egr_set_team_help(1) take the teams)
+        auto launch_forward = [&](auto team_tag) {
+            constexpr uint32_t T = (uint32_t) decltype(team_tag)::value;
+            const dim3 fgrid((sgrid.x + T - 1u) / T), fblock(EGR_WAVE * T); // (num_slots is a multiple of EGR_TEAM: every wave of a team has its scratch)
             if (grads) {
-                static const bool order_backward = !(getenv("EGR_ORDER_BACKWARD") && atoi(getenv("EGR_ORDER_BACKWARD")) == 0); // (experiments: 0 = tasks in queue order)
-                w.bwd_order = order_backward ? c->bwd_order : nullptr;
-                if (order_backward) hipLaunchKernelGGL(k_order_backward, dim3(8), dim3(256), 0, ls, w);
-                egr_stamp_begin(c, "backward_chain", ls);
-                // (under-filled ranks: the backward chain as teams whose waves without tiles take batches of their mates' bounce hits - gradients are
-                // atomic adds, so no result depends on who sends them; a whole image keeps single-wave workgroups: a team's LDS is only released with its last wave)
-                if (backward_teams) hipLaunchKernelGGL(k_backward_chain<EGR_BWD_TEAM>, dim3((sgrid.x + EGR_BWD_TEAM - 1u) / EGR_BWD_TEAM), dim3(EGR_WAVE * EGR_BWD_TEAM), 0, ls, w);
-                else hipLaunchKernelGGL(k_backward_chain<1>, sgrid, block, 0, ls, w);
-                egr_stamp_end(c, ls);
+                if (v.cube_mode) hipLaunchKernelGGL((k_forward_chain<true, true, (int)T>), fgrid, fblock, 0, s, v);
+                else hipLaunchKernelGGL((k_forward_chain<true, false, (int)T>), fgrid, fblock, 0, s, v);
             } else {
-                egr_stamp_begin(c, "write_outputs", ls);
-                hipLaunchKernelGGL(k_finish, dim3(std::max(1u, std::min(w.task_count, 65535u))), block, 0, ls, w);
-                egr_stamp_end(c, ls);
+                if (v.cube_mode) hipLaunchKernelGGL((k_forward_chain<false, true, (int)T>), fgrid, fblock, 0, s, v);
+                else hipLaunchKernelGGL((k_forward_chain<false, false, (int)T>), fgrid, fblock, 0, s, v);
             }
-            if (S > 1) {
-                EGR_HIP(hipEventRecord(c->ev_join[st], ls));
-                EGR_HIP(hipStreamWaitEvent(s, c->ev_join[st], 0));
-            }
+        };
+        if (v.team_help) launch_forward(std::integral_constant<int, EGR_TEAM>{});
+        else launch_forward(std::integral_constant<int, 1>{});
+        egr_stamp_end(c, s);
+        if (grads) {
+            hipLaunchKernelGGL(k_order_backward, dim3(8), dim3(256), 0, s, v);
+            egr_stamp_begin(c, "backward_chain", s);
+            // (under-filled ranks: the backward chain as teams whose waves without tiles take batches of their mates' bounce hits - gradients are
+            // atomic adds, so no result depends on who sends them; a whole image keeps single-wave workgroups: a team's LDS is only released with its last wave)
+            // (egr_set_team_help(1) takes the teams of both chains: tests/test_hip_parity.py)
+            const bool backward_teams = v.team_help == 1 || (c->world > 1 && (uint64_t)(v.num_tasks >> (v.task_shift - 2u)) < 2ull * c->num_slots);
+            if (backward_teams) hipLaunchKernelGGL(k_backward_chain<EGR_BWD_TEAM>, dim3((sgrid.x + EGR_BWD_TEAM - 1u) / EGR_BWD_TEAM), dim3(EGR_WAVE * EGR_BWD_TEAM), 0, s, v);
+            else hipLaunchKernelGGL(k_backward_chain<1>, sgrid, block, 0, s, v);
+            egr_stamp_end(c, s);
+        } else {
+            egr_stamp_begin(c, "write_outputs", s);
+            hipLaunchKernelGGL(k_finish, dim3(std::max(1u, std::min(v.num_tasks, 65535u))), block, 0, s, v);
+            egr_stamp_end(c, s);
         }
     }
     if (grads && v.n && (v.num_tasks || c->grad_overwrite)) { // (a rank without tiles still owes its per-launch buffer a row of zeros)

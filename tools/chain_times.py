@@ -5,7 +5,6 @@ syn = importlib.import_module("editable-gaussian-reflections_amd.synthetic"); re
 W, H, N = 1920, 1080, 1_000_000
 g = syn.make_scene(N, os.environ.get("VARIANT", "init"), seed=0); cam = syn.default_camera()
 rt = ren.GaussianRaytracer(ren.GaussianParams(g), W, H, ppll_forward_size=400_000_000, ppll_backward_size=300_000_000); m = rt.cuda_module
-m.set_strands(1)
 world = int(os.environ.get("EMU_WORLD", "1"))
 if world > 1: m.set_partition(int(os.environ.get("EMU_RANK", "0")), world)  # (build / run with EGR_RAYS_PER_TASK=64: the stamps sit in the first pixels of 8x8 tiles)
 camera = ren.camera_from_c2w(cam["origin"], cam["c2w"], cam["fov"])

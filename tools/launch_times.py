@@ -8,7 +8,7 @@ W, H, N = 1920, 1080, 1_000_000
 g = syn.make_scene(N, variant, seed=0); cam = syn.default_camera(); tg = syn.make_targets(W, H)
 rt = ren.GaussianRaytracer(ren.GaussianParams(g), W, H, ppll_forward_size=400_000_000, ppll_backward_size=300_000_000); m = rt.cuda_module
 camera = ren.camera_from_c2w(cam["origin"], cam["c2w"], cam["fov"], **{k + "_image": torch.tensor(v).cuda().moveaxis(-1, 0).contiguous() for k, v in tg.items()})
-m.set_strands(1); m.enable_timing(True)
+m.enable_timing(True)
 fw = []
 for i in range(n):
     rt.zero_grad(); ren.render(camera, rt); torch.cuda.synchronize()

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Usage (on the GPU box): tools/profile.sh <tag>
-# 1) rocprofv3 --kernel-trace --stats of `bench.py --strands 1` (kernels run one at a time, so the per-kernel average durations
+# 1) rocprofv3 --kernel-trace --stats of `bench.py` (kernels run one at a time, so the per-kernel average durations
 #    are exclusive and agree with the bench line's roofline.avg_kernel_ms); 2) separate, time-boxed --pmc passes on ONE launch of
-#    each bench workload (EGR_STRANDS=1: one dispatch per chain): FETCH_SIZE and WRITE_SIZE for C_init, C_trained and B_init, the
+#    each bench workload (one dispatch per chain): FETCH_SIZE and WRITE_SIZE for C_init, C_trained and B_init, the
 #    cache / TA / SQ groups for the headline workload. PMC is never combined with trace domains other than --kernel-trace.
 set -u
 RUNS=${EGR_RUNS_DIR:-runs}  # results go to $RUNS/<tag> (runs/ is kept out of git)
@@ -12,13 +12,13 @@ OUT=$RUNS/$TAG; mkdir -p $OUT
 # one process per opacity variant, so that a kernel's average in the stats file belongs to ONE workload (the headline line first);
 # 400+ launches, so that the first few cold ones (clock ramp: up to 3x the steady duration) do not carry the average
 for VAR in init trained; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$VAR -o t -- python bench.py --full --strands 1 --steps 100 --warmup 300 --prewarm-seconds 3 --no-cpu-baseline --no-second-variant --primary-steps 0 --variant $VAR > $OUT/bench_under_rocprof_$VAR.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$VAR -o t -- python bench.py --full --steps 100 --warmup 300 --prewarm-seconds 3 --no-cpu-baseline --no-second-variant --primary-steps 0 --variant $VAR > $OUT/bench_under_rocprof_$VAR.log 2>&1
   grep -a "^{" $OUT/bench_under_rocprof_$VAR.log | tail -1 > $OUT/bench_line_under_rocprof_$VAR.json
   find $OUT/trace_$VAR -name "*kernel_stats.csv" -exec cp {} $OUT/rocprofv3_kernel_stats_$VAR.csv \;
 done
 pass() { # workload-config workload-variant index counters...
   local CFG=$1 VAR=$2 IDX=$3; shift 3
-  ( time PMC_CONFIG=$CFG PMC_VARIANT=$VAR EGR_STRANDS=1 timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_${CFG}_${VAR}_$IDX -o p -- python tools/pmc_run.py ) > $OUT/pmc_${CFG}_${VAR}_$IDX.log 2>&1
+  ( time PMC_CONFIG=$CFG PMC_VARIANT=$VAR timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_${CFG}_${VAR}_$IDX -o p -- python tools/pmc_run.py ) > $OUT/pmc_${CFG}_${VAR}_$IDX.log 2>&1
 }
 for WL in "C init" "C trained" "B init"; do
   set -- $WL

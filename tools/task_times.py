@@ -7,7 +7,6 @@ W, H, N = 1920, 1080, 1_000_000
 world = int(os.environ.get("EMU_WORLD", "1"))
 g = syn.make_scene(N, os.environ.get("VARIANT", "trained"), seed=0); cam = syn.default_camera(); pc = ren.GaussianParams(g)
 rt = ren.GaussianRaytracer(pc, W, H, ppll_forward_size=400_000_000, ppll_backward_size=300_000_000); m = rt.cuda_module
-m.set_strands(1)
 m.get_config().num_bounces.fill_(int(os.environ["TT_STEP"]))  # the measured step must be the last one (later steps overwrite the stats)
 if world > 1: m.set_partition(0, world)
 camera = ren.camera_from_c2w(cam["origin"], cam["c2w"], cam["fov"])

@@ -4,7 +4,7 @@ import csv, glob, json, os, sys
 import numpy as np
 d = sys.argv[1]
 print("# per-launch durations of the two chain kernels from the rocprofv3 kernel trace of the same processes as rocprofv3_kernel_stats_{init,trained}.csv")
-print("# (python bench.py --full --strands 1 --steps 100 --warmup 300 --prewarm-seconds 3 --no-cpu-baseline --no-second-variant --variant V).")
+print("# (python bench.py --full --steps 100 --warmup 300 --prewarm-seconds 3 --no-cpu-baseline --no-second-variant --variant V).")
 print("# bench.py's roofline.avg_kernel_ms is the MEDIAN of its profile pass (HIP events on the launch stream).")
 for var in ("init", "trained"):
     f = glob.glob(os.path.join(d, f"trace_{var}", "*kernel_trace.csv"))
