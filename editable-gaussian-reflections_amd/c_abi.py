@@ -39,6 +39,9 @@ egr_counters = _struct("egr_counters", [("rays", C.c_uint64 * 3), ("candidates",
                                         ("lifetime_launches", C.c_uint32), ("status", C.c_uint32), ("bvh_depth", C.c_uint32), ("bucket_records", C.c_uint32),
                                         ("device_bytes", C.c_uint64), ("arena_blocks_used", C.c_uint32), ("arena_blocks_cap", C.c_uint32),
                                         ("ext_blocks_used", C.c_uint32), ("ext_blocks_cap", C.c_uint32), ("accepted", C.c_uint64 * 3)])
+VIEW_BATCH_OUTPUTS = ("final", "rgb", "depth", "normal", "f0", "roughness")
+egr_view_batch = _struct("egr_view_batch", [("num_views", C.c_uint32), ("samples_per_view", C.c_uint32), ("rotation_c2w_dataset", _F), ("camera_center", _F),
+                                            ("vertical_fov_radians", _F), ("znear", C.c_float), ("zfar", C.c_float)] + [(k, _F) for k in VIEW_BATCH_OUTPUTS])
 
 _lib = None
 
@@ -73,6 +76,8 @@ def lib(path=None):
         L.egr_set_strands.argtypes = [P, C.c_int]
         L.egr_set_rays_per_task.argtypes = [P, C.c_int]
         L.egr_set_team_help.argtypes = [P, C.c_int]
+        L.egr_render_views.argtypes = [P, C.POINTER(egr_view_batch), P]
+        L.egr_set_batch_frames.argtypes = [P, C.c_int]
         L.egr_get_counters.argtypes = [P, C.POINTER(egr_counters), P]
         L.egr_get_counters_ex.argtypes = [P, P, C.c_size_t, P]
         L.egr_last_error.argtypes = [P]
@@ -120,6 +125,19 @@ class RawRaytracer:
 
     def raytrace(self, grads_enabled):  # :81-94
         self._check(self.L.egr_raytrace(self.ctx, 1 if grads_enabled else 0, self.stream))
+
+    def render_views(self, num_views, samples_per_view, rotation_c2w_dataset, camera_center, vertical_fov_radians, znear=0.01, zfar=999.9, **outputs):
+        """egr_render_views: the camera arrays and `outputs` (final= required; rgb=, depth=, normal=, f0=, roughness= optional) are integer
+        device addresses of the caller's buffers (include/egr_raytracer.h: egr_view_batch has their shapes)."""
+        unknown = set(outputs) - set(VIEW_BATCH_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}; expected some of {VIEW_BATCH_OUTPUTS}")
+        b = egr_view_batch(num_views=num_views, samples_per_view=samples_per_view, rotation_c2w_dataset=rotation_c2w_dataset, camera_center=camera_center,
+                           vertical_fov_radians=vertical_fov_radians, znear=znear, zfar=zfar, **{k: outputs.get(k) for k in VIEW_BATCH_OUTPUTS})
+        self._check(self.L.egr_render_views(self.ctx, C.byref(b), self.stream))
+
+    def set_batch_frames(self, frames):
+        self._check(self.L.egr_set_batch_frames(self.ctx, frames))
 
     def denoise(self):  # :96
         self._check(self.L.egr_denoise(self.ctx, self.stream))

@@ -4,6 +4,8 @@
 #include <cstdlib>
 #include <cstring>
 
+#include <algorithm>
+
 #include "egr_internal.hpp"
 #include "egr_device.hpp" // egr_div_rn / egr_sqrt_rn: the debug kernel below runs exactly the functions the hot kernels use
 
@@ -56,7 +58,7 @@ template <class F> int guarded(egr_context *c, F &&f) {
 
 extern "C" {
 
-const char *egr_version(void) { return "egr-hip 0.7 (gfx950)"; } // 0.7: strands removed, egr_set_strands accepts only 1; 0.6: egr_grad_delta_consumed (round 5); 0.4: egr_counters grew (round 3), egr_get_counters_ex, egr_set_rays_per_task; 0.5: egr_set_team_help
+const char *egr_version(void) { return "egr-hip 0.8 (gfx950)"; } // 0.8: egr_render_views, egr_set_batch_frames; 0.7: strands removed, egr_set_strands accepts only 1; 0.6: egr_grad_delta_consumed (round 5); 0.4: egr_counters grew (round 3), egr_get_counters_ex, egr_set_rays_per_task; 0.5: egr_set_team_help
 
 int egr_create(egr_context **out, int device, int width, int height, int64_t ppll_forward_size, int64_t ppll_backward_size) {
     if (!out || width <= 0 || height <= 0) return 1;
@@ -70,6 +72,7 @@ int egr_create(egr_context **out, int device, int width, int height, int64_t ppl
     c->fwd_capacity = ppll_forward_size > 0 ? ppll_forward_size : 1, c->bwd_capacity = ppll_backward_size > 0 ? ppll_backward_size : 1;
     if (const char *e = getenv("EGR_DENOISE")) c->denoise_mode = atoi(e);
     if (const char *e = getenv("EGR_TEAM_HELP")) c->team_help = atoi(e) != 0 ? 1 : 0;
+    if (const char *e = getenv("EGR_BATCH_FRAMES")) c->batch_frames = (uint32_t)std::max(1, atoi(e));
     int rc = guarded(c, [&] {
         egr_trace_alloc(c);
         EGR_HIP(hipEventCreate(&c->ev_rt0)), EGR_HIP(hipEventCreate(&c->ev_rt1));
@@ -206,6 +209,38 @@ int egr_raytrace(egr_context *c, int grads_enabled, void *stream) {
         egr_trace_launch(c, grads_enabled != 0, live_fresh, s);
         if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt1, s)), c->have_rt = true;
     });
+}
+
+int egr_render_views(egr_context *c, const egr_view_batch *b, void *stream) {
+    if (!c) return 1;
+    const bool live_fresh = c->live_fresh; // (consumed as by egr_raytrace: the batch's first chunk may use the live records of a fused update)
+    c->live_fresh = false;
+    if (!b || b->num_views == 0 || b->samples_per_view == 0 || !b->final || !b->rotation_c2w_dataset || !b->camera_center || !b->vertical_fov_radians) {
+        c->last_error = "libegr_hip: egr_render_views: num_views and samples_per_view must be >= 1, final and the three camera arrays non-NULL";
+        return 1;
+    }
+    if ((uint64_t)b->num_views * b->samples_per_view > 0x7FFFFFFFull) {
+        c->last_error = "libegr_hip: egr_render_views: num_views x samples_per_view must stay below 2^31";
+        return 1;
+    }
+    if (require_ready(c, true)) return 1;
+    if (c->exact_stats != c->boxes_are_cubes) {
+        c->last_error = "libegr_hip: egr_set_exact_stats changed since the tree was last refitted; call egr_update_bvh or egr_rebuild_bvh first";
+        return 1;
+    }
+    return guarded(c, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        c->stamps_used = 0;
+        if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt0, s));
+        egr_render_views_launch(c, b, live_fresh, s);
+        if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt1, s)), c->have_rt = true;
+    });
+}
+
+int egr_set_batch_frames(egr_context *c, int frames) {
+    if (!c || frames < 1) return 1;
+    c->batch_frames = (uint32_t)frames;
+    return 0;
 }
 
 int egr_set_camera_from_dataset(egr_context *c, const float *rotation_c2w_dataset, const float *camera_center, float vertical_fov_radians, float znear, float zfar, void *stream) {

@@ -36,7 +36,7 @@
                 // primary ray is regenerated from the seed instead of being stored
                 uint32_t seed = tea4(pid, (uint32_t)*v.meta.total_num_calls);
                 ro = mk3(v.cam.origin[0], v.cam.origin[1], v.cam.origin[2]);
-                rd = primary_direction(v, tg.px, tg.py, *v.cfg.jitter_primary_rays != 0, seed, view_size);
+                rd = primary_direction(v, tg.px, tg.py, *v.cfg.jitter_primary_rays != 0, seed, view_size, v.cam.rotation_w2c);
             } else {
                 f3 spec = mk3(0, 0, 0);
                 for (int j = 1; j < num_bounces + 1; j++)

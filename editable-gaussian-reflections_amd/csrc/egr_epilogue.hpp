@@ -25,7 +25,8 @@ EGR_DI f3u unfused(f3 a) { return f3u{a.x, a.y, a.z}; }
 EGR_DI f3 fused(f3u a) { return f3{a.x, a.y, a.z}; }
 
 // the lane's ray of `task` after forward step `step` (the caller checked tg.inside)
-EGR_DI void step_epilogue_lane(const DeviceView &v, int step, bool grads, int num_bounces, const TaskGeom &tg, const StateRef &S) {
+// (write_seed: false for the frames of a batch but its last - random_seeds is a "last launch wins" store)
+EGR_DI void step_epilogue_lane(const DeviceView &v, int step, bool grads, int num_bounces, const TaskGeom &tg, const StateRef &S, bool write_seed) {
     if (step > 0 && S.ld(F_ALIVE) == 0.0f) return;
     const f3u ro = unfused(S.ld3(F_RAY_O)), rd = unfused(S.ld3(F_RAY_D));
     uint32_t seed = f2u(S.ld(F_SEED));
@@ -73,7 +74,7 @@ EGR_DI void step_epilogue_lane(const DeviceView &v, int step, bool grads, int nu
     S.st(F_ALIVE, (cont && step < num_bounces) ? 1.0f : 0.0f);
     S.st3(F_RAY_O, fused(next_o)), S.st3(F_RAY_D, fused(next_d));
     S.st(F_SEED, u2f(seed));
-    v.meta.random_seeds[tg.pixel_id] = (int32_t)seed; // shaders.cu:172
+    if (write_seed) v.meta.random_seeds[tg.pixel_id] = (int32_t)seed; // shaders.cu:172
 }
 } // namespace
 #ifdef EGR_CONTRACT_AFTER_EPILOGUE // trace.hip: back to the translation unit's default for what follows

@@ -106,7 +106,15 @@ struct DeviceView { // everything a kernel needs, passed by value
     int team_help;         // forward chain: waves without tiles (or waiting for their own helpers) walk pairs their team mates offer (trace.hip: teams)
     const uint8_t *pixel_mask; // debug (egr_debug_set_pixel_mask): [H*W], a pixel with mask 0 is treated like a pixel outside the image; null = every pixel
     int cube_mode;         // exact-statistics launch (egr_set_exact_stats): the tree bounds instance CUBES, every overlap is counted
+    // batched no-grad render (egr_render_views; trace.hip: k_forward_batch, k_finish_batch). Read by the batch kernels only.
+    uint32_t batch_frames;     // frames of this chunk: task index = ((macro-tile group) * batch_frames + frame) << task_shift | sub-task
+    uint32_t batch_frame0;     // batch frame index of the chunk's first frame (frame f = view * samples_per_view + sample)
+    uint32_t batch_last_frame; // the batch's last frame: the only one that writes stats / random_seeds
+    uint32_t batch_spv;        // samples per view
+    const float *batch_cams;   // [views][EGR_BATCH_CAM_FLOATS] camera records (k_batch_cameras)
 };
+#define EGR_BATCH_CAM_FLOATS 16 // per view: origin (3), rows of w2c (9), tanf(fov / 2), pad (3)
+#define EGR_BATCH_CARRY_FLOATS (11 * EGR_NSTEPS) // running sums of a view across a chunk boundary, per pixel and step: rgb 3, depth 1, normal 3, f0 3, roughness 1
 
 enum ControlWord : int {
     CW_ACCEPTED = 0,    // per-step 64-bit counters: accepted candidates = what the reference inserts into its forward list
@@ -193,6 +201,13 @@ struct egr_context {
     uint32_t *task_cost = nullptr, *bwd_order = nullptr;
     float *state = nullptr;
     uint32_t state_stride = 0;
+    // batched no-grad render (egr_render_views): allocated by the first batch call, freed by egr_destroy
+    uint32_t batch_frames = 8;         // frames per launch (egr_set_batch_frames / env EGR_BATCH_FRAMES)
+    uint32_t batch_alloc_frames = 0;   // frames the batch ray state below holds
+    float *batch_state = nullptr;      // F_TOTAL x batch_alloc_frames x state_stride
+    float *batch_carry = nullptr;      // [EGR_BATCH_CARRY_FLOATS][H*W]
+    float *batch_cams = nullptr;       // [batch_cams_cap + 1][EGR_BATCH_CAM_FLOATS] (the last record holds znear, zfar)
+    uint32_t batch_cams_cap = 0;
     uint32_t num_tasks_total = 0; // 8x8 wave tiles in the whole image (a 16x16 macro tile = 4 of them = 256 rays of ray state)
     int team_help = 1;            // egr_set_team_help / env EGR_TEAM_HELP: 1 (default) = waves without tiles help their team mates' walks, 0 = never, -1 = only for under-filled ranks of a partition (egr_team_help_on)
     int rays_per_task = 0;        // 0: automatic (64; 32 for a rank of a partition with fewer than two 8x8 tiles per wave slot); env EGR_RAYS_PER_TASK
@@ -240,6 +255,7 @@ int egr_bvh_check(egr_context *c, hipStream_t s, std::string &msg);
 void egr_trace_alloc(egr_context *c);
 void egr_trace_free(egr_context *c);
 void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s);
+void egr_render_views_launch(egr_context *c, const egr_view_batch *b, bool live_fresh, hipStream_t s);
 uint32_t egr_num_tasks_for_rank(const egr_context *c);
 void egr_build_task_order(egr_context *c);
 DeviceView egr_make_view(const egr_context *c);

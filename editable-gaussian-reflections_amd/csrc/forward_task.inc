@@ -1,8 +1,8 @@
 // k_forward_chain: ONE bounce step of ONE tile (R1 ray, R2 traversal + candidate evaluation, R3 compositing, raw step results).
-// Included into the task loop of the kernel; expects `step`, `tq`, `near_plane`, GRADS, CUBE and forward_decl.inc.
+// Included into the task loop of the kernel; expects `step`, `tq`, `tb`, `near_plane`, GRADS, CUBE, BATCH (`bframe`, `bcam`, `last_frame`) and forward_decl.inc.
 // A `continue` ends this step of this tile.
         const uint32_t task = tq;
-        const TaskGeom tg = task_geom(v, task, lane);
+        const TaskGeom tg = task_geom(v, tb, lane); // (tb == tq outside a batch)
         const StateRef S = state_of(v, task, lane);
         const size_t chain_head = (size_t)step * v.num_tasks + task;
         if (GRADS && lane == 0) v.task_last_block[chain_head] = 0xFFFFFFFFu; // nothing recorded yet
@@ -13,9 +13,15 @@
         uint32_t seed = 0;
         if (step == 0) {
             if (active) {
-                seed = tea4(tg.pixel_id, (uint32_t)*v.meta.total_num_calls); // shaders.cu:88
-                ro = mk3(v.cam.origin[0], v.cam.origin[1], v.cam.origin[2]);
-                rd = primary_direction(v, tg.px, tg.py, *v.cfg.jitter_primary_rays != 0, seed, tanf(*v.cam.vertical_fov_radians / 2.0f));
+                if constexpr (BATCH) { // frame f of a batch: the f-th of the sequential launches would see total_num_calls + f + 1 (its prologue adds 1)
+                    seed = tea4(tg.pixel_id, (uint32_t)*v.meta.total_num_calls + bframe + 1u);
+                    ro = mk3(bcam[0], bcam[1], bcam[2]);
+                    rd = primary_direction(v, tg.px, tg.py, *v.cfg.jitter_primary_rays != 0, seed, bcam[12], bcam + 3);
+                } else {
+                    seed = tea4(tg.pixel_id, (uint32_t)*v.meta.total_num_calls); // shaders.cu:88
+                    ro = mk3(v.cam.origin[0], v.cam.origin[1], v.cam.origin[2]);
+                    rd = primary_direction(v, tg.px, tg.py, *v.cfg.jitter_primary_rays != 0, seed, tanf(*v.cam.vertical_fov_radians / 2.0f), v.cam.rotation_w2c);
+                }
             }
         } else {
             active = active && S.ld(F_ALIVE) != 0.0f;
@@ -177,7 +183,7 @@
                 const float kappa = narrow ? wmax(ray_ok ? 1.0f / pw : 1.0f) * 1.000001f : big; // distance along a ray <= kappa x (distance along the axis)
                 // everything below in the tree's cell coordinates: world offset = (cell - oq) / scale per axis
                 const float isx = 1.0f / v.frame.sx, isy = 1.0f / v.frame.sy, isz = 1.0f / v.frame.sz;
-                const f3 cam_o = mk3(v.cam.origin[0], v.cam.origin[1], v.cam.origin[2]); // the rays' common origin (NOT this lane's `ro`: a lane without a ray - a masked pixel - holds none, and lane 0's value is what `uni` broadcasts)
+                const f3 cam_o = BATCH ? mk3(bcam[0], bcam[1], bcam[2]) : mk3(v.cam.origin[0], v.cam.origin[1], v.cam.origin[2]); // the rays' common origin (NOT this lane's `ro`: a lane without a ray - a masked pixel - holds none, and lane 0's value is what `uni` broadcasts)
                 const float oqx = (cam_o.x - v.frame.ox) * v.frame.sx + 2.0f, oqy = (cam_o.y - v.frame.oy) * v.frame.sy + 2.0f, oqz = (cam_o.z - v.frame.oz) * v.frame.sz + 2.0f;
                 // half projections: X(box) in [S1 - S2, S1 + S2], S1 = sum_a (e_a / 2s_a) (lo_a + hi_a) - C, S2 = sum_a |e_a / 2s_a| (hi_a - lo_a)
                 const float hux = uni(0.5f * eu.x * isx), huy = uni(0.5f * eu.y * isy), huz = uni(0.5f * eu.z * isz);
@@ -655,9 +661,11 @@
                 S.st3(F_RAY_O, ro), S.st3(F_RAY_D, rd);
                 S.st(F_SEED, u2f(seed));
             }
-            v.stats.num_accumulated_per_pixel[tg.pixel_id] = (int32_t)nhits;  // forward_pass.cu:140 (last step wins)
-            if (step == 0) v.stats.num_traversed_per_pixel[tg.pixel_id] = (int32_t)traversed;
-            else v.stats.num_traversed_per_pixel[tg.pixel_id] += (int32_t)traversed; // forward_pass.cu:46
+            if (last_frame) { // (a batch: its last frame only)
+                v.stats.num_accumulated_per_pixel[tg.pixel_id] = (int32_t)nhits;  // forward_pass.cu:140 (last step wins)
+                if (step == 0) v.stats.num_traversed_per_pixel[tg.pixel_id] = (int32_t)traversed;
+                else v.stats.num_traversed_per_pixel[tg.pixel_id] += (int32_t)traversed; // forward_pass.cu:46
+            }
         }
 #ifdef EGR_TASK_TIMES // diagnostic build: the tile's first pixel carries the task's start / end time of one step (which must be the last)
         if (step == EGR_TASK_TIMES && lane == 0 && tg.inside) {

@@ -445,6 +445,55 @@ struct Raytracer : torch::CustomClassHolder {
         }
         check(egr_set_targets_chw(ctx, p[0], p[1], p[2], p[3], p[4], p[5], current_stream()), "set_targets_chw");
     }
+    // batched no-grad render (egr_render_views): R [V,3,3] (dataset c2w rotations), centers [V,3], fovy [V] (any device, moved like set_camera's),
+    // `outputs` = names among final / rgb / depth / normal / f0 / roughness. render_views allocates them (zeros) in the framebuffer's HWC layout with a
+    // leading V - final [V,H,W,3], the others [V,3,H,W,c] - and returns them in the order asked; render_views_into writes the caller's tensors instead.
+    static int64_t view_output_channels(const std::string &name) {
+        if (name == "final" || name == "rgb" || name == "normal" || name == "f0") return 3;
+        if (name == "depth" || name == "roughness") return 1;
+        return 0;
+    }
+    std::vector<Tensor> render_views(Tensor R, Tensor centers, Tensor fovy, double znear, double zfar, int64_t samples_per_view, std::vector<std::string> outputs) {
+        const auto opts = framebuffer_data->output_rgb.options();
+        const int64_t V = R.dim() == 3 ? R.size(0) : 0;
+        std::vector<Tensor> bufs;
+        for (const auto &name : outputs) {
+            const int64_t ch = view_output_channels(name);
+            TORCH_CHECK(ch != 0, "render_views: unknown output '", name, "' (final, rgb, depth, normal, f0, roughness)");
+            bufs.push_back(name == "final" ? torch::zeros({V, height, width, 3}, opts) : torch::zeros({V, EGR_NUM_STEPS, height, width, ch}, opts));
+        }
+        render_views_into(R, centers, fovy, znear, zfar, samples_per_view, outputs, bufs);
+        return bufs;
+    }
+    void render_views_into(Tensor R, Tensor centers, Tensor fovy, double znear, double zfar, int64_t samples_per_view, std::vector<std::string> outputs,
+                           std::vector<Tensor> buffers) {
+        TORCH_CHECK(R.dim() == 3 && R.size(1) == 3 && R.size(2) == 3, "render_views: R must be [V,3,3], got ", R.sizes());
+        const int64_t V = R.size(0);
+        TORCH_CHECK(centers.dim() == 2 && centers.size(0) == V && centers.size(1) == 3, "render_views: centers must be [V,3] = [", V, ",3], got ", centers.sizes());
+        TORCH_CHECK(fovy.dim() == 1 && fovy.size(0) == V, "render_views: fovy must be [V] = [", V, "], got ", fovy.sizes());
+        TORCH_CHECK(samples_per_view >= 0 && samples_per_view <= 0x7FFFFFFF, "render_views: samples_per_view out of range");
+        TORCH_CHECK(outputs.size() == buffers.size(), "render_views_into: one buffer per output name expected");
+        const auto dev = framebuffer_data->output_rgb.device();
+        Tensor r = R.to(dev, torch::kFloat32).contiguous(), cc = centers.to(dev, torch::kFloat32).contiguous(), fv = fovy.to(dev, torch::kFloat32).contiguous();
+        egr_view_batch b{};
+        b.num_views = (uint32_t)V, b.samples_per_view = (uint32_t)samples_per_view;
+        b.rotation_c2w_dataset = r.data_ptr<float>(), b.camera_center = cc.data_ptr<float>(), b.vertical_fov_radians = fv.data_ptr<float>();
+        b.znear = (float)znear, b.zfar = (float)zfar;
+        for (size_t i = 0; i < outputs.size(); i++) {
+            const std::string &name = outputs[i];
+            const int64_t ch = view_output_channels(name);
+            TORCH_CHECK(ch != 0, "render_views: unknown output '", name, "' (final, rgb, depth, normal, f0, roughness)");
+            const Tensor &t = buffers[i];
+            const std::vector<int64_t> want = name == "final" ? std::vector<int64_t>{V, height, width, 3} : std::vector<int64_t>{V, EGR_NUM_STEPS, height, width, ch};
+            TORCH_CHECK(t.device() == dev && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.sizes() == torch::IntArrayRef(want), "render_views: output '", name,
+                        "' must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " on the tracer's device, got ", t.sizes());
+            float **slot = name == "final" ? &b.final : name == "rgb" ? &b.rgb : name == "depth" ? &b.depth : name == "normal" ? &b.normal : name == "f0" ? &b.f0 : &b.roughness;
+            TORCH_CHECK(*slot == nullptr, "render_views: output '", name, "' requested twice");
+            *slot = t.data_ptr<float>();
+        }
+        check(egr_render_views(ctx, &b, current_stream()), "render_views");
+    }
+    void set_batch_frames(int64_t n) { TORCH_CHECK(n >= 1 && n <= 0x7FFFFFFF && egr_set_batch_frames(ctx, (int)n) == 0, "set_batch_frames: a frame count >= 1 expected"); }
     void set_rays_per_task(int64_t n) { TORCH_CHECK(egr_set_rays_per_task(ctx, (int)n) == 0, "set_rays_per_task: 0 (automatic), 16, 32 or 64 expected"); }
     void set_team_help(bool on) { TORCH_CHECK(egr_set_team_help(ctx, on ? 1 : 0) == 0, "set_team_help failed"); }
     void set_team_help_auto() { TORCH_CHECK(egr_set_team_help(ctx, -1) == 0, "set_team_help_auto failed"); } // on for under-filled ranks of a partition only (egr_set_team_help(-1))
@@ -548,6 +597,9 @@ struct Raytracer : torch::CustomClassHolder {
             .def("debug_set_pixel_mask", &Raytracer::debug_set_pixel_mask)
             .def("set_targets_chw", &Raytracer::set_targets_chw)
             .def("set_camera", &Raytracer::set_camera)
+            .def("render_views", &Raytracer::render_views)
+            .def("render_views_into", &Raytracer::render_views_into)
+            .def("set_batch_frames", &Raytracer::set_batch_frames)
             .def("set_exact_stats", &Raytracer::set_exact_stats)
             .def("set_strands", &Raytracer::set_strands)
             .def("set_team_help", &Raytracer::set_team_help)

@@ -92,7 +92,8 @@ EGR_DI void add64(uint32_t *ctrl, int word, uint32_t x) {
 // interleaved same-box pairs); the forward chain keeps it per tile: held across its task loop the value costs two more spilled VGPRs and 2 % (2.94-2.99 against
 // 2.89-2.90 ms), and read per tile from a word the prologue wrote it measures the same as the tanf (2.85-2.87 against 2.84-2.86 ms) - as long as that word sits on a
 // cache line of its own: on the line of the arena's bump counter the one load per tile took the chain from 2.9 to 4.5 ms.
-EGR_DI f3 primary_direction(const DeviceView &v, int ix, int iy, bool jitter, uint32_t &seed, const float view_size) {
+// `w2c` = rows of the world-to-camera rotation: the bound camera's, or a batch view's record (k_batch_cameras).
+EGR_DI f3 primary_direction(const DeviceView &v, int ix, int iy, bool jitter, uint32_t &seed, const float view_size, const float *w2c) {
     float aspect_ratio = (float)v.width / (float)v.height;
     float fx = (float)ix, fy = (float)iy;
     if (jitter) {
@@ -103,7 +104,7 @@ EGR_DI f3 primary_direction(const DeviceView &v, int ix, int iy, bool jitter, ui
     }
     float y = view_size * (1.0f - 2.0f * (fy + 0.5f) / (float)v.height);
     float x = aspect_ratio * view_size * (2.0f * (fx + 0.5f) / (float)v.width - 1.0f);
-    const float *w = v.cam.rotation_w2c; // rows of w2c (= columns of c2w)
+    const float *w = w2c; // rows of w2c (= columns of c2w)
     f3 w0 = mk3(w[0], w[1], w[2]), w1 = mk3(w[3], w[4], w[5]), w2 = mk3(w[6], w[7], w[8]);
     return normalize(w0 * x + w1 * y - w2);
 }
@@ -694,78 +695,14 @@ __global__ void __launch_bounds__(256) k_live(DeviceView v, int grads) {
 #define EGR_FWD_WAVES 4 // waves per SIMD the forward chain is built for (register budget 512 / EGR_FWD_WAVES)
 #endif
 template <bool GRADS, bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribute__((amdgpu_waves_per_eu(EGR_FWD_WAVES, EGR_FWD_WAVES))) k_forward_chain(DeviceView v) {
-#include "forward_decl.inc"
-    if (lane < 4 * EGR_NSTEPS) wc[lane] = 0u;
-    if (threadIdx.x == 0) team.done = 0u, team.hungry = 0u;
-    if (threadIdx.x < TEAM) team.box_count[threadIdx.x] = 0u, team.busy[threadIdx.x] = 0u;
-    __syncthreads(); // the kernel's only workgroup barrier: from here on the waves of a team run independently
-    uint32_t cur_q = blockIdx.x & 7u;
-    uint32_t arena_next = 0u, arena_end = 0u; // this wave's run of hit-arena blocks (forward_task.inc)
-
-    for (;;) {
-        const uint32_t tq = slot < v.num_slots ? wave_next_task(v.queues, v.num_tasks, cur_q, lane) : 0xFFFFFFFFu;
-        if (tq == 0xFFFFFFFFu) break;
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 9 // diagnostic build: stamps of the WHOLE chain of a task (start, end of every step) in its first pixels
-        unsigned long long chain_t[EGR_NSTEPS + 1] = {__builtin_amdgcn_s_memrealtime(), 0ull, 0ull, 0ull};
-        uint32_t chain_leaves = 0u;
-#endif
-#ifdef EGR_TRAVERSAL_STATS
-        const unsigned long long tchain0 = __builtin_amdgcn_s_memtime();
-        unsigned long long tepi = 0ull;
-#endif
-        uint32_t bwd_cost = 0u; // (grad launches) what this tile's backward will cost, roughly in microseconds: 8 per primary hit row, 8 per 64 bounce hits + 2 per bounce hit row
-        for (int step = 0; step <= num_bounces; step++) {
-            do { // (a `continue` in the step body ends the step)
-                const float near_plane = step == 0 ? *v.cam.znear : 0.0f; // forward_pass.cu:8-11
-#include "forward_task.inc"
-                const uint32_t a = wave_sum_u32(active ? 1u : 0u), b = wave_sum_u32(active ? traversed : 0u), c2 = wave_sum_u32(active ? nhits : 0u);
-                const uint32_t d2 = wave_sum_u32(active ? cnt : 0u);
-                if (lane == 0) wc[4 * step] += a, wc[4 * step + 1] += b, wc[4 * step + 2] += c2, wc[4 * step + 3] += d2;
-                if (GRADS) {
-                    const uint32_t rows = wave_max_u32(active ? nhits : 0u);
-                    bwd_cost += step == 0 ? 8u * rows : c2 / 8u + 2u * rows;
-                }
-            } while (false);
-            // R4 / R5 of this step for the tile's rays
-            const TaskGeom etg = task_geom(v, tq, lane);
-#ifdef EGR_TRAVERSAL_STATS
-            const unsigned long long tepi0 = __builtin_amdgcn_s_memtime();
-#endif
-            if (etg.inside) step_epilogue_lane(v, step, GRADS, num_bounces, etg, state_of(v, tq, lane));
-#ifdef EGR_TRAVERSAL_STATS
-            tepi += __builtin_amdgcn_s_memtime() - tepi0;
-#endif
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 9
-            chain_t[step + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
-        }
-        if (GRADS && lane == 0) v.task_cost[tq] = bwd_cost;
-#ifdef EGR_TRAVERSAL_STATS
-        if (lane == 0) { // CW_DBG2 + 8: step epilogues, + 12: whole chains (task pull to task end)
-            atomicAdd(reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 8), tepi);
-            atomicAdd(reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 12), __builtin_amdgcn_s_memtime() - tchain0);
-        }
-#endif
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 9
-        {
-            const TaskGeom ctg = task_geom(v, tq, lane);
-            if (lane <= EGR_NSTEPS && ctg.inside) v.stats.num_traversed_per_pixel[ctg.pixel_id] = (int32_t)(chain_t[lane] & 0x7FFFFFFFull);
-            if (lane == 4 && ctg.inside) v.stats.num_traversed_per_pixel[ctg.pixel_id] = (int32_t)chain_leaves;
-        }
-#endif
-    }
-    wave_sync();
-    if (lane < EGR_NSTEPS) {
-        add64(v.control, CW_RAYS + 2 * lane, wc[4 * lane]), add64(v.control, CW_CAND + 2 * lane, wc[4 * lane + 1]), add64(v.control, CW_COMP + 2 * lane, wc[4 * lane + 2]);
-        add64(v.control, CW_ACCEPTED + 2 * lane, wc[4 * lane + 3]);
-    }
-    if (TEAM > 1 && v.team_help) {
-        // no tiles left for this wave: it helps its team mates with the walks of theirs until all of them are through
-        if (lane == 0) atomicAdd(&team.done, 1u);
-        bool h_over = false;
-        team_help_while<CUBE, TEAM>(v, fc, wsh_all, team, wv, blockIdx.x * (uint32_t)TEAM, h_over, [&]() { return uniform_u32(lds_peek(&team.done)) < (uint32_t)TEAM; });
-        if (h_over) atomicOr(v.control + CW_STATUS, EGR_STATUS_CANDIDATE_OVERFLOW);
-    }
+    constexpr bool BATCH = false;
+#include "forward_chain.inc"
+}
+// The same chain for a batch of no-grad frames (egr_render_views): the frame is part of the task index, the primary rays read the frame's
+// view record, and only the batch's last frame writes stats / random_seeds. Its own kernel, so that the launches of egr_raytrace keep theirs.
+template <bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribute__((amdgpu_waves_per_eu(EGR_FWD_WAVES, EGR_FWD_WAVES))) k_forward_batch(DeviceView v) {
+    constexpr bool GRADS = false, BATCH = true;
+#include "forward_chain.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1268,6 +1205,122 @@ __global__ void __launch_bounds__(EGR_WAVE) k_finish(DeviceView v) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// batched no-grad render (egr_render_views): camera table, per-batch / per-chunk control, output write
+// ---------------------------------------------------------------------------------------------------------
+// One record per view from the dataset convention (k_set_camera's conversion, one thread per view): origin, rows of w2c, tanf(fov / 2) -
+// what a single launch evaluates from the bound camera, the same operations - and after the last view the batch's znear / zfar, which the
+// batch's DeviceView points cam.znear / cam.zfar at.
+__global__ void k_batch_cameras(const float *__restrict__ R, const float *__restrict__ centre, const float *__restrict__ fov, uint32_t views, float znear, float zfar,
+                                float *__restrict__ table) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == views) table[(size_t)views * EGR_BATCH_CAM_FLOATS] = znear, table[(size_t)views * EGR_BATCH_CAM_FLOATS + 1] = zfar;
+    if (i >= views) return;
+    float *rec = table + (size_t)i * EGR_BATCH_CAM_FLOATS;
+    const float *r9 = R + 9 * (size_t)i;
+    for (int t = 0; t < 9; t++) {
+        const int r = t / 3, c = t % 3;
+        rec[3 + 3 * c + r] = c == 0 ? r9[t] : -r9[t]; // w2c = transpose of the Blender c2w ((-R)[:, 0] *= -1)
+    }
+    for (int a = 0; a < 3; a++) rec[a] = centre[3 * (size_t)i + a];
+    rec[12] = tanf(fov[i] / 2.0f);
+    rec[13] = rec[14] = rec[15] = 0.0f;
+}
+// k_prologue for a batch: the per-launch control words, grads_enabled = 0; total_num_calls stays as it is until k_batch_epilogue (the
+// chunks derive every frame's seed from it).
+__global__ void k_batch_prologue(DeviceView v) {
+    const int t = threadIdx.x;
+    if (t < CW_RESET_END) v.control[t] = 0;
+    for (int w = CW_DBG + t; w < CW_COUNT; w += (int)blockDim.x) v.control[w] = 0;
+    if (t < 12) v.control[CW_DBG3 + t] = ((t & 3) < 2) ? 0xFFFFFFFFu : 0u;
+    if (t == 0) *v.meta.grads_enabled = 0;
+}
+// every chunk: fresh task queues and extension blocks (the lists of the previous chunk's tiles are done with)
+__global__ void k_batch_chunk_begin(DeviceView v) {
+    const int t = threadIdx.x;
+    for (uint32_t q = t; q < EGR_QUEUE_WORDS; q += blockDim.x) v.queues[q] = 0;
+    if (t == 0) v.control[CW_EXT_BUMP] = 0;
+}
+__global__ void k_batch_epilogue(DeviceView v, uint32_t frames) {
+    if (threadIdx.x == 0) {
+        *v.meta.total_num_calls += (int32_t)frames; // metadata.h:30, once per frame
+        unsigned long long rays = 0;
+        for (int s = 0; s < EGR_NSTEPS; s++) rays += *reinterpret_cast<unsigned long long *>(v.control + CW_RAYS + 2 * s);
+        *reinterpret_cast<unsigned long long *>(v.control + CW_LIFE_RAYS) += rays;
+        v.control[CW_LIFE_LAUNCHES] += frames;
+    }
+}
+struct BatchOutputs {
+    float *final, *rgb, *depth, *normal, *f0, *roughness; // egr_view_batch's per-view buffers (NULL: not written)
+};
+// k_finish for a chunk of a batch: per pixel, the chunk's frames in order; a view's samples are summed in sample order (fp32, k_finish's
+// EGR_ACC* operations) and its outputs written when its last sample arrives. A view that continues in the next chunk leaves its running
+// sums in the carry buffer (at most one view spans a chunk boundary). S == 1: the values are written as they are (a non-accumulating launch).
+__global__ void __launch_bounds__(EGR_WAVE) k_finish_batch(DeviceView v, BatchOutputs out, float *__restrict__ carry) {
+    const int lane = threadIdx.x;
+    const size_t P = v.num_pixels;
+    const uint32_t S = v.batch_spv, B = v.batch_frames, sh = v.task_shift;
+    const float cnt = (float)S;
+    constexpr int NF = 11; // carried floats per step
+    for (uint32_t task = blockIdx.x; task < v.num_tasks; task += gridDim.x) {
+        const TaskGeom tg = task_geom(v, task, lane);
+        if (!tg.inside) continue;
+        float acc[EGR_NSTEPS][NF];
+        if (v.batch_frame0 % S != 0) { // the chunk starts inside a view
+#pragma unroll
+            for (int s = 0; s < EGR_NSTEPS; s++)
+#pragma unroll
+                for (int k = 0; k < NF; k++) acc[s][k] = carry[(size_t)(s * NF + k) * P + tg.pixel_id];
+        }
+        for (uint32_t f = 0; f < B; f++) {
+            const uint32_t frame = v.batch_frame0 + f, view = frame / S, sample = frame % S;
+            if (sample == 0) {
+#pragma unroll
+                for (int s = 0; s < EGR_NSTEPS; s++)
+#pragma unroll
+                    for (int k = 0; k < NF; k++) acc[s][k] = 0.0f; // (reset_accumulators)
+            }
+            const StateRef St = state_of(v, (((task >> sh) * B + f) << sh) | (task & ((1u << sh) - 1u)), lane);
+            const uint32_t steps = f2u(St.ld(F_STEPS));
+            const bool last = sample == S - 1u;
+            f3 final = mk3(0, 0, 0);
+#pragma unroll
+            for (int s = 0; s < EGR_NSTEPS; s++) {
+                const bool done = (uint32_t)s < steps;
+                f3 rgb = done ? St.ld3(SF(s, S_RGB)) : mk3(0, 0, 0), n = done ? St.ld3(SF(s, S_NORMAL)) : mk3(0, 0, 0);
+                f3 f0 = done ? St.ld3(SF(s, S_F0)) : mk3(0, 0, 0);
+                float depth = done ? St.ld(SF(s, S_DEPTH)) : 0.0f, rough = done ? St.ld(SF(s, S_ROUGH)) : 0.0f;
+                if (S > 1u) { // framebuffer.h:104-128, as k_finish: running sum, then sum / count
+                    float *a = acc[s];
+                    a[0] += rgb.x, a[1] += rgb.y, a[2] += rgb.z, a[3] += depth, a[4] += n.x, a[5] += n.y, a[6] += n.z;
+                    a[7] += f0.x, a[8] += f0.y, a[9] += f0.z, a[10] += rough;
+                    if (!last) continue;
+                    rgb = div_s(mk3(a[0], a[1], a[2]), cnt), depth = a[3] / cnt, n = div_s(mk3(a[4], a[5], a[6]), cnt);
+                    f0 = div_s(mk3(a[7], a[8], a[9]), cnt), rough = a[10] / cnt;
+                }
+                final = final + rgb;
+                const size_t q = tg.pixel_id + P * (size_t)s + 3 * P * (size_t)view; // [view][step][pixel]
+                float *o;
+                if (out.rgb) o = out.rgb + 3 * q, o[0] = rgb.x, o[1] = rgb.y, o[2] = rgb.z;
+                if (out.normal) o = out.normal + 3 * q, o[0] = n.x, o[1] = n.y, o[2] = n.z;
+                if (out.f0) o = out.f0 + 3 * q, o[0] = f0.x, o[1] = f0.y, o[2] = f0.z;
+                if (out.depth) out.depth[q] = depth;
+                if (out.roughness) out.roughness[q] = rough;
+            }
+            if (last) {
+                float *o = out.final + 3 * ((size_t)tg.pixel_id + P * (size_t)view);
+                o[0] = final.x, o[1] = final.y, o[2] = final.z;
+            }
+        }
+        if ((v.batch_frame0 + B) % S != 0) { // the chunk ends inside a view: its sums continue in the next chunk
+#pragma unroll
+            for (int s = 0; s < EGR_NSTEPS; s++)
+#pragma unroll
+                for (int k = 0; k < NF; k++) carry[(size_t)(s * NF + k) * P + tg.pixel_id] = acc[s][k];
+        }
+    }
+}
+
 // Diagnostic export (egr_debug_get_step_hits): composited hits per pixel and bounce step of the last GRAD launch, from the ray state
 // the backward chain reads (S_NHITS); steps a ray did not execute report 0. Pixels outside this rank's partition are not written.
 __global__ void __launch_bounds__(EGR_WAVE) k_export_step_hits(DeviceView v, int32_t *__restrict__ out) {
@@ -1453,6 +1506,8 @@ void egr_build_task_order(egr_context *c) {
 }
 
 void egr_trace_free(egr_context *c) {
+    egr_dev_free(c, c->batch_state), egr_dev_free(c, c->batch_carry), egr_dev_free(c, c->batch_cams);
+    c->batch_alloc_frames = 0, c->batch_cams_cap = 0;
     for (auto &o : c->task_orders) egr_dev_free(c, o.table);
     c->task_orders.clear(), c->task_macro = nullptr;
     egr_dev_free(c, c->stack_spill), egr_dev_free(c, c->cand_keys), egr_dev_free(c, c->cand_vals), egr_dev_free(c, c->hit_arena), egr_dev_free(c, c->task_last_block), egr_dev_free(c, c->task_cost), egr_dev_free(c, c->bwd_order), egr_dev_free(c, c->state), egr_dev_free(c, c->control), egr_dev_free(c, c->queues), egr_dev_free(c, c->denoise_tmp), egr_dev_free(c, c->ext_keys), egr_dev_free(c, c->ext_vals);
@@ -1609,6 +1664,60 @@ void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s
         if (c->grad_overwrite) c->delta_pending = true;
     }
     hipLaunchKernelGGL(k_epilogue, dim3(1), dim3(64), 0, s, v, grads ? 1 : 0);
+}
+
+// egr_render_views: V x S frames in chunks of B = min(V x S, batch_frames) frames, in frame order. Each chunk is one forward chain over
+// (this rank's tasks) x B and one k_finish_batch; the per-launch work of a single frame - prologue, stats reset, k_live, epilogue - runs
+// once per batch.
+void egr_render_views_launch(egr_context *c, const egr_view_batch *b, bool live_fresh, hipStream_t s) {
+    const uint32_t V = b->num_views, F = b->num_views * b->samples_per_view;
+    const uint32_t B = std::min(F, std::max(1u, c->batch_frames));
+    if (c->batch_alloc_frames < B || c->batch_cams_cap < V) EGR_HIP(hipDeviceSynchronize()); // (kernels in flight may still read the buffers replaced below)
+    if (c->batch_alloc_frames < B) { // ray state of B frames (allocated by the first batch call; grows with a larger chunk)
+        egr_dev_free(c, c->batch_state);
+        c->batch_alloc_frames = 0;
+        egr_dev_alloc_raw(c, (void **)&c->batch_state, (size_t)F_TOTAL * B * c->state_stride * sizeof(float));
+        c->batch_alloc_frames = B;
+    }
+    if (!c->batch_carry) egr_dev_alloc(c, c->batch_carry, (size_t)EGR_BATCH_CARRY_FLOATS * c->width * c->height);
+    if (c->batch_cams_cap < V) {
+        egr_dev_free(c, c->batch_cams);
+        c->batch_cams_cap = 0;
+        egr_dev_alloc(c, c->batch_cams, (size_t)(V + 1) * EGR_BATCH_CAM_FLOATS);
+        c->batch_cams_cap = V;
+    }
+    DeviceView v = egr_make_view(c);
+    v.state = c->batch_state, v.state_stride = c->state_stride * c->batch_alloc_frames;
+    v.batch_cams = c->batch_cams, v.batch_spv = b->samples_per_view, v.batch_last_frame = F - 1u;
+    v.cam.znear = c->batch_cams + (size_t)V * EGR_BATCH_CAM_FLOATS, v.cam.zfar = v.cam.znear + 1;
+    const BatchOutputs out{b->final, b->rgb, b->depth, b->normal, b->f0, b->roughness};
+    egr_stamp_begin(c, "prologue+live", s);
+    hipLaunchKernelGGL(k_batch_cameras, dim3((V + 64u) / 64u), dim3(64), 0, s, b->rotation_c2w_dataset, b->camera_center, b->vertical_fov_radians, V, b->znear, b->zfar, c->batch_cams);
+    hipLaunchKernelGGL(k_batch_prologue, dim3(1), dim3(64), 0, s, v);
+    EGR_HIP(hipMemsetAsync(c->stats.num_accumulated_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
+    EGR_HIP(hipMemsetAsync(c->stats.num_traversed_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
+    if (v.n && !live_fresh) hipLaunchKernelGGL(k_live, dim3((v.n + 255) / 256), dim3(256), 0, s, v, 0);
+    egr_stamp_end(c, s);
+    for (uint32_t f0 = 0; f0 < F && v.num_tasks; f0 += B) {
+        v.batch_frame0 = f0, v.batch_frames = std::min(B, F - f0);
+        hipLaunchKernelGGL(k_batch_chunk_begin, dim3(1), dim3(64), 0, s, v);
+        const uint32_t tasks = v.num_tasks * v.batch_frames;
+        const dim3 sgrid(std::max(1u, std::min(c->num_slots, tasks)));
+        egr_stamp_begin(c, "forward_chain", s);
+        auto launch_forward = [&](auto team_tag) {
+            constexpr uint32_t T = (uint32_t) decltype(team_tag)::value;
+            const dim3 fgrid((sgrid.x + T - 1u) / T), fblock(EGR_WAVE * T);
+            if (v.cube_mode) hipLaunchKernelGGL((k_forward_batch<true, (int)T>), fgrid, fblock, 0, s, v);
+            else hipLaunchKernelGGL((k_forward_batch<false, (int)T>), fgrid, fblock, 0, s, v);
+        };
+        if (v.team_help) launch_forward(std::integral_constant<int, EGR_TEAM>{});
+        else launch_forward(std::integral_constant<int, 1>{});
+        egr_stamp_end(c, s);
+        egr_stamp_begin(c, "write_outputs", s);
+        hipLaunchKernelGGL(k_finish_batch, dim3(std::max(1u, std::min(v.num_tasks, 65535u))), dim3(EGR_WAVE), 0, s, v, out, c->batch_carry);
+        egr_stamp_end(c, s);
+    }
+    hipLaunchKernelGGL(k_batch_epilogue, dim3(1), dim3(64), 0, s, v, F);
 }
 
 void egr_export_step_hits(egr_context *c, int32_t *host_out, hipStream_t s) {

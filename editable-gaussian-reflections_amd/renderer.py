@@ -252,6 +252,43 @@ def render(camera, raytracer: GaussianRaytracer, targets_available=True, force_u
                            target_normal=tg["normal_image"], target_roughness=tg["roughness_image"], target_f0=tg["f0_image"])
 
 
+VIEW_OUTPUTS = ("final", "rgb", "depth", "normal", "roughness", "f0")
+
+
+def render_views(cameras, raytracer: GaussianRaytracer, spp=1, outputs=VIEW_OUTPUTS, force_update_bvh=False, znear=0.01, zfar=999.9):
+    """Batched no-grad render (egr_render_views): every camera of `cameras` with `spp` accumulated samples, in as few launches as the ray
+    state allows. View v equals reset_accumulators() + spp x (`render` of cameras[v] with accumulate_samples = spp > 1) bit for bit when team
+    help is off; the framebuffer is not touched, total_num_calls advances by len(cameras) * spp. Returns one SimpleNamespace per view with the
+    CHW fields of `render` (rgb [3,3,H,W], final [1,3,H,W], depth / roughness [3,1,H,W], normal / f0 [3,3,H,W]); fields not in `outputs`
+    are None. Parameters are exported (and the tree refitted with `force_update_bvh`) as by `GaussianRaytracer.__call__`. A partitioned
+    tracer renders the whole image on the calling rank (eval_mode="full_image")."""
+    cameras = list(cameras)
+    outputs = tuple(outputs)
+    if "final" not in outputs:
+        outputs = ("final",) + outputs  # (the library always writes it)
+    m = raytracer.cuda_module
+    with torch.no_grad():
+        as_t = lambda x: torch.from_numpy(np.asarray(x)).float() if isinstance(x, np.ndarray) else torch.as_tensor(x).float()
+        R = torch.stack([as_t(c.R).cuda() for c in cameras]) if cameras else torch.zeros((0, 3, 3), device="cuda")
+        centers = torch.stack([as_t(c.camera_center).cuda() for c in cameras]) if cameras else torch.zeros((0, 3), device="cuda")
+        fovy = torch.tensor([float(c.FoVy) for c in cameras], dtype=torch.float32, device="cuda")
+        raytracer._export_param_values()
+        if force_update_bvh:
+            m.update_bvh(True)
+        raytracer._set_full_image(True)
+        try:
+            bufs = m.render_views(R, centers, fovy, float(os.getenv("ZNEAR", znear)), float(os.getenv("ZFAR", zfar)), int(spp), list(outputs))
+        finally:
+            raytracer._set_full_image(False)
+    got = dict(zip(outputs, bufs))
+    views = []
+    for v in range(len(cameras)):
+        f = lambda k: got[k][v].moveaxis(-1, 1) if k in got else None
+        views.append(SimpleNamespace(final=got["final"][v : v + 1].moveaxis(-1, 1), rgb=f("rgb"), depth=f("depth"), normal=f("normal"), roughness=f("roughness"),
+                                     f0=f("f0")))
+    return views
+
+
 def camera_from_RT(R, T, FoVy, device="cuda", **images):
     """What scene/cameras.py:22-152 holds for a view, from the dataset's (R, T, FovY) (dataset/blender_dataset.py:62-75: R is the
     camera-to-world rotation in COLMAP axes - "stored transposed" -, T the world-to-camera translation): `R` unchanged, `FoVy`, and

@@ -233,6 +233,45 @@ int egr_set_rays_per_task(egr_context *ctx, int rays_per_task);
  * case: its waves without tiles take batches of their team mates' bounce hits - gradients are atomic adds, no result depends on it.) */
 int egr_set_team_help(egr_context *ctx, int on);
 
+/* Batched no-grad render (not in the reference): V views x S samples per view in as few launches as the ray state allows.
+ * A batch is V views times S samples per view; frame f = v * S + s is sample s of view v. For each view v the outputs equal, bit for bit
+ * when team help is off, what this library leaves for: reset the accumulators, then S times (camera of view v, egr_raytrace with
+ * grads_enabled = 0 and accumulate_samples = (S > 1)), then read the framebuffer outputs. In detail:
+ *   - seeds: metadata.total_num_calls advances by V * S; frame f draws its seeds from (value before the batch) + f + 1, as the f-th of the
+ *     sequential launches would, so a launch after the batch sees the same counter as after V * S single launches;
+ *   - accumulation: a view's samples are added into fp32 running sums in sample order and divided by S (k_finish's accumulation); for S == 1
+ *     the value is written undivided (a non-accumulating launch);
+ *   - config: the config scalars are read on the device as in any launch; accumulate_samples is ignored (S decides);
+ *   - outputs: the caller's per-view buffers below (NULL: not written). The framebuffer's output_*, accumulated_* and accumulated_sample_count
+ *     are NOT touched by a batch;
+ *   - stats.* and metadata.random_seeds hold what the LAST frame's sequential launch would leave; metadata.grads_enabled is set to 0;
+ *   - egr_counters: rays / candidates / composited / accepted are sums over the batch's frames, status is ORed over them, lifetime_launches
+ *     grows by V * S;
+ *   - the BVH gates (stale tree, changed exact-stats flag), the partition (a rank traces its own tiles of every frame; other pixels of the
+ *     outputs are left untouched), the debug pixel mask, team help and the exact-statistics build behave as for egr_raytrace.
+ * The camera arrays use the dataset convention of egr_set_camera_from_dataset, one entry per view. */
+typedef struct egr_view_batch {
+    uint32_t num_views;               /* V >= 1 */
+    uint32_t samples_per_view;        /* S >= 1 */
+    const float *rotation_c2w_dataset; /* [V][3][3] device pointer: the dataset's camera-to-world rotations (viewpoint_camera.R) */
+    const float *camera_center;       /* [V][3] device pointer */
+    const float *vertical_fov_radians; /* [V] device pointer */
+    float znear;
+    float zfar;
+    float *final;                     /* [V][H][W][3] required */
+    float *rgb;                       /* [V][3][H][W][3] per bounce step, or NULL */
+    float *depth;                     /* [V][3][H][W][1] or NULL */
+    float *normal;                    /* [V][3][H][W][3] or NULL */
+    float *f0;                        /* [V][3][H][W][3] or NULL */
+    float *roughness;                 /* [V][3][H][W][1] or NULL */
+} egr_view_batch;
+/* Asynchronous on the stream. A batch runs in chunks of min(V * S, batch frames) frames (egr_set_batch_frames); the ray state of a chunk
+ * (444 B per pixel and frame) is allocated by the first call and counted in egr_counters.device_bytes from then on. Wrong arguments (V == 0,
+ * S == 0, a NULL final or a NULL camera array) return non-zero with an egr_last_error message and write nothing. */
+int egr_render_views(egr_context *ctx, const egr_view_batch *batch, void *hip_stream);
+/* Frames per launch of egr_render_views (default 8; env EGR_BATCH_FRAMES at creation). Returns 1 for values < 1. */
+int egr_set_batch_frames(egr_context *ctx, int frames);
+
 /* Synchronises the stream and returns the work counters / status of the most recent egr_raytrace.
  * ABI: egr_counters only ever GROWS AT ITS END (version string of egr_version() bumps with it). egr_get_counters writes
  * sizeof(egr_counters) of THIS header; a host compiled against an older header passes its own sizeof to egr_get_counters_ex, which
