@@ -87,6 +87,7 @@ def lib():
         L.orc_update_bvh.argtypes = [ctypes.c_void_p]
         L.orc_reset_accumulators.argtypes = [ctypes.c_void_p]
         L.orc_raytrace.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        L.orc_raytrace_abs_sums.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.orc_get_instances.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4
         L.orc_primary_ray.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.orc_tea4.restype = ctypes.c_uint32
@@ -204,9 +205,11 @@ class Oracle:
                 d[iy, ix] = v
         return d
 
-    def raytrace(self, grads_enabled=False, targets=None, grads_into=None):
+    def raytrace(self, grads_enabled=False, targets=None, grads_into=None, abs_sums=False):
         """One launch. Returns dict of numpy arrays with the reference's tensor shapes
-        (core/framebuffer.h:161-187). total_num_calls is incremented first (metadata.h:28-31)."""
+        (core/framebuffer.h:161-187). total_num_calls is incremented first (metadata.h:28-31).
+        abs_sums (with grads_enabled): out["grad_abs"] = {gradient key: array of its shape} holding, per component, the sum over every
+        hit that feeds it of |contribution| - a scale that cancellation does not shrink, for bars on single gaussians."""
         self.total_num_calls += 1
         P = self.W * self.H
         H, W = self.H, self.W
@@ -251,7 +254,17 @@ class Oracle:
         for k in _OUT_F64 + _OUT_INT + _OUT_DIAG + _OUT_GRAD:
             if k in out:
                 setattr(o, k, out[k].ctypes.data)
-        self.L.orc_raytrace(self.h, int(bool(grads_enabled)), ctypes.c_uint32(self.total_num_calls), ctypes.byref(tg), ctypes.byref(o))
+        absrow = None
+        if grads_enabled and abs_sums:
+            absrow = np.zeros((n, sum(gshape[k][1] for k in _OUT_GRAD)), np.float64)  # [N, 22]: the nine tensors side by side (GradTable's row)
+            self.L.orc_raytrace_abs_sums(self.h, 1, ctypes.c_uint32(self.total_num_calls), ctypes.byref(tg), ctypes.byref(o), _ptr(absrow))
+        else:
+            self.L.orc_raytrace(self.h, int(bool(grads_enabled)), ctypes.c_uint32(self.total_num_calls), ctypes.byref(tg), ctypes.byref(o))
+        if absrow is not None:
+            out["grad_abs"], c = {}, 0
+            for k in _OUT_GRAD:
+                out["grad_abs"][k] = absrow[:, c:c + gshape[k][1]].copy()
+                c += gshape[k][1]
         return out
 
 

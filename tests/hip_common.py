@@ -159,3 +159,132 @@ def grads_vs_oracle_listing_flipped_pixels(ren, rt, o, camera, tg, W, H, name, m
     report(name, worst_grad_all_pixels=f"{worst_all:.1e}", worst_grad_without_listed=f"{worst_rest:.1e}", flipped_pixels=listing)
     assert worst_rest < bar, (name, err_rest, listing)
     return err_all, err_rest, listing
+
+
+LOSS_WEIGHTS = dict(loss_weight_diffuse=5.0, loss_weight_specular=3.0, loss_weight_normal=2.5, loss_weight_depth=2.5, loss_weight_f0=1.0, loss_weight_roughness=1.0)  # make_pair's
+
+
+def set_config_everywhere(rt, oracles, **cfg):
+    """The same config scalars on the HIP tracer and on every oracle (loss weights, num_bounces: read on the device at every launch)."""
+    mc = rt.cuda_module.get_config()
+    for k, v in cfg.items():
+        getattr(mc, k).fill_(v)
+    for oo in oracles:
+        oo.set_config(**cfg)
+
+
+class SequenceMatched:
+    """The two-pass idea of test_config_c_gradient_check_vs_oracle_at_size for small scenes, with THREE sides: HIP, the fp32 oracle `o` and the fp64
+    oracle `o64` (Oracle(W, H, double=True), same scene / camera / config).
+
+    pass 1 (`trace(None)`) traces every pixel on all three sides - images of a no-grad launch, gradients and the ordered composited sequences of a
+    grad launch - and `masks(p1)` calls a pixel CLEAN when all three sides composite the same gaussians in the same order on every step (equal
+    hit_sequence_hash; HIP: debug_hit_sequence_hash), agree on output_total_transmittance within 2e-5 on every step (the backward reads T - Ttot, quirk Q1)
+    and on every forward output within 1e-3; pass 2 (`trace(clean)`) traces the clean pixels only, on all sides (debug_set_pixel_mask /
+    Oracle.set_pixel_mask) with the same total_num_calls `K`: a masked pixel is a pixel outside the image, the others trace exactly the rays of pass 1.
+    `parts`: the (rank, world) launches the HIP side is made of (images tiled, gradients summed)."""
+
+    def __init__(self, ren, rt, o, o64, camera, tg, K=5, parts=((0, 1),)):
+        self.ren, self.rt, self.o, self.o64, self.camera, self.tg, self.K, self.parts = ren, rt, o, o64, camera, tg, K, list(parts)
+        self.W, self.H = o.W, o.H
+
+    def _hip(self, mask, images):
+        m = self.rt.cuda_module
+        H, W = self.H, self.W
+        if mask is not None:
+            m.debug_set_pixel_mask(torch.from_numpy(mask.astype(np.uint8)).cuda())
+        try:
+            img = None
+            if images:
+                for name in OUT_KEYS:
+                    getattr(m.get_framebuffer(), name).zero_()
+                for r, w in self.parts:
+                    m.set_partition(r, w)
+                    m.get_metadata().total_num_calls.fill_(self.K - 1)
+                    with torch.no_grad():
+                        self.rt(self.camera)
+                img = hip_outputs(self.rt)
+            self.rt.zero_grad()
+            m.get_gaussians().total_weight.zero_()
+            rays, seq = 0, np.zeros((3, H, W), np.uint64)
+            for r, w in self.parts:
+                m.set_partition(r, w)
+                m.get_metadata().total_num_calls.fill_(self.K - 1)
+                self.ren.render(self.camera, self.rt)
+                assert m.get_counters()[11] == 0  # no capacity overflow
+                rays += m.get_counters()[0]
+                seq = seq | m.debug_hit_sequence_hash().numpy().view(np.uint64)  # (0 outside the rank's tiles)
+            torch.cuda.synchronize()
+            assert rays == (H * W if mask is None else int(np.count_nonzero(mask)))
+            return img, hip_grads(self.rt), seq
+        finally:
+            if mask is not None:
+                m.debug_set_pixel_mask(torch.empty(0, dtype=torch.uint8))
+            m.set_partition(0, 1)
+
+    def _oracle(self, oo, mask, images, abs_sums):
+        oo.set_pixel_mask(mask)
+        try:
+            oo.total_num_calls = self.K - 1
+            ref = oo.raytrace(True, targets=self.tg, abs_sums=abs_sums)
+            img = None
+            if images:
+                oo.total_num_calls = self.K - 1
+                img = oo.raytrace(False)
+            return ref, img
+        finally:
+            oo.set_pixel_mask(None)
+
+    def trace(self, mask=None):
+        """One launch set on all three sides (mask None: every pixel, with images). Returns a dict: img_{h,32,64}, grad_{h,32,64}, abs64 (o64's
+        grad_abs), abs32, seq_{h,32,64} ([3,H,W] hashes)."""
+        images = mask is None
+        img_h, grad_h, seq_h = self._hip(mask, images)
+        r32, img32 = self._oracle(self.o, mask, images, True)
+        r64, img64 = self._oracle(self.o64, mask, images, True)
+        return dict(img_h=img_h, img_32=img32, img_64=img64, grad_h=grad_h, grad_32={k: r32[k] for k in GRAD_KEYS}, grad_64={k: r64[k] for k in GRAD_KEYS},
+                    abs64=r64["grad_abs"], abs32=r32["grad_abs"], seq_h=seq_h, seq_32=r32["hit_sequence_hash"], seq_64=r64["hit_sequence_hash"], ref32=r32)
+
+    @staticmethod
+    def masks(p1):
+        """(same_sequence, clean) [H,W] masks of a pass-1 result: same_sequence = equal hashes on all sides and steps and total transmittances within 2e-5
+        (the rays composite and pass the same candidates); clean = that and every forward output within 1e-3 between HIP and both oracles."""
+        same = np.all((p1["seq_h"] == p1["seq_32"]) & (p1["seq_h"] == p1["seq_64"]), axis=0)
+        for ref in (p1["img_32"], p1["img_64"]):
+            same &= np.all(np.abs(p1["img_h"]["output_total_transmittance"] - ref["output_total_transmittance"]) <= 2e-5, axis=(0, -1))
+        off = np.zeros_like(same)
+        for key in OUT_KEYS:
+            if key in ("output_ray_origin", "output_ray_direction"):
+                continue  # (the next ray of a step: follows from the outputs, and has no loss of its own)
+            for ref in (p1["img_32"], p1["img_64"]):
+                off |= np.any(np.abs(p1["img_h"][key] - ref[key]) > 1e-3, axis=(0, -1))
+        return same, same & ~off
+
+    def run(self, max_unclean, name):
+        """pass 1, the asserted cap on the pixels that are not clean, pass 2. Returns (pass 1, pass 2, clean mask)."""
+        p1 = self.trace(None)
+        same, clean = self.masks(p1)
+        unclean = int(clean.size - np.count_nonzero(clean))
+        report(name + "_pass1", pixels=int(clean.size), not_clean=unclean, other_sequence_or_T_total=int(clean.size - np.count_nonzero(same)), cap=max_unclean)
+        assert unclean <= max_unclean, (name, unclean, max_unclean)
+        p2 = self.trace(clean)
+        reordered = int(np.count_nonzero(np.any(p2["seq_h"] != p2["seq_64"], axis=0) & clean))
+        report(name + "_pass2", clean_pixels_with_another_sequence=reordered)
+        return p1, p2, clean
+
+
+def per_component_ratio(x, ref64, abs64, floor=1e-7):
+    """The worst |x - ref| - floor * max|ref| over the components, in units of the reference's sum of absolute contributions of the component
+    (grad_abs): the per-gaussian bar |x - ref| <= kappa * abs + floor * max|ref| holds iff the returned ratio is <= kappa. A component no hit feeds
+    (abs == 0) must be within the floor (inf otherwise)."""
+    worst = 0.0
+    for k in GRAD_KEYS:
+        if k == "total_weight":
+            continue
+        excess = np.abs(np.asarray(x[k], np.float64) - ref64[k]) - floor * float(np.abs(ref64[k]).max())
+        fed = abs64[k] > 0
+        if np.any(excess[~fed] > 0):
+            return float("inf")
+        if np.any(fed):
+            worst = max(worst, float((np.maximum(excess[fed], 0.0) / abs64[k][fed]).max()))
+    return worst
