@@ -42,6 +42,9 @@ egr_counters = _struct("egr_counters", [("rays", C.c_uint64 * 3), ("candidates",
 VIEW_BATCH_OUTPUTS = ("final", "rgb", "depth", "normal", "f0", "roughness")
 egr_view_batch = _struct("egr_view_batch", [("num_views", C.c_uint32), ("samples_per_view", C.c_uint32), ("rotation_c2w_dataset", _F), ("camera_center", _F),
                                             ("vertical_fov_radians", _F), ("znear", C.c_float), ("zfar", C.c_float)] + [(k, _F) for k in VIEW_BATCH_OUTPUTS])
+TRAIN_BATCH_TARGETS = ("target_diffuse", "target_specular", "target_depth", "target_normal", "target_roughness", "target_f0")
+egr_train_batch = _struct("egr_train_batch", [("num_views", C.c_uint32), ("rotation_c2w_dataset", _F), ("camera_center", _F), ("vertical_fov_radians", _F),
+                                              ("znear", C.c_float), ("zfar", C.c_float)] + [(k, _F) for k in TRAIN_BATCH_TARGETS])
 
 _lib = None
 
@@ -78,6 +81,7 @@ def lib(path=None):
         L.egr_set_team_help.argtypes = [P, C.c_int]
         L.egr_render_views.argtypes = [P, C.POINTER(egr_view_batch), P]
         L.egr_set_batch_frames.argtypes = [P, C.c_int]
+        L.egr_train_views.argtypes = [P, C.POINTER(egr_train_batch), P]
         L.egr_get_counters.argtypes = [P, C.POINTER(egr_counters), P]
         L.egr_get_counters_ex.argtypes = [P, P, C.c_size_t, P]
         L.egr_last_error.argtypes = [P]
@@ -135,6 +139,17 @@ class RawRaytracer:
         b = egr_view_batch(num_views=num_views, samples_per_view=samples_per_view, rotation_c2w_dataset=rotation_c2w_dataset, camera_center=camera_center,
                            vertical_fov_radians=vertical_fov_radians, znear=znear, zfar=zfar, **{k: outputs.get(k) for k in VIEW_BATCH_OUTPUTS})
         self._check(self.L.egr_render_views(self.ctx, C.byref(b), self.stream))
+
+    def train_views(self, num_views, rotation_c2w_dataset, camera_center, vertical_fov_radians, znear=0.01, zfar=999.9, **targets):
+        """egr_train_views: the camera arrays and `targets` (target_diffuse=, target_specular=, target_depth=, target_normal=, target_roughness=,
+        target_f0=; each optional, absent = zeros) are integer device addresses of the caller's buffers (include/egr_raytracer.h: egr_train_batch
+        has their shapes)."""
+        unknown = set(targets) - set(TRAIN_BATCH_TARGETS)
+        if unknown:
+            raise ValueError(f"unknown targets {sorted(unknown)}; expected some of {TRAIN_BATCH_TARGETS}")
+        b = egr_train_batch(num_views=num_views, rotation_c2w_dataset=rotation_c2w_dataset, camera_center=camera_center, vertical_fov_radians=vertical_fov_radians,
+                            znear=znear, zfar=zfar, **{k: targets.get(k) for k in TRAIN_BATCH_TARGETS})
+        self._check(self.L.egr_train_views(self.ctx, C.byref(b), self.stream))
 
     def set_batch_frames(self, frames):
         self._check(self.L.egr_set_batch_frames(self.ctx, frames))

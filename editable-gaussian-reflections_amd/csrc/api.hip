@@ -58,7 +58,7 @@ template <class F> int guarded(egr_context *c, F &&f) {
 
 extern "C" {
 
-const char *egr_version(void) { return "egr-hip 0.8 (gfx950)"; } // 0.8: egr_render_views, egr_set_batch_frames; 0.7: strands removed, egr_set_strands accepts only 1; 0.6: egr_grad_delta_consumed (round 5); 0.4: egr_counters grew (round 3), egr_get_counters_ex, egr_set_rays_per_task; 0.5: egr_set_team_help
+const char *egr_version(void) { return "egr-hip 0.8 (gfx950)"; } // 0.8: egr_render_views, egr_set_batch_frames, and (additive, same version) egr_train_views; 0.7: strands removed, egr_set_strands accepts only 1; 0.6: egr_grad_delta_consumed (round 5); 0.4: egr_counters grew (round 3), egr_get_counters_ex, egr_set_rays_per_task; 0.5: egr_set_team_help
 
 int egr_create(egr_context **out, int device, int width, int height, int64_t ppll_forward_size, int64_t ppll_backward_size) {
     if (!out || width <= 0 || height <= 0) return 1;
@@ -233,6 +233,32 @@ int egr_render_views(egr_context *c, const egr_view_batch *b, void *stream) {
         c->stamps_used = 0;
         if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt0, s));
         egr_render_views_launch(c, b, live_fresh, s);
+        if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt1, s)), c->have_rt = true;
+    });
+}
+
+int egr_train_views(egr_context *c, const egr_train_batch *b, void *stream) {
+    if (!c) return 1;
+    const bool live_fresh = c->live_fresh; // (consumed as by egr_raytrace)
+    c->live_fresh = false;
+    if (!b || b->num_views == 0 || !b->rotation_c2w_dataset || !b->camera_center || !b->vertical_fov_radians) {
+        c->last_error = "libegr_hip: egr_train_views: num_views must be >= 1 and the three camera arrays non-NULL";
+        return 1;
+    }
+    if (b->num_views > 0x7FFFFFFFu) {
+        c->last_error = "libegr_hip: egr_train_views: num_views must stay below 2^31";
+        return 1;
+    }
+    if (require_ready(c, true)) return 1;
+    if (c->exact_stats != c->boxes_are_cubes) {
+        c->last_error = "libegr_hip: egr_set_exact_stats changed since the tree was last refitted; call egr_update_bvh or egr_rebuild_bvh first";
+        return 1;
+    }
+    return guarded(c, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        c->stamps_used = 0;
+        if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt0, s));
+        egr_train_views_launch(c, b, live_fresh, s);
         if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt1, s)), c->have_rt = true;
     });
 }

@@ -1,10 +1,13 @@
-// k_backward_chain: the backward of ONE step of ONE tile (B1 output gradients, B2 per-hit chain newest first, gradient table
-// flush). Included into the task loop of the kernel; expects `step`, `tq`, PRIMARY, `records`, the LDS table (gt_keys, gt_vals,
+// k_backward_chain / k_backward_batch: the backward of ONE step of ONE tile (B1 output gradients, B2 per-hit chain newest first, gradient table
+// flush). Included into the task loop of the kernel; expects `step`, `tq`, PRIMARY, BATCH, `records`, the LDS table (gt_keys, gt_vals,
 // stage) and the launch constants. A `continue` ends this step of this tile.
         const uint32_t task = v.bwd_order[tq]; // (costliest tasks of the queue's chunk first: k_order_backward)
-        uint32_t blk = v.task_last_block[(size_t)step * v.num_tasks + task]; // the tile's arena chain of this step (wave-uniform)
+        uint32_t blk = v.task_last_block[(size_t)step * (BATCH ? v.num_tasks * v.batch_frames : v.num_tasks) + task]; // the tile's arena chain of this step (wave-uniform)
         if (blk == 0xFFFFFFFFu) continue;
-        const TaskGeom tg = task_geom(v, task, lane);
+        uint32_t tb = task, bframe = 0u; // (BATCH) the tile's pixels; the task's batch frame = its view (egr_train_views: one sample per view)
+        if constexpr (BATCH) tb = batch_base_task(v, task), bframe = v.batch_frame0 + (task >> v.task_shift) % v.batch_frames;
+        (void)bframe;
+        const TaskGeom tg = task_geom(v, tb, lane);
         const StateRef S = state_of(v, task, lane);
         uint32_t steps_done = tg.inside ? f2u(S.ld(F_STEPS)) : 0u;
         uint32_t nhits = (tg.inside && (uint32_t)step < steps_done && blk != 0xFFFFFFFFu) ? f2u(S.ld(SF(step, S_NHITS))) : 0u; // shaders.cu:157-158
@@ -23,7 +26,23 @@
         if (nhits > 0) {
             const uint32_t pid = tg.pixel_id;
             const float third = 1.0f / 3.0f;
-            if (PRIMARY) {
+            if (PRIMARY && BATCH) {
+                f3 o_rgb = S.ld3(SF(0, S_RGB)), o_n = S.ld3(SF(0, S_NORMAL)), o_f0 = S.ld3(SF(0, S_F0));
+                float o_depth = S.ld(SF(0, S_DEPTH)), o_rough = S.ld(SF(0, S_ROUGH));
+                // the view's own targets (channel-major [V][C][H][W]; NULL: zeros) - the same operations as below on the same values
+                const size_t P = v.num_pixels;
+                auto tgt = [&](int b, uint32_t ch, uint32_t c) { const float *p = v.batch_targets[b]; return p ? p[((size_t)bframe * ch + c) * P + pid] : 0.0f; };
+                dL_rgb = mk3(third * sign1(o_rgb.x - tgt(0, 3, 0)), third * sign1(o_rgb.y - tgt(0, 3, 1)), third * sign1(o_rgb.z - tgt(0, 3, 2))) * *v.cfg.loss_weight_diffuse;
+                dL_depth = sign1(o_depth - tgt(2, 1, 0)) * *v.cfg.loss_weight_depth;
+                dL_n = mk3(third * sign1(o_n.x - tgt(3, 3, 0)), third * sign1(o_n.y - tgt(3, 3, 1)), third * sign1(o_n.z - tgt(3, 3, 2))) * *v.cfg.loss_weight_normal;
+                dL_f0 = mk3(third * sign1(o_f0.x - tgt(5, 3, 0)), third * sign1(o_f0.y - tgt(5, 3, 1)), third * sign1(o_f0.z - tgt(5, 3, 2))) * *v.cfg.loss_weight_f0;
+                dL_rough = sign1(o_rough - tgt(4, 1, 0)) * *v.cfg.loss_weight_roughness;
+                // the view's primary ray: its camera record and the seed base of its frame (forward_task.inc)
+                uint32_t seed = tea4(pid, (uint32_t)*v.meta.total_num_calls + bframe + 1u);
+                const float *bcam = v.batch_cams + (size_t)bframe * EGR_BATCH_CAM_FLOATS;
+                ro = mk3(bcam[0], bcam[1], bcam[2]);
+                rd = primary_direction(v, tg.px, tg.py, *v.cfg.jitter_primary_rays != 0, seed, bcam[12], bcam + 3);
+            } else if (PRIMARY) {
                 f3 o_rgb = S.ld3(SF(0, S_RGB)), o_n = S.ld3(SF(0, S_NORMAL)), o_f0 = S.ld3(SF(0, S_F0));
                 float o_depth = S.ld(SF(0, S_DEPTH)), o_rough = S.ld(SF(0, S_ROUGH));
                 const float *td = v.fb.target_diffuse + 3 * (size_t)pid, *tn = v.fb.target_normal + 3 * (size_t)pid,
@@ -41,9 +60,17 @@
                 f3 spec = mk3(0, 0, 0);
                 for (int j = 1; j < num_bounces + 1; j++)
                     if ((uint32_t)j < steps_done) spec = spec + S.ld3(SF(j, S_RGB)); // unexecuted steps hold 0 upstream
-                const float *ts = v.fb.target_specular + 3 * (size_t)pid;
+                f3 t_spec;
+                if constexpr (BATCH) {
+                    const float *p = v.batch_targets[1];
+                    const size_t P = v.num_pixels, q = (size_t)bframe * 3 * P + pid;
+                    t_spec = p ? mk3(p[q], p[q + P], p[q + 2 * P]) : mk3(0, 0, 0);
+                } else {
+                    const float *ts = v.fb.target_specular + 3 * (size_t)pid;
+                    t_spec = mk3(ts[0], ts[1], ts[2]);
+                }
                 float down = powf(1.0f - S.ld(SF(step - 1, S_ROUGH)), EGR_ROUGHNESS_DOWNWEIGHT_GRAD_POWER); // :11-13
-                dL_rgb = (mk3(third * sign1(spec.x - ts[0]), third * sign1(spec.y - ts[1]), third * sign1(spec.z - ts[2])) *
+                dL_rgb = (mk3(third * sign1(spec.x - t_spec.x), third * sign1(spec.y - t_spec.y), third * sign1(spec.z - t_spec.z)) *
                           *v.cfg.loss_weight_specular) * down;
                 dL_rgb = dL_rgb * S.ld3(SF(step - 1, S_THR)); // :107, throughput of the previous step
                 ro = S.ld3(SF(step - 1, S_NEXT_O));

@@ -112,6 +112,9 @@ struct DeviceView { // everything a kernel needs, passed by value
     uint32_t batch_last_frame; // the batch's last frame: the only one that writes stats / random_seeds
     uint32_t batch_spv;        // samples per view
     const float *batch_cams;   // [views][EGR_BATCH_CAM_FLOATS] camera records (k_batch_cameras)
+    // multi-view training (egr_train_views; k_forward_batch_grads, k_backward_batch): frame = view (batch_spv = 1). The per-view targets, channel-major
+    // [V][C][H][W] as egr_train_batch holds them (diffuse, specular, depth, normal, roughness, f0; NULL: zeros). Read by the batch backward only.
+    const float *batch_targets[6];
 };
 #define EGR_BATCH_CAM_FLOATS 16 // per view: origin (3), rows of w2c (9), tanf(fov / 2), pad (3)
 #define EGR_BATCH_CARRY_FLOATS (11 * EGR_NSTEPS) // running sums of a view across a chunk boundary, per pixel and step: rgb 3, depth 1, normal 3, f0 3, roughness 1
@@ -208,6 +211,12 @@ struct egr_context {
     float *batch_carry = nullptr;      // [EGR_BATCH_CARRY_FLOATS][H*W]
     float *batch_cams = nullptr;       // [batch_cams_cap + 1][EGR_BATCH_CAM_FLOATS] (the last record holds znear, zfar)
     uint32_t batch_cams_cap = 0;
+    // multi-view training (egr_train_views): the hit arena and per-task tables of a grad chunk, allocated by the first call, freed by egr_destroy. A batch
+    // has buffers of its own, so the debug exports (egr_debug_get_step_hits / _hit_sequence_hash) keep describing the last egr_raytrace
+    uint32_t train_alloc_frames = 0;   // frames the buffers below hold
+    float4 *train_arena = nullptr;     // train_blocks_cap blocks = train_alloc_frames x hit_blocks_cap (capped like the single-launch arena)
+    uint32_t train_blocks_cap = 0;
+    uint32_t *train_last_block = nullptr, *train_cost = nullptr, *train_order = nullptr; // task_last_block / task_cost / bwd_order for (tasks x frames)
     uint32_t num_tasks_total = 0; // 8x8 wave tiles in the whole image (a 16x16 macro tile = 4 of them = 256 rays of ray state)
     int team_help = 1;            // egr_set_team_help / env EGR_TEAM_HELP: 1 (default) = waves without tiles help their team mates' walks, 0 = never, -1 = only for under-filled ranks of a partition (egr_team_help_on)
     int rays_per_task = 0;        // 0: automatic (64; 32 for a rank of a partition with fewer than two 8x8 tiles per wave slot); env EGR_RAYS_PER_TASK
@@ -256,6 +265,7 @@ void egr_trace_alloc(egr_context *c);
 void egr_trace_free(egr_context *c);
 void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s);
 void egr_render_views_launch(egr_context *c, const egr_view_batch *b, bool live_fresh, hipStream_t s);
+void egr_train_views_launch(egr_context *c, const egr_train_batch *b, bool live_fresh, hipStream_t s);
 uint32_t egr_num_tasks_for_rank(const egr_context *c);
 void egr_build_task_order(egr_context *c);
 DeviceView egr_make_view(const egr_context *c);

@@ -53,6 +53,11 @@ EGR_DI TaskGeom task_geom(const DeviceView &v, uint32_t task, int lane) {
     if (v.pixel_mask != nullptr && g.inside) g.inside = v.pixel_mask[g.pixel_id] != 0; // (parity tests: trace a chosen set of pixels; wave-uniform branch)
     return g;
 }
+// (batches) the base task - the tile's pixels - of a task index that carries the frame: ((macro-tile group) * batch_frames + frame) << task_shift | sub-task
+EGR_DI uint32_t batch_base_task(const DeviceView &v, uint32_t task) {
+    const uint32_t grp = task >> v.task_shift;
+    return ((grp / v.batch_frames) << v.task_shift) | (task & ((1u << v.task_shift) - 1u));
+}
 // ray state of (task, lane): task-linear, rays_per_task entries per task (lanes beyond that own no ray and must not touch it)
 EGR_DI StateRef state_of(const DeviceView &v, uint32_t task, int lane) { return StateRef{v.state, v.state_stride, task * v.rays_per_task + (uint32_t)lane}; }
 

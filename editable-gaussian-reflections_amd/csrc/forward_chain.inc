@@ -1,5 +1,6 @@
-// k_forward_chain / k_forward_batch: the kernel body (included into both; expects GRADS, CUBE, TEAM and BATCH). A wave takes tiles from the
-// XCD queues and runs each through all its bounce steps. BATCH (no-grad frames of egr_render_views): task index tq =
+// k_forward_chain / k_forward_batch / k_forward_batch_grads: the kernel body (included into all three; expects GRADS, CUBE, TEAM and BATCH). A wave takes
+// tiles from the XCD queues and runs each through all its bounce steps. BATCH (the frames of egr_render_views, or with GRADS the views of egr_train_views,
+// which then record hits into the batch's own arena and per-task tables, sized for tasks x frames): task index tq =
 // ((macro-tile group) * batch_frames + frame) << task_shift | sub-task - the frames of one macro tile are adjacent, so the samples of a
 // tile run close in time on one XCD (the queue chunks are contiguous task ranges). The tile's pixels come from the base task `tb`, its ray
 // state from the full index.
@@ -67,7 +68,7 @@
 #endif
 #if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 9
         {
-            const TaskGeom ctg = task_geom(v, tq, lane);
+            const TaskGeom ctg = task_geom(v, tb, lane);
             if (lane <= EGR_NSTEPS && ctg.inside) v.stats.num_traversed_per_pixel[ctg.pixel_id] = (int32_t)(chain_t[lane] & 0x7FFFFFFFull);
             if (lane == 4 && ctg.inside) v.stats.num_traversed_per_pixel[ctg.pixel_id] = (int32_t)chain_leaves;
         }

@@ -4,7 +4,7 @@
         const uint32_t task = tq;
         const TaskGeom tg = task_geom(v, tb, lane); // (tb == tq outside a batch)
         const StateRef S = state_of(v, task, lane);
-        const size_t chain_head = (size_t)step * v.num_tasks + task;
+        const size_t chain_head = (size_t)step * (BATCH ? v.num_tasks * v.batch_frames : v.num_tasks) + task; // (a batch's task index carries the frame: its tables hold tasks x frames per step)
         if (GRADS && lane == 0) v.task_last_block[chain_head] = 0xFFFFFFFFu; // nothing recorded yet
 
         // ---- R1: ray for this step ----------------------------------------------------------------------

@@ -493,6 +493,35 @@ struct Raytracer : torch::CustomClassHolder {
         }
         check(egr_render_views(ctx, &b, current_stream()), "render_views");
     }
+    // multi-view training launch (egr_train_views): R [V,3,3], centers [V,3], fovy [V] as for render_views; the six targets are channel-major [V,C,H,W]
+    // fp32 tensors on the tracer's device (C = 3, depth / roughness 1; None or an empty tensor = absent = zeros). Adds the gradients of the V views to
+    // the gradient tensors (or the per-launch buffer: one grad launch for the whole batch) as V sequential raytrace() calls with grad mode on would.
+    void train_views(Tensor R, Tensor centers, Tensor fovy, double znear, double zfar, c10::optional<Tensor> diffuse, c10::optional<Tensor> specular,
+                     c10::optional<Tensor> depth, c10::optional<Tensor> normal, c10::optional<Tensor> roughness, c10::optional<Tensor> f0) {
+        TORCH_CHECK(R.dim() == 3 && R.size(1) == 3 && R.size(2) == 3, "train_views: R must be [V,3,3], got ", R.sizes());
+        const int64_t V = R.size(0);
+        TORCH_CHECK(centers.dim() == 2 && centers.size(0) == V && centers.size(1) == 3, "train_views: centers must be [V,3] = [", V, ",3], got ", centers.sizes());
+        TORCH_CHECK(fovy.dim() == 1 && fovy.size(0) == V, "train_views: fovy must be [V] = [", V, "], got ", fovy.sizes());
+        const auto dev = framebuffer_data->output_rgb.device();
+        Tensor r = R.to(dev, torch::kFloat32).contiguous(), cc = centers.to(dev, torch::kFloat32).contiguous(), fv = fovy.to(dev, torch::kFloat32).contiguous();
+        egr_train_batch b{};
+        b.num_views = (uint32_t)V;
+        b.rotation_c2w_dataset = r.data_ptr<float>(), b.camera_center = cc.data_ptr<float>(), b.vertical_fov_radians = fv.data_ptr<float>();
+        b.znear = (float)znear, b.zfar = (float)zfar;
+        const c10::optional<Tensor> *in[6] = {&diffuse, &specular, &depth, &normal, &roughness, &f0};
+        const char *names[6] = {"diffuse", "specular", "depth", "normal", "roughness", "f0"};
+        const int64_t ch[6] = {3, 3, 1, 3, 1, 3};
+        const float **slot[6] = {&b.target_diffuse, &b.target_specular, &b.target_depth, &b.target_normal, &b.target_roughness, &b.target_f0};
+        for (int k = 0; k < 6; k++) {
+            if (!in[k]->has_value() || !(*in[k])->defined() || (*in[k])->numel() == 0) continue;
+            const Tensor &t = **in[k];
+            const std::vector<int64_t> want{V, ch[k], height, width};
+            TORCH_CHECK(t.device() == dev && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.sizes() == torch::IntArrayRef(want), "train_views: target '", names[k],
+                        "' must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " (channel-major) on the tracer's device, got ", t.sizes(), " ", t.scalar_type(), " on ", t.device());
+            *slot[k] = t.data_ptr<float>();
+        }
+        check(egr_train_views(ctx, &b, current_stream()), "train_views");
+    }
     void set_batch_frames(int64_t n) { TORCH_CHECK(n >= 1 && n <= 0x7FFFFFFF && egr_set_batch_frames(ctx, (int)n) == 0, "set_batch_frames: a frame count >= 1 expected"); }
     void set_rays_per_task(int64_t n) { TORCH_CHECK(egr_set_rays_per_task(ctx, (int)n) == 0, "set_rays_per_task: 0 (automatic), 16, 32 or 64 expected"); }
     void set_team_help(bool on) { TORCH_CHECK(egr_set_team_help(ctx, on ? 1 : 0) == 0, "set_team_help failed"); }
@@ -599,6 +628,7 @@ struct Raytracer : torch::CustomClassHolder {
             .def("set_camera", &Raytracer::set_camera)
             .def("render_views", &Raytracer::render_views)
             .def("render_views_into", &Raytracer::render_views_into)
+            .def("train_views", &Raytracer::train_views)
             .def("set_batch_frames", &Raytracer::set_batch_frames)
             .def("set_exact_stats", &Raytracer::set_exact_stats)
             .def("set_strands", &Raytracer::set_strands)

@@ -704,6 +704,11 @@ template <bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM
     constexpr bool GRADS = false, BATCH = true;
 #include "forward_chain.inc"
 }
+// ... and for the views of a multi-view training launch (egr_train_views): one sample per view, hits recorded for the backward into the batch's own arena.
+template <bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribute__((amdgpu_waves_per_eu(EGR_FWD_WAVES, EGR_FWD_WAVES))) k_forward_batch_grads(DeviceView v) {
+    constexpr bool GRADS = true, BATCH = true;
+#include "forward_chain.inc"
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // backward: walked newest (farthest) hit first  (backward_pass.cu:3-222)
@@ -1040,86 +1045,13 @@ template <int TEAM> EGR_DI uint32_t bwd_team_help(const DeviceView &v, const flo
 }
 
 template <int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribute__((amdgpu_waves_per_eu(EGR_BWD_WAVES, EGR_BWD_WAVES))) k_backward_chain(DeviceView v) {
-    const int lane = threadIdx.x & (EGR_WAVE - 1);
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    __shared__ uint32_t gt_keys_all[TEAM][EGR_GT_SLOTS];
-    __shared__ __attribute__((aligned(16))) float gt_vals_all[TEAM][EGR_GT_STRIDE * EGR_GT_SLOTS];
-    __shared__ uint32_t gt_claim_all[TEAM][EGR_GT_SLOTS]; // which lane adds to a slot in this round (backward_task.inc)
-    __shared__ float4 stage_all[TEAM][4 * EGR_WAVE];     // records on their way out (wide_add_wave)
-    __shared__ BwdTeamShared<TEAM> bteam;
-    uint32_t *const gt_keys = gt_keys_all[wv], *const gt_claim = gt_claim_all[wv];
-    float *const gt_vals = gt_vals_all[wv];
-    float4 *const stage = stage_all[wv];
-    if (threadIdx.x == 0) bteam.done = 0u;
-    if (threadIdx.x < TEAM) bteam.ticket[threadIdx.x] = 0u, bteam.nitems[threadIdx.x] = 0u, bteam.finished[threadIdx.x] = 0u;
-    uint32_t bepoch = 0u;
-    // the two queues of the bounce steps live in the table's memory: the table is empty (flushed, all zero) while a tile's bounce steps run -
-    // they come before its primary step - and the words they dirtied are cleared again before that step (backward_task.inc).
-#define EGR_BQ_FLOATS (25 * EGR_WAVE) // floats of the table's memory the bounce steps use
-    static_assert(EGR_GT_STRIDE * EGR_GT_SLOTS >= EGR_BQ_FLOATS, "the bounce queues must fit into the table");
-    uint4 *bitems = reinterpret_cast<uint4 *>(gt_vals);  // [4 x 64] bounce steps: (ray, dL/dalpha, record, weight) of the hits of a chunk of four rows
-    float *bdl = gt_vals + 16 * EGR_WAVE;                // [3 x 64] bounce steps: the rays' radiance gradient
-    float *bray = gt_vals + 19 * EGR_WAVE;               // [6 x 64] bounce steps: the rays (origin, direction)
-    for (int s = lane; s < EGR_GT_SLOTS; s += EGR_WAVE) gt_keys[s] = EGR_GT_EMPTY;
-    for (int s = lane; s < EGR_GT_STRIDE * EGR_GT_SLOTS; s += EGR_WAVE) gt_vals[s] = 0.0f;
-    __syncthreads(); // the kernel's only workgroup barrier (a team's waves run independently from here on)
-    const float exp_power = *v.cfg.exp_power;
-    const float eps_scale_grad = *v.cfg.eps_scale_grad;
-    const int num_bounces = min(*v.cfg.num_bounces, EGR_MAX_BOUNCES);
-    const float view_size = tanf(*v.cam.vertical_fov_radians / 2.0f); // (primary_direction)
-    uint32_t cur_q = blockIdx.x & 7u;
-    uint32_t records = 0u; // 64-B gradient records this wave sent: bounce hits, primary hits without a table slot (two each), flushed table slots (two each) (egr_counters::bucket_records)
-
-    for (;;) {
-        const uint32_t tq = wave_next_task(v.queues + 8 * EGR_QUEUE_STRIDE, v.num_tasks, cur_q, lane);
-        if (tq == 0xFFFFFFFFu) break;
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 8 // diagnostic build: stamps of a task's BACKWARD chain in its first pixels (tools/bwd_times.py)
-        const unsigned long long bw_t0 = __builtin_amdgcn_s_memrealtime();
-        unsigned long long bw_t1 = 0ull;
-        uint32_t bw_rows0 = 0u;
-#endif
-        // The steps of a tile are independent in the backward (each reads its own arena chain and the forward's state, all gradients are
-        // atomic adds), so their order is free: the PRIMARY step goes first and the bounce steps last - the bounce steps' batches are what
-        // team mates can take (backward_task.inc), and team mates only have time once their own tiles are through, i.e. late in a heavy tile.
-        bool table_dirty = false; // (wave-uniform) a bounce step used the table's memory for its queues
-        {
-            constexpr bool PRIMARY = true;
-            const int step = 0;
-            do {
-#include "backward_task.inc"
-            } while (false);
-        }
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 8
-        bw_t1 = __builtin_amdgcn_s_memrealtime();
-#endif
-        for (int step = num_bounces; step >= 1; step--) {
-            constexpr bool PRIMARY = false;
-            do {
-#include "backward_task.inc"
-            } while (false);
-        }
-        if (table_dirty) { // (the table's memory held the bounce steps' queues: empty again for the next tile's primary step)
-            EGR_BWD_SYNC();
-            for (int s = lane; s < EGR_BQ_FLOATS; s += EGR_WAVE) gt_vals[s] = 0.0f;
-            EGR_BWD_SYNC();
-        }
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 8
-        {
-            const unsigned long long bw_t2 = __builtin_amdgcn_s_memrealtime();
-            const TaskGeom btg = task_geom(v, v.bwd_order[tq], lane);
-            if (btg.inside) {
-                if (lane == 0) v.stats.num_traversed_per_pixel[btg.pixel_id] = (int32_t)(bw_t0 & 0x7FFFFFFFull), v.stats.num_accumulated_per_pixel[btg.pixel_id] = (int32_t)(bw_t2 & 0x7FFFFFFFull);
-                if (lane == 1) v.stats.num_traversed_per_pixel[btg.pixel_id] = (int32_t)(bw_t1 & 0x7FFFFFFFull), v.stats.num_accumulated_per_pixel[btg.pixel_id] = (int32_t)bw_rows0;
-            }
-        }
-#endif
-    }
-    if constexpr (TEAM > 1) {
-        // no tiles left: this wave takes batches of bounce hits its team mates have queued until all of them are through
-        if (lane == 0) atomicAdd(&bteam.done, 1u);
-        records += bwd_team_help<TEAM>(v, exp_power, eps_scale_grad, bteam, gt_vals_all, stage, wv, lane);
-    }
-    if (lane == 0 && records) atomicAdd(v.control + CW_BUCKET_RECORDS, records);
+    constexpr bool BATCH = false;
+#include "backward_chain.inc"
+}
+// The same chain for the views of a multi-view training launch (egr_train_views). Its own kernel, so that the launches of egr_raytrace keep theirs.
+template <int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribute__((amdgpu_waves_per_eu(EGR_BWD_WAVES, EGR_BWD_WAVES))) k_backward_batch(DeviceView v) {
+    constexpr bool BATCH = true;
+#include "backward_chain.inc"
 }
 
 // Last backward kernel: one thread per gaussian id adds its gradient row (a 128-B line at its record position) to the
@@ -1226,20 +1158,21 @@ __global__ void k_batch_cameras(const float *__restrict__ R, const float *__rest
     rec[12] = tanf(fov[i] / 2.0f);
     rec[13] = rec[14] = rec[15] = 0.0f;
 }
-// k_prologue for a batch: the per-launch control words, grads_enabled = 0; total_num_calls stays as it is until k_batch_epilogue (the
-// chunks derive every frame's seed from it).
-__global__ void k_batch_prologue(DeviceView v) {
+// k_prologue for a batch: the per-launch control words, grads_enabled = grads (0: egr_render_views, 1: egr_train_views); total_num_calls stays as it is
+// until k_batch_epilogue (the chunks derive every frame's seed from it).
+__global__ void k_batch_prologue(DeviceView v, int grads) {
     const int t = threadIdx.x;
     if (t < CW_RESET_END) v.control[t] = 0;
     for (int w = CW_DBG + t; w < CW_COUNT; w += (int)blockDim.x) v.control[w] = 0;
     if (t < 12) v.control[CW_DBG3 + t] = ((t & 3) < 2) ? 0xFFFFFFFFu : 0u;
-    if (t == 0) *v.meta.grads_enabled = 0;
+    if (t == 0) *v.meta.grads_enabled = grads ? 1 : 0;
 }
-// every chunk: fresh task queues and extension blocks (the lists of the previous chunk's tiles are done with)
+// every chunk: fresh task queues of both chains, extension blocks and hit-arena blocks (the lists and hits of the previous chunk's tiles are done with:
+// its backward ran before this chunk's forward)
 __global__ void k_batch_chunk_begin(DeviceView v) {
     const int t = threadIdx.x;
     for (uint32_t q = t; q < EGR_QUEUE_WORDS; q += blockDim.x) v.queues[q] = 0;
-    if (t == 0) v.control[CW_EXT_BUMP] = 0;
+    if (t == 0) v.control[CW_EXT_BUMP] = 0, v.control[CW_HIT_BUMP] = 0;
 }
 __global__ void k_batch_epilogue(DeviceView v, uint32_t frames) {
     if (threadIdx.x == 0) {
@@ -1508,6 +1441,8 @@ void egr_build_task_order(egr_context *c) {
 void egr_trace_free(egr_context *c) {
     egr_dev_free(c, c->batch_state), egr_dev_free(c, c->batch_carry), egr_dev_free(c, c->batch_cams);
     c->batch_alloc_frames = 0, c->batch_cams_cap = 0;
+    egr_dev_free(c, c->train_arena), egr_dev_free(c, c->train_last_block), egr_dev_free(c, c->train_cost), egr_dev_free(c, c->train_order);
+    c->train_alloc_frames = 0, c->train_blocks_cap = 0;
     for (auto &o : c->task_orders) egr_dev_free(c, o.table);
     c->task_orders.clear(), c->task_macro = nullptr;
     egr_dev_free(c, c->stack_spill), egr_dev_free(c, c->cand_keys), egr_dev_free(c, c->cand_vals), egr_dev_free(c, c->hit_arena), egr_dev_free(c, c->task_last_block), egr_dev_free(c, c->task_cost), egr_dev_free(c, c->bwd_order), egr_dev_free(c, c->state), egr_dev_free(c, c->control), egr_dev_free(c, c->queues), egr_dev_free(c, c->denoise_tmp), egr_dev_free(c, c->ext_keys), egr_dev_free(c, c->ext_vals);
@@ -1666,26 +1601,32 @@ void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s
     hipLaunchKernelGGL(k_epilogue, dim3(1), dim3(64), 0, s, v, grads ? 1 : 0);
 }
 
-// egr_render_views: V x S frames in chunks of B = min(V x S, batch_frames) frames, in frame order. Each chunk is one forward chain over
-// (this rank's tasks) x B and one k_finish_batch; the per-launch work of a single frame - prologue, stats reset, k_live, epilogue - runs
-// once per batch.
-void egr_render_views_launch(egr_context *c, const egr_view_batch *b, bool live_fresh, hipStream_t s) {
-    const uint32_t V = b->num_views, F = b->num_views * b->samples_per_view;
-    const uint32_t B = std::min(F, std::max(1u, c->batch_frames));
+// The buffers every batch needs: the ray state of B frames and the camera records of V views (allocated by the first batch call; they grow with a
+// larger chunk / view count).
+static void egr_batch_reserve(egr_context *c, uint32_t B, uint32_t V) {
     if (c->batch_alloc_frames < B || c->batch_cams_cap < V) EGR_HIP(hipDeviceSynchronize()); // (kernels in flight may still read the buffers replaced below)
-    if (c->batch_alloc_frames < B) { // ray state of B frames (allocated by the first batch call; grows with a larger chunk)
+    if (c->batch_alloc_frames < B) {
         egr_dev_free(c, c->batch_state);
         c->batch_alloc_frames = 0;
         egr_dev_alloc_raw(c, (void **)&c->batch_state, (size_t)F_TOTAL * B * c->state_stride * sizeof(float));
         c->batch_alloc_frames = B;
     }
-    if (!c->batch_carry) egr_dev_alloc(c, c->batch_carry, (size_t)EGR_BATCH_CARRY_FLOATS * c->width * c->height);
     if (c->batch_cams_cap < V) {
         egr_dev_free(c, c->batch_cams);
         c->batch_cams_cap = 0;
         egr_dev_alloc(c, c->batch_cams, (size_t)(V + 1) * EGR_BATCH_CAM_FLOATS);
         c->batch_cams_cap = V;
     }
+}
+
+// egr_render_views: V x S frames in chunks of B = min(V x S, batch_frames) frames, in frame order. Each chunk is one forward chain over
+// (this rank's tasks) x B and one k_finish_batch; the per-launch work of a single frame - prologue, stats reset, k_live, epilogue - runs
+// once per batch.
+void egr_render_views_launch(egr_context *c, const egr_view_batch *b, bool live_fresh, hipStream_t s) {
+    const uint32_t V = b->num_views, F = b->num_views * b->samples_per_view;
+    const uint32_t B = std::min(F, std::max(1u, c->batch_frames));
+    egr_batch_reserve(c, B, V);
+    if (!c->batch_carry) egr_dev_alloc(c, c->batch_carry, (size_t)EGR_BATCH_CARRY_FLOATS * c->width * c->height);
     DeviceView v = egr_make_view(c);
     v.state = c->batch_state, v.state_stride = c->state_stride * c->batch_alloc_frames;
     v.batch_cams = c->batch_cams, v.batch_spv = b->samples_per_view, v.batch_last_frame = F - 1u;
@@ -1693,7 +1634,7 @@ void egr_render_views_launch(egr_context *c, const egr_view_batch *b, bool live_
     const BatchOutputs out{b->final, b->rgb, b->depth, b->normal, b->f0, b->roughness};
     egr_stamp_begin(c, "prologue+live", s);
     hipLaunchKernelGGL(k_batch_cameras, dim3((V + 64u) / 64u), dim3(64), 0, s, b->rotation_c2w_dataset, b->camera_center, b->vertical_fov_radians, V, b->znear, b->zfar, c->batch_cams);
-    hipLaunchKernelGGL(k_batch_prologue, dim3(1), dim3(64), 0, s, v);
+    hipLaunchKernelGGL(k_batch_prologue, dim3(1), dim3(64), 0, s, v, 0);
     EGR_HIP(hipMemsetAsync(c->stats.num_accumulated_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
     EGR_HIP(hipMemsetAsync(c->stats.num_traversed_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
     if (v.n && !live_fresh) hipLaunchKernelGGL(k_live, dim3((v.n + 255) / 256), dim3(256), 0, s, v, 0);
@@ -1718,6 +1659,75 @@ void egr_render_views_launch(egr_context *c, const egr_view_batch *b, bool live_
         egr_stamp_end(c, s);
     }
     hipLaunchKernelGGL(k_batch_epilogue, dim3(1), dim3(64), 0, s, v, F);
+}
+
+// egr_train_views: V views (one sample each) in chunks of B = min(V, batch_frames) frames. Per chunk: the forward chain over (this rank's tasks) x B, which
+// records every frame's hits into the batch arena, k_order_backward over the same (tasks x frames), and the backward chain over them - all three with the
+// frame in the task index. Prologue, stats reset, k_live, k_grad_gather and the epilogue run once per call, so the chunks' gradients meet in the gradient
+// rows and leave them in ONE gather (the whole batch is one grad launch for the per-launch buffer).
+void egr_train_views_launch(egr_context *c, const egr_train_batch *b, bool live_fresh, hipStream_t s) {
+    const uint32_t V = b->num_views;
+    const uint32_t B = std::min(V, std::max(1u, c->batch_frames));
+    egr_batch_reserve(c, B, V);
+    if (c->train_alloc_frames < B) { // hit arena (B x the single launch's) and per-task tables of a chunk of B frames
+        EGR_HIP(hipDeviceSynchronize());
+        egr_dev_free(c, c->train_arena), egr_dev_free(c, c->train_last_block), egr_dev_free(c, c->train_cost), egr_dev_free(c, c->train_order);
+        c->train_alloc_frames = 0, c->train_blocks_cap = 0;
+        const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)c->hit_blocks_cap * B, 0x7FFFFFFFull);
+        egr_dev_alloc_raw(c, (void **)&c->train_arena, (size_t)cap * (EGR_HIT_BLOCK_ROWS + 1) * EGR_WAVE * sizeof(float4));
+        const size_t tasks = (size_t)4u * c->num_tasks_total * B; // (up to 16 tasks per macro tile, as the single launch's tables)
+        egr_dev_alloc(c, c->train_last_block, (size_t)EGR_NSTEPS * tasks);
+        egr_dev_alloc(c, c->train_cost, tasks);
+        egr_dev_alloc(c, c->train_order, tasks);
+        c->train_alloc_frames = B, c->train_blocks_cap = cap;
+    }
+    DeviceView v = egr_make_view(c);
+    v.state = c->batch_state, v.state_stride = c->state_stride * c->batch_alloc_frames;
+    v.batch_cams = c->batch_cams, v.batch_spv = 1u, v.batch_last_frame = V - 1u;
+    v.cam.znear = c->batch_cams + (size_t)V * EGR_BATCH_CAM_FLOATS, v.cam.zfar = v.cam.znear + 1;
+    v.hit_arena = c->train_arena, v.hit_blocks_cap = c->train_blocks_cap, v.task_last_block = c->train_last_block, v.task_cost = c->train_cost, v.bwd_order = c->train_order;
+    const float *const tgt[6] = {b->target_diffuse, b->target_specular, b->target_depth, b->target_normal, b->target_roughness, b->target_f0};
+    for (int k = 0; k < 6; k++) v.batch_targets[k] = tgt[k];
+    egr_stamp_begin(c, "prologue+live", s);
+    hipLaunchKernelGGL(k_batch_cameras, dim3((V + 64u) / 64u), dim3(64), 0, s, b->rotation_c2w_dataset, b->camera_center, b->vertical_fov_radians, V, b->znear, b->zfar, c->batch_cams);
+    hipLaunchKernelGGL(k_batch_prologue, dim3(1), dim3(64), 0, s, v, 1);
+    EGR_HIP(hipMemsetAsync(c->stats.num_accumulated_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
+    EGR_HIP(hipMemsetAsync(c->stats.num_traversed_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
+    if (v.n && !live_fresh) hipLaunchKernelGGL(k_live, dim3((v.n + 255) / 256), dim3(256), 0, s, v, 1);
+    egr_stamp_end(c, s);
+    for (uint32_t f0 = 0; f0 < V && v.num_tasks; f0 += B) {
+        v.batch_frame0 = f0, v.batch_frames = std::min(B, V - f0);
+        hipLaunchKernelGGL(k_batch_chunk_begin, dim3(1), dim3(64), 0, s, v);
+        const uint32_t tasks = v.num_tasks * v.batch_frames;
+        const dim3 sgrid(std::max(1u, std::min(c->num_slots, tasks)));
+        egr_stamp_begin(c, "forward_chain", s);
+        auto launch_forward = [&](auto team_tag) {
+            constexpr uint32_t T = (uint32_t) decltype(team_tag)::value;
+            const dim3 fgrid((sgrid.x + T - 1u) / T), fblock(EGR_WAVE * T);
+            if (v.cube_mode) hipLaunchKernelGGL((k_forward_batch_grads<true, (int)T>), fgrid, fblock, 0, s, v);
+            else hipLaunchKernelGGL((k_forward_batch_grads<false, (int)T>), fgrid, fblock, 0, s, v);
+        };
+        if (v.team_help) launch_forward(std::integral_constant<int, EGR_TEAM>{});
+        else launch_forward(std::integral_constant<int, 1>{});
+        egr_stamp_end(c, s);
+        DeviceView ov = v; // k_order_backward sorts every queue chunk of the (tasks x frames) range, the chunks the backward's wave_next_task hands out
+        ov.num_tasks = tasks;
+        hipLaunchKernelGGL(k_order_backward, dim3(8), dim3(256), 0, s, ov);
+        egr_stamp_begin(c, "backward_chain", s);
+        // (the team rule of egr_trace_launch, applied to the chunk's tiles)
+        const bool backward_teams = v.team_help == 1 || (c->world > 1 && (uint64_t)(tasks >> (v.task_shift - 2u)) < 2ull * c->num_slots);
+        if (backward_teams) hipLaunchKernelGGL(k_backward_batch<EGR_BWD_TEAM>, dim3((sgrid.x + EGR_BWD_TEAM - 1u) / EGR_BWD_TEAM), dim3(EGR_WAVE * EGR_BWD_TEAM), 0, s, v);
+        else hipLaunchKernelGGL(k_backward_batch<1>, sgrid, dim3(EGR_WAVE), 0, s, v);
+        egr_stamp_end(c, s);
+    }
+    if (v.n && (v.num_tasks || c->grad_overwrite)) { // (as egr_trace_launch: a rank without tiles still owes its per-launch buffer a row of zeros)
+        egr_stamp_begin(c, "backward_grad_gather", s);
+        if (v.grad_overwrite) hipLaunchKernelGGL(k_grad_gather<true>, dim3((v.n + 255u) / 256u), dim3(256), 0, s, v);
+        else hipLaunchKernelGGL(k_grad_gather<false>, dim3((v.n + 255u) / 256u), dim3(256), 0, s, v);
+        egr_stamp_end(c, s);
+        if (c->grad_overwrite) c->delta_pending = true;
+    }
+    hipLaunchKernelGGL(k_batch_epilogue, dim3(1), dim3(64), 0, s, v, V);
 }
 
 void egr_export_step_hits(egr_context *c, int32_t *host_out, hipStream_t s) {

@@ -289,6 +289,41 @@ def render_views(cameras, raytracer: GaussianRaytracer, spp=1, outputs=VIEW_OUTP
     return views
 
 
+TRAIN_TARGETS = (("diffuse", "diffuse_image", 3), ("specular", "specular_image", 3), ("depth", "depth_image", 1), ("normal", "normal_image", 3),
+                 ("roughness", "roughness_image", 1), ("f0", "f0_image", 3))
+
+
+def train_views(cameras, raytracer: GaussianRaytracer, targets_available=True, znear=0.01, zfar=999.9):
+    """Multi-view training launch (egr_train_views): the grad branch of `GaussianRaytracer.__call__` for every camera of `cameras` at once. The
+    parameters are exported and the tree refitted ONCE (all views share them), one launch adds the gradients of all views, then the gradient
+    exchange of a partitioned tracer (`all_reduce_grads`) and the import into the parameters' .grad (when `import_grads`) run once. The targets come
+    from each camera's *_image attributes as `render` takes them (CHW; absent, or targets_available=False: zeros). Leaves in the gradients what
+    `render(cam)` with grad mode on leaves summed over the cameras, and advances total_num_calls by len(cameras); writes no images. NOTE: the
+    gradient is the SUM over the views and total_weight grows by all of them (a V-view training step)."""
+    cameras = list(cameras)
+    m = raytracer.cuda_module
+    W, H = raytracer.image_width, raytracer.image_height
+    with torch.no_grad():
+        as_t = lambda x: torch.from_numpy(np.asarray(x)).float() if isinstance(x, np.ndarray) else torch.as_tensor(x).float()
+        R = torch.stack([as_t(c.R).cuda() for c in cameras]) if cameras else torch.zeros((0, 3, 3), device="cuda")
+        centers = torch.stack([as_t(c.camera_center).cuda() for c in cameras]) if cameras else torch.zeros((0, 3), device="cuda")
+        fovy = torch.tensor([float(c.FoVy) for c in cameras], dtype=torch.float32, device="cuda")
+        targets = []
+        for _, attr, ch in TRAIN_TARGETS:
+            imgs = [getattr(c, attr, None) if targets_available else None for c in cameras]
+            if all(t is None for t in imgs):
+                targets.append(None)  # absent for every view: the library reads zeros
+                continue
+            zeros = torch.zeros((ch, H, W), dtype=torch.float32, device="cuda")
+            targets.append(torch.stack([zeros if t is None else torch.as_tensor(t).to("cuda", torch.float32) for t in imgs]).contiguous())
+        raytracer._export_param_values()
+        m.update_bvh(True)  # the launch follows with the same parameter values (fused live records)
+        m.train_views(R, centers, fovy, float(os.getenv("ZNEAR", znear)), float(os.getenv("ZFAR", zfar)), *targets)
+    raytracer.all_reduce_grads()
+    if raytracer.import_grads:
+        raytracer._import_param_gradients()
+
+
 def camera_from_RT(R, T, FoVy, device="cuda", **images):
     """What scene/cameras.py:22-152 holds for a view, from the dataset's (R, T, FovY) (dataset/blender_dataset.py:62-75: R is the
     camera-to-world rotation in COLMAP axes - "stored transposed" -, T the world-to-camera translation): `R` unchanged, `FoVy`, and

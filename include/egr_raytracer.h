@@ -269,8 +269,46 @@ typedef struct egr_view_batch {
  * (444 B per pixel and frame) is allocated by the first call and counted in egr_counters.device_bytes from then on. Wrong arguments (V == 0,
  * S == 0, a NULL final or a NULL camera array) return non-zero with an egr_last_error message and write nothing. */
 int egr_render_views(egr_context *ctx, const egr_view_batch *batch, void *hip_stream);
-/* Frames per launch of egr_render_views (default 8; env EGR_BATCH_FRAMES at creation). Returns 1 for values < 1. */
+/* Frames per launch of egr_render_views and egr_train_views (default 8; env EGR_BATCH_FRAMES at creation). Returns 1 for values < 1. */
 int egr_set_batch_frames(egr_context *ctx, int frames);
+
+/* Multi-view training launch (not in the reference; an additive symbol of library version 0.8, egr_version() is unchanged): the gradients of V views,
+ * one sample each, in as few launches as the ray state allows. After the call the context is in the state V sequential egr_raytrace(grads_enabled = 1)
+ * calls leave, where call v has camera v and targets v bound. In detail:
+ *   - gradients: the dL_d* tensors and total_weight gain the sum over the views (equal up to the order of the float atomic adds). With
+ *     egr_set_grad_overwrite the whole batch is ONE grad launch: the first after egr_grad_delta_consumed stores, any later one adds;
+ *   - seeds: metadata.total_num_calls advances by V; view v draws its seeds from (value before the call) + v + 1, as in egr_render_views;
+ *   - stats.* and metadata.random_seeds hold what the LAST view's launch would leave (bit for bit when team help is off); grads_enabled is set to 1;
+ *   - egr_counters: rays / candidates / composited / accepted / bucket_records are sums over the views, status is ORed over them,
+ *     lifetime_launches grows by V; arena_blocks_used is what the last chunk took of the batch arena (see below);
+ *   - NOT touched: the framebuffer (outputs - a grad launch writes none, shaders.cu:155-169 -, accumulators, accumulated_sample_count: accumulate_samples
+ *     is ignored as in egr_render_views - and the target buffers) and the bound camera;
+ *   - the BVH gates (stale tree, changed exact-stats flag), the partition (a rank traces its own tiles of every view), the debug pixel mask, team help
+ *     (both chains' team builds are chosen as for egr_raytrace) and the exact-statistics build behave as for egr_raytrace;
+ *   - debug exports: a batch traces into buffers of its own, so egr_debug_get_step_hits and egr_debug_get_hit_sequence_hash keep describing the
+ *     last egr_raytrace with grads_enabled.
+ * Targets are channel-major like egr_set_targets_chw's, one image per view; NULL = the target is absent and reads zero (the reference zeroes the buffer).
+ * The camera arrays use the dataset convention of egr_set_camera_from_dataset. */
+typedef struct egr_train_batch {
+    uint32_t num_views;               /* V >= 1 */
+    const float *rotation_c2w_dataset; /* [V][3][3] device pointer: the dataset's camera-to-world rotations (viewpoint_camera.R) */
+    const float *camera_center;       /* [V][3] device pointer */
+    const float *vertical_fov_radians; /* [V] device pointer */
+    float znear;
+    float zfar;
+    const float *target_diffuse;      /* [V][3][H][W] or NULL */
+    const float *target_specular;     /* [V][3][H][W] or NULL */
+    const float *target_depth;        /* [V][1][H][W] or NULL */
+    const float *target_normal;       /* [V][3][H][W] or NULL */
+    const float *target_roughness;    /* [V][1][H][W] or NULL */
+    const float *target_f0;           /* [V][3][H][W] or NULL */
+} egr_train_batch;
+/* Asynchronous on the stream. Runs in chunks of min(V, batch frames) views (egr_set_batch_frames). The first call allocates, counted in
+ * egr_counters.device_bytes from then on: the ray state of a chunk (shared with egr_render_views: 444 B per pixel and frame), a composited-hit arena of
+ * (batch frames) x the single-launch arena (so a view whose hits fit one egr_raytrace also fits inside a chunk; an overflow is still flagged,
+ * EGR_STATUS_HIT_ARENA_OVERFLOW, never silent) and 80 B per 8x8 tile and frame of per-task tables. Wrong arguments (V == 0, a NULL camera array), a stale
+ * tree and the exact-stats gate return non-zero with an egr_last_error message and write nothing. */
+int egr_train_views(egr_context *ctx, const egr_train_batch *batch, void *hip_stream);
 
 /* Synchronises the stream and returns the work counters / status of the most recent egr_raytrace.
  * ABI: egr_counters only ever GROWS AT ITS END (version string of egr_version() bumps with it). egr_get_counters writes
