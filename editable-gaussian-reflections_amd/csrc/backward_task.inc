@@ -81,10 +81,10 @@
             T_minus_Ttot = S.ld(SF(step, S_T)) - S.ld(SF(step, S_TTOT));
         }
 
-        // ---- the geometry half of B2 for one hit (backward_pass.cu:151-205): components 0 .. 10 of its gradient (opacity, scale, mean,
-        // rotation) from the record position, the ray, the live (.., opacity, sigma) quarter and dL/dalpha. Independent of the other hits of
-        // the ray - the sequential half (suffix sums -> dL/dalpha) is the caller's.
-        auto hit_geometry = [&](uint32_t pos, const float4 &a2, const f3 &ro, const f3 &rd, float dL_dalpha, auto &gx) { hit_geometry_fn(v, exp_power, eps_scale_grad, pos, a2, ro, rd, dL_dalpha, gx); };
+        // ---- the geometry half of B2 for one PRIMARY hit (trace.hip: hit_geometry_fn): opacity, mean and the six components of Q from the record
+        // position, the ray, the live (.., opacity, sigma) quarter and dL/dalpha. Independent of the other hits of the ray - the sequential half
+        // (suffix sums -> dL/dalpha) is the caller's. (A bounce hit: bounce_batch.)
+        auto hit_geometry = [&](uint32_t pos, const float4 &a2, const f3 &ro, const f3 &rd, float dL_dalpha, auto &gx) { hit_geometry_fn<true>(v, exp_power, eps_scale_grad, pos, a2, ro, rd, dL_dalpha, gx); };
 
         // ---- B2 of a BOUNCE step in two passes per chunk of four hit rows. A row of the arena holds the it-th hit of every ray, and rays
         // end at different depths: with one lane per RAY a row costs the full per-hit arithmetic however few rays still have a hit (58 %
@@ -168,7 +168,7 @@
             }
             continue; // this step of this tile is done
         }
-        // ---- B2: per-hit chain -------------------------------------------------------------------------
+        // ---- B2 of the PRIMARY step (a bounce step has left through the `continue` above): per-hit chain -------------------------------------------------------------------------
         f3 prev_rgb = mk3(0, 0, 0), w_rgb = mk3(0, 0, 0), prev_n = mk3(0, 0, 0), w_n = mk3(0, 0, 0), prev_f0 = mk3(0, 0, 0), w_f0 = mk3(0, 0, 0);
         float prev_rough = 0, w_rough = 0, prev_depth = 0, w_depth = 0;
         const uint32_t nblocks = (max_hits + EGR_HIT_BLOCK_ROWS - 1) / EGR_HIT_BLOCK_ROWS;
@@ -185,10 +185,10 @@
             for (int row = EGR_HIT_BLOCK_ROWS - 1; row >= 0; row--) {
                 const uint32_t it = b * EGR_HIT_BLOCK_ROWS + (uint32_t)row;
                 if (it >= max_hits) continue;
-                // a bounce hit leaves the divergent block with its gradients in `dg`: the wide add that follows is a wave-level operation
+                // a hit without a table slot leaves the divergent block with its gradients in `gx`: the wide add that follows is a wave-level operation
                 bool direct = false, want = false; // want: this lane's contribution looks for a slot of the table
                 uint32_t dpos = 0;
-                float gx[EGR_GT_COMPS]; // this hit's gradient components (what leaves the lane when `direct`: 15 of a bounce hit, 22 of a primary hit without a table slot)
+                float gx[EGR_GT_COMPS]; // this hit's gradient components, PC_* order (what leaves the lane when `direct`: a primary hit without a table slot)
                 EGR_BT(const unsigned long long bt0 = __builtin_amdgcn_s_memtime(); unsigned long long bt1 = bt0; bt_rows++;)
                 // a row costs two dependent round trips - its arena entry, then the records the entry names: the NEXT row's entry is requested now
                 // (the request comes first and the rare direct load - the first row of a block - completes inside its own branch: with the two the other
@@ -219,7 +219,7 @@
 
                     w_rgb = w_rgb + (g_rgb - prev_rgb) * transmittance; // :118-132
                     prev_rgb = g_rgb;
-                    if (PRIMARY) {
+                    {
                         f3 g_n = mk3(a0.w, a1.x, a1.y), g_f0 = mk3(a1.z, a1.w, a2.x);
                         w_n = w_n + (g_n - prev_n) * transmittance;
                         prev_n = g_n;
@@ -245,41 +245,36 @@
                     dL_dalpha += tmp2 * (rem_rough * dL_rough);
                     dL_dalpha += tmp2 * (rem_depth * dL_depth);
 
-                    hit_geometry(pos, a2, ro, rd, dL_dalpha, gx); // components 0 .. 10 (opacity, scale, mean, rotation)
-                    gx[GC_RGB] = d_rgb.x, gx[GC_RGB + 1] = d_rgb.y, gx[GC_RGB + 2] = d_rgb.z, gx[GC_WEIGHT] = weight;
-                    gx[GC_NORMAL] = d_n.x, gx[GC_NORMAL + 1] = d_n.y, gx[GC_NORMAL + 2] = d_n.z;
-                    gx[GC_F0] = d_f0.x, gx[GC_F0 + 1] = d_f0.y, gx[GC_F0 + 2] = d_f0.z, gx[GC_ROUGH] = d_rough;
+                    hit_geometry(pos, a2, ro, rd, dL_dalpha, gx); // opacity, mean, Q
+                    gx[PC_RGB] = d_rgb.x, gx[PC_RGB + 1] = d_rgb.y, gx[PC_RGB + 2] = d_rgb.z, gx[PC_WEIGHT] = weight;
+                    gx[PC_NORMAL] = d_n.x, gx[PC_NORMAL + 1] = d_n.y, gx[PC_NORMAL + 2] = d_n.z;
+                    gx[PC_F0] = d_f0.x, gx[PC_F0 + 1] = d_f0.y, gx[PC_F0 + 2] = d_f0.z, gx[PC_ROUGH] = d_rough;
                     EGR_BT(bt1 = __builtin_amdgcn_s_memtime();)
                     // primary hits go through the wave's LDS table (trace.hip: primary_presum here, primary_table_add below, outside this divergent
-                    // block: a full table is emptied by the whole wave). Bounce tiles are incoherent (an LDS table removed only 25 % of the
-                    // contributions at 15 ds_add_f32 per hit): the 15 components go straight to the gaussian's gradient row as one 16-lane record
+                    // block: a full table is emptied by the whole wave). (Bounce tiles are incoherent - an LDS table removed only 25 % of the
+                    // contributions at 15 ds_add_f32 per hit: bounce_batch sends a hit's 15 components straight to the gradient row as one record.)
                     dpos = pos;
-                    if (PRIMARY) want = primary_presum(pos, gx, lane);
-                    else direct = true;
+                    want = primary_presum(pos, gx, lane);
                 }
-                if (PRIMARY) direct = primary_table_add(v, want, dpos, gx, gt_keys, gt_vals, gt_claim, stage, lane, records);
+                direct = primary_table_add(v, want, dpos, gx, gt_keys, gt_vals, gt_claim, stage, lane, records);
                 EGR_BT(const unsigned long long bt2 = __builtin_amdgcn_s_memtime(); bt_math += bt1 - bt0; bt_table += bt2 - bt1;)
                 if (__ballot(direct) != 0ull) {
                     float lo[15];
 #pragma unroll
                     for (int c = 0; c < 15; c++) lo[c] = gx[c];
-                    wide_add_wave(v, direct, dpos, lo, 0u, stage);
-                    if (PRIMARY) {
-                        float hi[15];
+                    wide_add_wave<REC_PRIMARY_A>(v, direct, dpos, lo, stage);
+                    float hi[15];
 #pragma unroll
-                        for (int c = 0; c < 15; c++) hi[c] = (15 + c < EGR_GT_COMPS) ? gx[(15 + c < EGR_GT_COMPS) ? 15 + c : 0] : 0.0f;
-                        wide_add_wave(v, direct, dpos, hi, 15u, stage);
-                        records += 2u * (uint32_t)__popcll(__ballot(direct));
-                    } else {
-                        records += (uint32_t)__popcll(__ballot(direct));
-                    }
+                    for (int c = 0; c < 15; c++) hi[c] = (15 + c < EGR_GT_COMPS) ? gx[(15 + c < EGR_GT_COMPS) ? 15 + c : 0] : 0.0f;
+                    wide_add_wave<REC_PRIMARY_Q>(v, direct, dpos, hi, stage);
+                    records += 2u * (uint32_t)__popcll(__ballot(direct));
                 }
                 EGR_BT(bt_wide += __builtin_amdgcn_s_memtime() - bt2;)
             }
             blk = f2u(rows[0].x); // header: previous (older) block of this chain
         }
         EGR_BT(const unsigned long long bt3 = __builtin_amdgcn_s_memtime();)
-        if (PRIMARY) records += grad_table_flush(v, gt_keys, gt_vals, stage, lane); // one flush per tile
+        records += grad_table_flush(v, gt_keys, gt_vals, stage, lane); // one flush per tile
 #ifdef EGR_TRAVERSAL_STATS
         if (lane == 0) {
             unsigned long long *d = reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 16 + (PRIMARY ? 0 : 10));

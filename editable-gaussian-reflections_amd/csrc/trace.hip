@@ -123,7 +123,6 @@ EGR_DI float egr_dot3(float ax, float ay, float az, float bx, float by, float bz
 EGR_DI float egr_madd(float a, float b, float c) { // a b + c
     return __builtin_fmaf(a, b, c);
 }
-EGR_DI f3 egr_div3_rn(const f3 &a, const f3 &b, const f3 &r) { return mk3(egr_div_rn(a.x, b.x, r.x), egr_div_rn(a.y, b.y, r.y), egr_div_rn(a.z, b.z, r.z)); } // a / b per component, r = refined reciprocals of b
 EGR_DI float egr_gaussian_sq(float sq, float exp_power) { // eval_gaussian_sq (kernel.cu:8-12) with the division by the launch constant 2p spelled out: its reciprocal is loop-invariant
     const float two_p = 2.0f * exp_power;
     return expf(egr_div_rn(-pow_exp(sq, exp_power), two_p, egr_rcp_refined(two_p)));
@@ -721,21 +720,34 @@ template <bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM
                         // (round 4) a smaller one is as good: 64 / 72 / 80 / 94 slots -> 3.02 / 3.05 / 3.01-3.03 / 3.11 ms backward chain
                         // dense-init (same box). Before that: 94 beat 64 (hits without a slot left as records of their own), 128 and 256 cost waves per CU
 #endif
-#define EGR_GT_COMPS 22
-#define EGR_GT_STRIDE 23 // floats per table slot ([slot][component], odd stride: lanes on different slots fall on different LDS banks)
+#define EGR_GT_COMPS 21
+#define EGR_GT_STRIDE 21 // floats per table slot ([slot][component], odd stride: lanes on different slots fall on different LDS banks)
 #define EGR_GT_EMPTY 0xFFFFFFFFu
-// component order of the LDS table, of a wide-add record (first 15) and of a gradient row (DeviceView::grad_rows)
-enum : int { GC_OPA = 0, GC_SCALE = 1, GC_MEAN = 4, GC_ROT = 7, GC_RGB = 11, GC_WEIGHT = 14, GC_NORMAL = 15, GC_F0 = 18, GC_ROUGH = 21 };
+// cell order of a gradient row (DeviceView::grad_rows; 28 of its 32 floats used) and, cells 0-14, of a BOUNCE hit's wide-add record. A bounce hit adds its
+// finished d_scale / d_rot to GC_SCALE / GC_ROT; a PRIMARY hit leaves those cells alone and adds the six components of its symmetric local matrix Q
+// (hit_geometry_fn) to GC_Q - k_grad_gather applies the scale / rotation chain to their sum, once per gaussian.
+enum : int { GC_OPA = 0, GC_SCALE = 1, GC_MEAN = 4, GC_ROT = 7, GC_RGB = 11, GC_WEIGHT = 14, GC_NORMAL = 15, GC_F0 = 18, GC_ROUGH = 21, GC_Q = 22 };
+// component order of a PRIMARY hit: the LDS table and the two records a slot (or a hit without a slot) leaves as - A = components 0-14, B = Q (15-20: xx xy xz yy yz zz)
+enum : int { PC_OPA = 0, PC_MEAN = 1, PC_RGB = 4, PC_WEIGHT = 7, PC_NORMAL = 8, PC_F0 = 11, PC_ROUGH = 14, PC_Q = 15 };
+// which cells of the gradient row the 15 values of a record go to
+enum : int { REC_BOUNCE = 0, REC_PRIMARY_A = 1, REC_PRIMARY_Q = 2 };
 #define EGR_ROW_STRIDE 32 // floats per gradient row: one 128-B line per gaussian
 #define EGR_BWD_SYNC() wave_sync() // the backward chain's waves run independently (like the forward's): phases that exchange data through LDS within ONE wave need no more than program order
 
-// SIXTEEN LANES PER RECORD add the 15 values of every lane with `ok` to components base .. base+14 of its gaussian's
-// gradient row - one 64-B atomic request per record, nothing returned, so the requests drain behind the wave's arithmetic
+// SIXTEEN LANES PER RECORD add the 15 values of every lane with `ok` to the cells of its gaussian's gradient row that REC names - one 64-B atomic request per record, nothing returned, so the requests drain behind the wave's arithmetic
 // (a lane adding its own 15 values issues 15 x 64 scattered 4-B requests per instruction row; the earlier record paths -
 // per-block buckets + counting-sort reduce, per-wave record logs + an apply kernel - are measured in DESIGN.md 4 and gone).
 // Wave-uniform call; `stage` = 64 x 4 float4.
-EGR_DI void wide_add_wave(const DeviceView &v, bool ok, uint32_t pos, const float (&r)[15], uint32_t base, float4 *stage) {
+template <int REC> EGR_DI void wide_add_wave(const DeviceView &v, bool ok, uint32_t pos, const float (&r)[15], float4 *stage) {
     const int lane = threadIdx.x & (EGR_WAVE - 1);
+    uint32_t cell = 0u; // the row cell of this lane's component (lane & 15) - 1
+    if constexpr (REC == REC_PRIMARY_A) { // record A is not contiguous in the row: the lane picks its cell from the compile-time map (fifteen selects, once per call)
+        constexpr int cells[15] = {GC_OPA, GC_MEAN, GC_MEAN + 1, GC_MEAN + 2, GC_RGB, GC_RGB + 1, GC_RGB + 2, GC_WEIGHT, GC_NORMAL, GC_NORMAL + 1, GC_NORMAL + 2, GC_F0, GC_F0 + 1, GC_F0 + 2, GC_ROUGH};
+#pragma unroll
+        for (int i = 0; i < 15; i++) cell = (lane & 15) == i + 1 ? (uint32_t)cells[i] : cell;
+    } else {
+        cell = (REC == REC_PRIMARY_Q ? (uint32_t)GC_Q : 0u) + (uint32_t)((lane & 15) - 1); // contiguous
+    }
     if (ok) {
         stage[4 * lane + 0] = make_float4(u2f(pos), r[0], r[1], r[2]);
         stage[4 * lane + 1] = make_float4(r[3], r[4], r[5], r[6]);
@@ -751,12 +763,12 @@ EGR_DI void wide_add_wave(const DeviceView &v, bool ok, uint32_t pos, const floa
         if (((okm >> (4 * pass)) & 0xFull) == 0ull) continue; // wave-uniform: none of these four records exists
         const float x = sf[16 * src + c];
         const uint32_t p = f2u(sf[16 * src]);
-        if (((okm >> src) & 1ull) && c != 0 && x != 0.0f) atomicAdd(v.grad_rows + (size_t)p * EGR_ROW_STRIDE + base + (uint32_t)(c - 1), x);
+        if (((okm >> src) & 1ull) && c != 0 && (REC != REC_PRIMARY_Q || c <= 6) && x != 0.0f) atomicAdd(v.grad_rows + (size_t)p * EGR_ROW_STRIDE + cell, x);
     }
     EGR_BWD_SYNC();
 }
 
-// Flush of the primary step's LDS table: every used slot leaves as two 16-lane records (components 0-14 and 15-21 of the row).
+// Flush of the primary step's LDS table: every used slot leaves as two 16-lane records (components 0-14 and the six of Q).
 EGR_DI uint32_t grad_table_flush(const DeviceView &v, uint32_t *gt_keys, float *gt_vals, float4 *stage, int lane) {
     uint32_t sent = 0u; // records (two per used slot)
     EGR_BWD_SYNC();
@@ -781,15 +793,15 @@ EGR_DI uint32_t grad_table_flush(const DeviceView &v, uint32_t *gt_keys, float *
             }
         }
         if (__ballot(valid) == 0ull) continue;
-        wide_add_wave(v, valid, pos, lo, 0u, stage);
-        wide_add_wave(v, valid, pos, hi, 15u, stage);
+        wide_add_wave<REC_PRIMARY_A>(v, valid, pos, lo, stage);
+        wide_add_wave<REC_PRIMARY_Q>(v, valid, pos, hi, stage);
         sent += 2u * (uint32_t)__popcll(__ballot(valid));
     }
     EGR_BWD_SYNC();
     return sent;
 }
 
-// The 22 gradient components of the PRIMARY hits of one hit row (one per lane; `pos` = record index) on their way into the wave's LDS table, in two
+// The 21 gradient components of the PRIMARY hits of one hit row (one per lane; `pos` = record index) on their way into the wave's LDS table, in two
 // calls: primary_presum (1), then primary_table_add (2, 3), which returns true for a lane whose contribution found no slot and has to leave
 // as two records of its own.
 //  (1) Primary tiles are coherent: the pixel to the right / below very often composites the SAME gaussian at the same hit index, so equal
@@ -798,7 +810,7 @@ EGR_DI uint32_t grad_table_flush(const DeviceView &v, uint32_t *gt_keys, float *
 //      ds_add_f32 per hit row (1408 lane-operations) made the table half of the backward chain (round 3, per-phase stamps: 12k of 23k
 //      wave-cycles per row on the dense-init cloud). The table is private to this wave, so only lanes of the SAME row can collide, and only
 //      on the same gaussian: a lane finds its slot with plain reads (one CAS when it has to create it), the lanes of a slot elect one of them
-//      per round through a claim word, and the winner adds its 22 components with plain ds_read / ds_write (conflict-free: odd slot stride)
+//      per round through a claim word, and the winner adds its 21 components with plain ds_read / ds_write (conflict-free: odd slot stride)
 //      - the others follow in the next round (after the register-level pre-sums few slots see more than one lane).
 //  (3) A hit that finds no slot within 8 probes: the table is (as good as) full. A tile of the dense-init cloud composites more gaussians
 //      (~ 100-130) than the table holds, and every hit of a gaussian without a slot used to leave the wave as two 64-B records of its own -
@@ -872,17 +884,80 @@ EGR_DI bool primary_table_add(const DeviceView &v, const bool want, const uint32
         }
         EGR_BWD_SYNC();
     }
-    return want && !found; // (still no slot: the 22 components leave as two 16-lane records, like a flushed slot)
+    return want && !found; // (still no slot: the 21 components leave as two 16-lane records, like a flushed slot)
 }
 
-// ---- the geometry half of B2 for one hit (backward_pass.cu:151-205): components 0 .. 10 of its gradient (opacity, scale, mean,
-// rotation) from the record position, the ray, the live (.., opacity, sigma) quarter and dL/dalpha. Independent of the other hits of
-// the ray - the sequential half (suffix sums -> dL/dalpha) is the caller's.
-template <class GX> EGR_DI void hit_geometry_fn(const DeviceView &v, const float exp_power, const float eps_scale_grad, uint32_t pos, const float4 &a2, const f3 &ro, const f3 &rd, float dL_dalpha, GX &gx) {
+// ---- the scale / rotation chain (backward_pass.cu:170-205, activations.cu:66-73): d_scale and d_rot from L = (dl2w_0, dl2w_1, dl2w_2), the gradient with
+// respect to the rows of the object->world matrix, and the gaussian's backward record (rows of M with exp(scale) in .w, raw quaternion). LINEAR in L with
+// coefficients that belong to the gaussian alone: a bounce hit applies it to its own dl2w (bounce_batch, T = float), for the primary hits of a launch
+// k_grad_gather applies it to the sum (rebuilt from the summed Q of the gradient row, T = double). The one copy of the formula.
+// Why double there: d_rot is what the projection along q leaves of dL/dq, a small difference of large terms. Per hit the rounding errors of that
+// difference average out over the hits of a gaussian; applied ONCE to the sum in fp32 the error of the one evaluation stays (measured: up to 2.8 x the
+// fp32 reference's distance from the fp64 one, tests/test_hip_gradient_terms.py). One evaluation per gaussian is cheap enough to do in fp64.
+template <class T> EGR_DI T chain_rcp(T b) {
+    if constexpr (sizeof(T) == sizeof(float)) return egr_rcp_refined(b);
+    else return T(1) / b;
+}
+template <class T> EGR_DI T chain_div(T a, T b, T r) { // a / b, r = chain_rcp(b)
+    if constexpr (sizeof(T) == sizeof(float)) return egr_div_rn(a, b, r);
+    else return a / b;
+}
+template <class T> EGR_DI T chain_sqrt(T x) {
+    if constexpr (sizeof(T) == sizeof(float)) return egr_sqrt_rn(x);
+    else return sqrt(x);
+}
+template <class T> struct ChainVec { T x, y, z; }; // (f3 is float only)
+template <class T> EGR_DI void scale_rot_chain(const float4 &M0, const float4 &M1, const float4 &M2, const float4 &qu, const float sigma, const float eps, const ChainVec<T> &dl2w0,
+                                               const ChainVec<T> &dl2w1, const ChainVec<T> &dl2w2, T (&d_scale)[3], T (&d_rot)[4]) {
+    const T scaling_factor = sigma, eps_scale_grad = eps;
+    const ChainVec<T> scaling = {T(M0.w), T(M1.w), T(M2.w)}; // exp(scale), stored by k_instances
+    const ChainVec<T> den = {scaling.x * scaling_factor + eps_scale_grad, scaling.y * scaling_factor + eps_scale_grad, scaling.z * scaling_factor + eps_scale_grad};
+    // (nine quotients over three denominators, further down four over |q| and two reciprocals: each denominator's reciprocal is refined once and every
+    // quotient corrected from it - egr_div_rn, the results of `/` - instead of seventeen full expansions of a division)
+    const ChainVec<T> rden = {chain_rcp(den.x), chain_rcp(den.y), chain_rcp(den.z)};
+    auto div3 = [&](const float4 &m) { return ChainVec<T>{chain_div(T(m.x), den.x, rden.x), chain_div(T(m.y), den.y, rden.y), chain_div(T(m.z), den.z, rden.z)}; };
+    const ChainVec<T> rot_0 = div3(M0), rot_1 = div3(M1), rot_2 = div3(M2); // :178-180
+    d_scale[0] = (dl2w0.x * rot_0.x + dl2w1.x * rot_1.x + dl2w2.x * rot_2.x) * scaling.x; // :181-182
+    d_scale[1] = (dl2w0.y * rot_0.y + dl2w1.y * rot_1.y + dl2w2.y * rot_2.y) * scaling.y;
+    d_scale[2] = (dl2w0.z * rot_0.z + dl2w1.z * rot_1.z + dl2w2.z * rot_2.z) * scaling.z;
+    auto mul3 = [](const ChainVec<T> &a, const ChainVec<T> &b) { return ChainVec<T>{a.x * b.x, a.y * b.y, a.z * b.z}; };
+    const ChainVec<T> dr0 = mul3(dl2w0, scaling), dr1 = mul3(dl2w1, scaling), dr2 = mul3(dl2w2, scaling); // :185-187
+    const T qr = qu.x, qx = qu.y, qy = qu.z, qz = qu.w;
+    const T qn = chain_sqrt(qr * qr + qx * qx + qy * qy + qz * qz);
+    const T rqn = chain_rcp(qn);
+    const T r = chain_div(qr, qn, rqn), x = chain_div(qx, qn, rqn), y = chain_div(qy, qn, rqn), z = chain_div(qz, qn, rqn); // activations.cu:66-69
+    const T dL_dr = T(2) * x * (dr2.y - dr1.z) + T(2) * y * (dr0.z - dr2.x) + T(2) * z * (dr1.x - dr0.y); // :194-205
+    const T dL_dx = T(-4) * x * (dr1.y + dr2.z) + T(2) * y * (dr0.y + dr1.x) + T(2) * z * (dr0.z + dr2.x) + T(2) * r * (dr2.y - dr1.z);
+    const T dL_dy = T(2) * x * (dr0.y + dr1.x) - T(4) * y * (dr0.x + dr2.z) + T(2) * z * (dr1.z + dr2.y) + T(2) * r * (dr0.z - dr2.x);
+    const T dL_dz = T(2) * x * (dr0.z + dr2.x) + T(2) * y * (dr1.z + dr2.y) - T(4) * z * (dr0.x + dr1.y) + T(2) * r * (dr1.x - dr0.y);
+    const T dd = dL_dr * qr + dL_dx * qx + dL_dy * qy + dL_dz * qz; // activations.cu:71-73
+    const T qn3 = qn * qn * qn;
+    const T inv3 = chain_div(T(1), qn3, chain_rcp(qn3)), inv1 = chain_div(T(1), qn, rqn);
+    d_rot[0] = dd * -qr * inv3 + dL_dr * inv1, d_rot[1] = dd * -qx * inv3 + dL_dx * inv1;
+    d_rot[2] = dd * -qy * inv3 + dL_dy * inv1, d_rot[3] = dd * -qz * inv3 + dL_dz * inv1;
+}
+
+// ---- the geometry half of B2 for one hit (backward_pass.cu:151-205) from the record position, the ray, the live (.., opacity, sigma) quarter and
+// dL/dalpha. Independent of the other hits of the ray - the sequential half (suffix sums -> dL/dalpha) is the caller's.
+// Here the two kinds of hit part:
+//  PRIMARY_HIT  stops after d_mean and returns opacity, mean and six numbers (PC_* order): the scale / rotation chain depends on the gaussian alone and
+//               is linear in dl2w, so it is applied once per gaussian to the launch's sum (k_grad_gather) - no fetch of the backward record (inst_m),
+//               no denominators, quotients or quaternion arithmetic in the hit row. What is summed is not dl2w itself but the LOCAL matrix
+//               Q = (-dL_dx_local * sigma) (x) local_hit, with dl2w_i = sum_k W_k,i * Q_k (W: the gaussian's world->object rows): dL_dx_local is a
+//               multiple of local_hit, so Q is symmetric - six components instead of nine - and a rounding error of the SUM is symmetric too.
+//               That matters: the rotation gradient is what is left of dl2w when its symmetric part cancels (nothing, for an isotropic gaussian),
+//               and a sum of the nine dl2w components carries an unsymmetric error of eps x sum |dl2w| into that difference (measured on a
+//               near-isotropic cloud, HIP's distance from the fp64 reference over the fp32 reference's, per loss term: 1.24-2.8 with dl2w summed
+//               and the chain in fp32; with Q and the chain in fp64 - scale_rot_chain - 0.33-0.95, as with the per-hit chain).
+//  bounce hit   runs the chain itself and returns the finished components 0 .. 10 (opacity, scale, mean, rotation; GC_* order): its 15 components are ONE
+//               64-B record; with L there would be 17, i.e. a second atomic record per bounce hit, and the record rate is the nearest ceiling of the
+//               bounce-heavy (trained-like) backward chain.
+template <bool PRIMARY_HIT, class GX> EGR_DI void hit_geometry_fn(const DeviceView &v, const float exp_power, const float eps_scale_grad, uint32_t pos, const float4 &a2, const f3 &ro, const f3 &rd, float dL_dalpha, GX &gx) {
     const float opacity = a2.z, scaling_factor = a2.w;
     // recompute the local hit exactly as the forward did
     const float4 W0 = v.inst_w[4 * pos], W1 = v.inst_w[4 * pos + 1], W2 = v.inst_w[4 * pos + 2];
-    const float4 M0 = v.inst_m[4 * pos], M1 = v.inst_m[4 * pos + 1], M2 = v.inst_m[4 * pos + 2], qu = v.inst_m[4 * pos + 3]; // (requested with W: left where they are used, the compiler issues them ~ 500 instructions later and the row waits a second time)
+    float4 M0, M1, M2, qu;
+    if constexpr (!PRIMARY_HIT) M0 = v.inst_m[4 * pos], M1 = v.inst_m[4 * pos + 1], M2 = v.inst_m[4 * pos + 2], qu = v.inst_m[4 * pos + 3]; // (requested with W: left where they are used, the compiler issues them ~ 500 instructions later and the row waits a second time)
     f3 lo, ld, dhat, u;
     float t_unused;
     bool behind_unused, outside_unused;
@@ -898,34 +973,20 @@ template <class GX> EGR_DI void hit_geometry_fn(const DeviceView &v, const float
     const f3 dL_dx_local = (-local_hit * dL_dsq_norm) * dL_dgaussval;
     const f3 dL_dx_world = mk3(dot(mk3(W0.x, W1.x, W2.x), dL_dx_local), dot(mk3(W0.y, W1.y, W2.y), dL_dx_local),
                                dot(mk3(W0.z, W1.z, W2.z), dL_dx_local)) * scaling_factor; // :161-167
-    const f3 dl2w0 = -dL_dx_world.x * local_hit, dl2w1 = -dL_dx_world.y * local_hit, dl2w2 = -dL_dx_world.z * local_hit;
     const f3 d_mean = -dL_dx_world;
-    const f3 scaling = mk3(M0.w, M1.w, M2.w); // exp(scale), stored by k_instances
-    const f3 den = mk3(scaling.x * scaling_factor + eps_scale_grad, scaling.y * scaling_factor + eps_scale_grad,
-                       scaling.z * scaling_factor + eps_scale_grad);
-    // (nine quotients over three denominators, further down four over |q| and two reciprocals: each denominator's reciprocal is refined once and every
-    // quotient corrected from it - egr_div_rn, the results of `/` - instead of seventeen full expansions of a division)
-    const f3 rden = mk3(egr_rcp_refined(den.x), egr_rcp_refined(den.y), egr_rcp_refined(den.z));
-    const f3 rot_0 = egr_div3_rn(mk3(M0.x, M0.y, M0.z), den, rden), rot_1 = egr_div3_rn(mk3(M1.x, M1.y, M1.z), den, rden), rot_2 = egr_div3_rn(mk3(M2.x, M2.y, M2.z), den, rden); // :178-180
-    const f3 d_scale = (dl2w0 * rot_0 + dl2w1 * rot_1 + dl2w2 * rot_2) * scaling; // :181-182
-    const f3 dr0 = dl2w0 * scaling, dr1 = dl2w1 * scaling, dr2 = dl2w2 * scaling; // :185-187
-    const float qn = egr_sqrt_rn(qu.x * qu.x + qu.y * qu.y + qu.z * qu.z + qu.w * qu.w);
-    const float rqn = egr_rcp_refined(qn);
-    const float r = egr_div_rn(qu.x, qn, rqn), x = egr_div_rn(qu.y, qn, rqn), y = egr_div_rn(qu.z, qn, rqn), z = egr_div_rn(qu.w, qn, rqn); // activations.cu:66-69
-    const float dL_dr = 2.f * x * (dr2.y - dr1.z) + 2.f * y * (dr0.z - dr2.x) + 2.f * z * (dr1.x - dr0.y); // :194-205
-    const float dL_dx = -4.f * x * (dr1.y + dr2.z) + 2.f * y * (dr0.y + dr1.x) + 2.f * z * (dr0.z + dr2.x) + 2.f * r * (dr2.y - dr1.z);
-    const float dL_dy = 2.f * x * (dr0.y + dr1.x) - 4.f * y * (dr0.x + dr2.z) + 2.f * z * (dr1.z + dr2.y) + 2.f * r * (dr0.z - dr2.x);
-    const float dL_dz = 2.f * x * (dr0.z + dr2.x) + 2.f * y * (dr1.z + dr2.y) - 4.f * z * (dr0.x + dr1.y) + 2.f * r * (dr1.x - dr0.y);
-    const float dd = dL_dr * qu.x + dL_dx * qu.y + dL_dy * qu.z + dL_dz * qu.w; // activations.cu:71-73
-    const float qn3 = qn * qn * qn;
-    const float inv3 = egr_div_rn(1.0f, qn3, egr_rcp_refined(qn3)), inv1 = egr_div_rn(1.0f, qn, rqn);
-
-    // :210-220 flush: into the LDS table when a slot is found within 8 probes, else straight to global
-    const float d_rot0 = dd * -qu.x * inv3 + dL_dr * inv1, d_rot1 = dd * -qu.y * inv3 + dL_dx * inv1;
-    const float d_rot2 = dd * -qu.z * inv3 + dL_dy * inv1, d_rot3 = dd * -qu.w * inv3 + dL_dz * inv1;
-    gx[GC_OPA] = d_opacity, gx[GC_SCALE] = d_scale.x, gx[GC_SCALE + 1] = d_scale.y, gx[GC_SCALE + 2] = d_scale.z;
-    gx[GC_MEAN] = d_mean.x, gx[GC_MEAN + 1] = d_mean.y, gx[GC_MEAN + 2] = d_mean.z;
-    gx[GC_ROT] = d_rot0, gx[GC_ROT + 1] = d_rot1, gx[GC_ROT + 2] = d_rot2, gx[GC_ROT + 3] = d_rot3;
+    if constexpr (PRIMARY_HIT) {
+        gx[PC_OPA] = d_opacity, gx[PC_MEAN] = d_mean.x, gx[PC_MEAN + 1] = d_mean.y, gx[PC_MEAN + 2] = d_mean.z;
+        const f3 ql = -dL_dx_local * scaling_factor;
+        gx[PC_Q] = ql.x * local_hit.x, gx[PC_Q + 1] = ql.x * local_hit.y, gx[PC_Q + 2] = ql.x * local_hit.z;
+        gx[PC_Q + 3] = ql.y * local_hit.y, gx[PC_Q + 4] = ql.y * local_hit.z, gx[PC_Q + 5] = ql.z * local_hit.z;
+    } else {
+        const f3 dl2w0 = -dL_dx_world.x * local_hit, dl2w1 = -dL_dx_world.y * local_hit, dl2w2 = -dL_dx_world.z * local_hit;
+        float d_scale[3], d_rot[4];
+        scale_rot_chain<float>(M0, M1, M2, qu, scaling_factor, eps_scale_grad, {dl2w0.x, dl2w0.y, dl2w0.z}, {dl2w1.x, dl2w1.y, dl2w1.z}, {dl2w2.x, dl2w2.y, dl2w2.z}, d_scale, d_rot);
+        gx[GC_OPA] = d_opacity, gx[GC_SCALE] = d_scale[0], gx[GC_SCALE + 1] = d_scale[1], gx[GC_SCALE + 2] = d_scale[2];
+        gx[GC_MEAN] = d_mean.x, gx[GC_MEAN + 1] = d_mean.y, gx[GC_MEAN + 2] = d_mean.z;
+        gx[GC_ROT] = d_rot[0], gx[GC_ROT + 1] = d_rot[1], gx[GC_ROT + 2] = d_rot[2], gx[GC_ROT + 3] = d_rot[3];
+    }
 }
 
 // One batch of 64 hits of a bounce step's queue (backward_task.inc: pass 2), lane = hit: the geometry gradient from the hit's record index, the
@@ -946,12 +1007,12 @@ EGR_DI uint32_t bounce_batch(const DeviceView &v, const float exp_power, const f
         const float weight = u2f(item.w);
         const float4 a2 = v.inst_w[4 * pos + 3];
         const f3 iro = mk3(bray[ray], bray[EGR_WAVE + ray], bray[2 * EGR_WAVE + ray]), ird = mk3(bray[3 * EGR_WAVE + ray], bray[4 * EGR_WAVE + ray], bray[5 * EGR_WAVE + ray]);
-        hit_geometry_fn(v, exp_power, eps_scale_grad, pos, a2, iro, ird, u2f(item.y), gx);
+        hit_geometry_fn<false>(v, exp_power, eps_scale_grad, pos, a2, iro, ird, u2f(item.y), gx);
         gx[GC_RGB] = bdl[ray] * weight, gx[GC_RGB + 1] = bdl[EGR_WAVE + ray] * weight, gx[GC_RGB + 2] = bdl[2 * EGR_WAVE + ray] * weight;
         gx[GC_WEIGHT] = weight;
         dpos = pos;
     }
-    wide_add_wave(v, valid, dpos, gx, 0u, stage);
+    wide_add_wave<REC_BOUNCE>(v, valid, dpos, gx, stage);
     return (uint32_t)__popcll(__ballot(valid));
 }
 
@@ -966,7 +1027,7 @@ template <int TEAM> struct BwdTeamShared {
 };
 
 // The backward half of the fused per-tile chain (see k_forward_chain): a wave takes a tile's backward through all its steps - the
-// primary step (22 gradient components per hit through the LDS table), then the bounce steps, last bounce first (15 components per
+// primary step (21 gradient components per hit through the LDS table), then the bounce steps, last bounce first (15 components per
 // hit, straight out as wide adds; in the team build their batches can be taken by team mates). Per-step code: backward_task.inc.
 #ifndef EGR_BWD_WAVES
 #define EGR_BWD_WAVES 3
@@ -1058,14 +1119,20 @@ template <int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribu
 // caller's gradient tensors - coalesced on the tensor side - and empties the row for the next launch.
 // OVERWRITE (egr_set_grad_overwrite: the tensors are a per-launch buffer that is all-reduced over the ranks): the launch's sums are
 // STORED, rows without a contribution store zeros - the caller neither clears the buffer nor pays the read half of a "+=".
+// A row holds finished values (bounce hits) and, in its GC_Q cells, the summed local matrix Q of the launch's PRIMARY hits (hit_geometry_fn): dl2w = W^T Q
+// and the scale / rotation chain (scale_rot_chain) are applied to that sum here, once, with the records the hits read - nothing rewrites them between the
+// chains and this kernel.
+// No cheap scatter kernel any more: the fp64 chain (three reciprocals, seventeen quotients and a square root in double per hit gaussian) takes it from 38 to
+// 98 VGPRs and from eight to four waves per SIMD; measured +0.015 ms on 0.095 ms at 1M gaussians (it still streams rows, records and nine tensors).
 template <bool OVERWRITE> __global__ void __launch_bounds__(256) k_grad_gather(DeviceView v) {
     const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
     if (gid >= v.n) return;
-    float4 *row = reinterpret_cast<float4 *>(v.grad_rows + (size_t)v.pos_of_gid[gid] * EGR_ROW_STRIDE);
-    float x[24];
-    uint32_t any = 0;
+    const size_t pos = v.pos_of_gid[gid];
+    float4 *row = reinterpret_cast<float4 *>(v.grad_rows + pos * EGR_ROW_STRIDE);
+    float x[EGR_ROW_STRIDE];
+    uint32_t any = 0, any_l = 0;
 #pragma unroll
-    for (int q = 0; q < 6; q++) {
+    for (int q = 0; q < EGR_ROW_STRIDE / 4; q++) {
         const float4 r = row[q];
         x[4 * q] = r.x, x[4 * q + 1] = r.y, x[4 * q + 2] = r.z, x[4 * q + 3] = r.w;
         any |= (f2u(r.x) | f2u(r.y) | f2u(r.z) | f2u(r.w)) << 1; // ignore the sign bit: -0 is empty too
@@ -1073,7 +1140,22 @@ template <bool OVERWRITE> __global__ void __launch_bounds__(256) k_grad_gather(D
     if (!OVERWRITE && any == 0) return;
     if (any != 0) {
 #pragma unroll
-        for (int q = 0; q < 6; q++) row[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = 0; q < EGR_ROW_STRIDE / 4; q++) row[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int c = 0; c < 6; c++) any_l |= f2u(x[GC_Q + c]) << 1;
+    if (any_l != 0) {
+        const float4 M0 = v.inst_m[4 * pos], M1 = v.inst_m[4 * pos + 1], M2 = v.inst_m[4 * pos + 2], qu = v.inst_m[4 * pos + 3];
+        const float4 W0 = v.inst_w[4 * pos], W1 = v.inst_w[4 * pos + 1], W2 = v.inst_w[4 * pos + 2];
+        const float scaling_factor = v.inst_w[4 * pos + 3].w;
+        const double q00 = x[GC_Q], q01 = x[GC_Q + 1], q02 = x[GC_Q + 2], q11 = x[GC_Q + 3], q12 = x[GC_Q + 4], q22 = x[GC_Q + 5];
+        auto dl2w_of = [&](double w0, double w1, double w2) { return ChainVec<double>{w0 * q00 + w1 * q01 + w2 * q02, w0 * q01 + w1 * q11 + w2 * q12, w0 * q02 + w1 * q12 + w2 * q22}; }; // dl2w_i = sum_k W_k,i Q_k
+        double d_scale[3], d_rot[4];
+        scale_rot_chain<double>(M0, M1, M2, qu, scaling_factor, *v.cfg.eps_scale_grad, dl2w_of(W0.x, W1.x, W2.x), dl2w_of(W0.y, W1.y, W2.y), dl2w_of(W0.z, W1.z, W2.z), d_scale, d_rot);
+#pragma unroll
+        for (int a = 0; a < 3; a++) x[GC_SCALE + a] = (float)((double)x[GC_SCALE + a] + d_scale[a]);
+#pragma unroll
+        for (int a = 0; a < 4; a++) x[GC_ROT + a] = (float)((double)x[GC_ROT + a] + d_rot[a]);
     }
     const egr_gaussians &g = v.g;
     auto put = [](float *p, float val) {
