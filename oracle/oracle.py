@@ -3,7 +3,9 @@
 TEST INFRASTRUCTURE ONLY: may be imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py. The shipped HIP path never imports this module.
 Parity status: unpinned by the reference (no golden numbers exist upstream for this path);
-pinned by the known-answer / finite-difference / golden-fixture tests in tests/.
+pinned by the known-answer / finite-difference / golden-fixture tests in tests/. The finite differences cover the primary step
+(tests/test_oracle_gradients.py) and, through Oracle.set_frozen_chain and frozen_chain_loss, the backward of the bounce steps
+(tests/test_oracle_bounce_gradients.py).
 """
 import ctypes
 import os
@@ -55,7 +57,7 @@ class _Targets(ctypes.Structure):
 
 
 _OUT_F64 = ["output_rgb", "output_depth", "output_normal", "output_f0", "output_roughness", "output_transmittance",
-            "output_total_transmittance", "output_ray_origin", "output_ray_direction", "output_final"]
+            "output_total_transmittance", "output_ray_origin", "output_ray_direction", "output_final", "output_throughput"]
 _OUT_INT = ["random_seeds", "num_traversed", "num_accumulated", "num_composited_all_steps", "effective_steps", "num_composited_per_step", "num_depth_ties"]
 _OUT_GRAD = ["dL_drgb", "dL_dnormal", "dL_df0", "dL_droughness", "dL_dopacity", "dL_dscale", "dL_dmean", "dL_drotation",
              "total_weight"]
@@ -84,6 +86,7 @@ def lib():
         L.orc_set_use_bvh.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.orc_set_partition.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.orc_set_pixel_mask.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.orc_set_frozen_chain.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.orc_update_bvh.argtypes = [ctypes.c_void_p]
         L.orc_reset_accumulators.argtypes = [ctypes.c_void_p]
         L.orc_raytrace.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
@@ -167,6 +170,29 @@ class Oracle:
             m = np.ascontiguousarray(np.asarray(mask).reshape(self.H * self.W) != 0, dtype=np.uint8)
             self.L.orc_set_pixel_mask(self.h, m.ctypes.data_as(ctypes.c_void_p))
 
+    def set_frozen_chain(self, table):
+        """Test hook for finite differences of the bounce steps. table: [2,H,W,10] float64 from frozen_chain_from (per bounce step s in {0, 1} and pixel:
+        origin and direction of the ray that leaves step s, output_throughput[s], 1.0 if the chain went on to step s + 1), or None (the default: free
+        chain). While set, a launch computes every step's outputs from the live parameters but takes the next ray, the throughput and the
+        continue / break decision of every step that has a successor from the table."""
+        if table is None:
+            self.L.orc_set_frozen_chain(self.h, None)
+        else:
+            t = _f64(table, (2, self.H, self.W, 10))
+            self.L.orc_set_frozen_chain(self.h, _ptr(t))  # (copied by the library)
+
+    @staticmethod
+    def frozen_chain_from(out):
+        """The table of set_frozen_chain from the outputs of a (free) launch."""
+        H, W = out["effective_steps"].shape
+        t = np.zeros((2, H, W, 10))
+        for s in range(2):
+            t[s, ..., 0:3] = out["output_ray_origin"][s]
+            t[s, ..., 3:6] = out["output_ray_direction"][s]
+            t[s, ..., 6:9] = out["output_throughput"][s]
+            t[s, ..., 9] = out["effective_steps"] > s + 1
+        return t
+
     def set_gaussians(self, g):
         """g: dict with raw (pre-activation) arrays rgb[N,3] normal[N,3] f0[N,3] roughness[N,1] opacity[N,1]
         scale[N,3] mean[N,3] rotation[N,4] (core/gaussians.h:6-13)."""
@@ -217,7 +243,7 @@ class Oracle:
         shp = {"output_rgb": (NSTEPS, H, W, 3), "output_depth": (NSTEPS, H, W, 1), "output_normal": (NSTEPS, H, W, 3),
                "output_f0": (NSTEPS, H, W, 3), "output_roughness": (NSTEPS, H, W, 1), "output_transmittance": (NSTEPS, H, W, 1),
                "output_total_transmittance": (NSTEPS, H, W, 1), "output_ray_origin": (NSTEPS, H, W, 3),
-               "output_ray_direction": (NSTEPS, H, W, 3), "output_final": (1, H, W, 3)}
+               "output_ray_direction": (NSTEPS, H, W, 3), "output_final": (1, H, W, 3), "output_throughput": (NSTEPS, H, W, 3)}
         for k in _OUT_F64:
             out[k] = np.zeros(shp[k], np.float64)
         out["random_seeds"] = np.zeros((H, W, 1), np.uint32)
@@ -293,10 +319,10 @@ def cook_torrance_weight(N, V, L, roughness, f0):
 
 
 def l1_loss(out, targets, cfg, num_bounces):
-    """The loss whose gradient backward_pass.cu:80-108 hard-codes (sum over pixels, no mean):
-    w_d/3*|rgb0-diffuse| + w_depth*|depth0-t| + w_n/3*|normal0-t| + w_f0/3*|f00-t| + w_r*|rough0-t|
-    (+ w_s/3*|sum_{j>=1} rgb_j - specular| for bounce steps; throughput/downweight are constants there)."""
-    z3 = 0.0
+    """The primary-step part of the loss whose gradient backward_pass.cu:80-108 hard-codes (sum over pixels, no mean):
+    w_d/3*|rgb0-diffuse| + w_depth*|depth0-t| + w_n/3*|normal0-t| + w_f0/3*|f00-t| + w_r*|rough0-t|.
+    `num_bounces` is IGNORED (kept for the callers): the specular term of the bounce steps, w_s/3*|sum_{j>=1} rgb_j - specular| with throughput and
+    down-weighting held constant, is not in here - frozen_chain_loss adds it."""
     def t(k, shape):
         v = targets.get(k) if targets else None
         return np.zeros(shape) if v is None else np.asarray(v, np.float64).reshape(shape)
@@ -306,4 +332,25 @@ def l1_loss(out, targets, cfg, num_bounces):
     L += cfg["loss_weight_normal"] / 3.0 * np.abs(out["output_normal"][0] - t("normal", (H, W, 3))).sum()
     L += cfg["loss_weight_f0"] / 3.0 * np.abs(out["output_f0"][0] - t("f0", (H, W, 3))).sum()
     L += cfg["loss_weight_roughness"] * np.abs(out["output_roughness"][0] - t("roughness", (H, W, 1))).sum()
+    return float(L)
+
+
+def frozen_chain_loss(out, targets, cfg, base):
+    """The loss that the analytic backward differentiates exactly when every bounce ray, throughput and down-weight is held at its value of the
+    launch `base` (`out`: a launch under set_frozen_chain(frozen_chain_from(base))):
+        l1_loss(step 0) + sum_{j=1..num_bounces} w_s/3 * D_j * sum_c s_c * output_rgb[j]_c        (sum over pixels)
+    with D_j = (1 - base output_roughness[j-1])^3 and s = sign(sum_j base output_rgb[j] - target_specular), sign(0) = +1; output_rgb[j] already
+    carries throughput[j-1] (the table's). Linear in output_rgb[j]: |.| is replaced by its slope at `base`, so targets must stay away from the
+    outputs for the two to agree within a finite-difference step."""
+    nb = min(int(cfg["num_bounces"]), NSTEPS - 1)
+    L = l1_loss(out, targets, cfg, nb)
+    if nb == 0:
+        return L
+    H, W = out["output_final"].shape[1:3]
+    v = targets.get("specular") if targets else None
+    tspec = np.zeros((H, W, 3)) if v is None else np.asarray(v, np.float64).reshape(H, W, 3)
+    sgn = np.copysign(1.0, base["output_rgb"][1:nb + 1].sum(axis=0) - tspec)
+    for j in range(1, nb + 1):
+        D = (1.0 - base["output_roughness"][j - 1]) ** 3  # [H,W,1]
+        L += cfg["loss_weight_specular"] / 3.0 * float((D * sgn * out["output_rgb"][j]).sum())
     return float(L)

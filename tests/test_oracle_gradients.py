@@ -2,7 +2,9 @@
 
 The reference's backward (backward_pass.cu:80-220) is the exact gradient of the in-kernel L1 loss when
 (i) no ray is truncated (transmittance_threshold = 0), (ii) loss_weight_depth = 0 (d depth / d geometry is not
-propagated), (iii) no candidate straddles a clip boundary within the FD step, (iv) num_bounces = 0."""
+propagated), (iii) no candidate straddles a clip boundary within the FD step, (iv) num_bounces = 0 IN THIS FILE: the bounce steps, where
+the backward additionally holds every bounce ray, throughput and down-weight constant, are differentiated in test_oracle_bounce_gradients.py
+(with those held at their base values: Oracle.set_frozen_chain)."""
 import numpy as np
 import pytest
 
