@@ -54,6 +54,34 @@ template <class F> int guarded(egr_context *c, F &&f) {
         return 1;
     }
 }
+int require_ready(egr_context *c, bool need_bvh) {
+    if (!c->bound || !c->have_gaussians) {
+        c->last_error = "libegr_hip: egr_bind / egr_set_gaussians must be called first";
+        return 1;
+    }
+    if (need_bvh && (!c->bvh_valid || c->n_built != c->g.count)) {
+        c->last_error = "libegr_hip: BVH is missing or was built for a different gaussian count; call egr_rebuild_bvh";
+        return 1;
+    }
+    return 0;
+}
+
+// A traced call (egr_raytrace, egr_render_views, egr_train_views) from the readiness checks on: `launch(stream)` runs between the two events
+// egr_last_raytrace_ms reads, with the per-kernel stamps counted from zero.
+template <class F> int traced(egr_context *c, void *stream, F &&launch) {
+    if (require_ready(c, true)) return 1;
+    if (c->exact_stats != c->boxes_are_cubes) {
+        c->last_error = "libegr_hip: egr_set_exact_stats changed since the tree was last refitted; call egr_update_bvh or egr_rebuild_bvh first";
+        return 1;
+    }
+    return guarded(c, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        c->stamps_used = 0;
+        if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt0, s));
+        launch(s);
+        if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt1, s)), c->have_rt = true;
+    });
+}
 } // namespace
 
 extern "C" {
@@ -155,18 +183,6 @@ int egr_set_team_help(egr_context *c, int on) {
 
 int egr_set_strands(egr_context *c, int strands) { return c && strands == 1 ? 0 : 1; }
 
-static int require_ready(egr_context *c, bool need_bvh) {
-    if (!c->bound || !c->have_gaussians) {
-        c->last_error = "libegr_hip: egr_bind / egr_set_gaussians must be called first";
-        return 1;
-    }
-    if (need_bvh && (!c->bvh_valid || c->n_built != c->g.count)) {
-        c->last_error = "libegr_hip: BVH is missing or was built for a different gaussian count; call egr_rebuild_bvh";
-        return 1;
-    }
-    return 0;
-}
-
 int egr_rebuild_bvh(egr_context *c, void *stream) {
     if (!c || require_ready(c, false)) return 1;
     return guarded(c, [&] { egr_bvh_rebuild(c, (hipStream_t)stream); });
@@ -197,18 +213,7 @@ int egr_raytrace(egr_context *c, int grads_enabled, void *stream) {
     // launch reading the live tensors itself.
     const bool live_fresh = c->live_fresh;
     c->live_fresh = false;
-    if (require_ready(c, true)) return 1;
-    if (c->exact_stats != c->boxes_are_cubes) {
-        c->last_error = "libegr_hip: egr_set_exact_stats changed since the tree was last refitted; call egr_update_bvh or egr_rebuild_bvh first";
-        return 1;
-    }
-    return guarded(c, [&] {
-        hipStream_t s = (hipStream_t)stream;
-        c->stamps_used = 0;
-        if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt0, s));
-        egr_trace_launch(c, grads_enabled != 0, live_fresh, s);
-        if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt1, s)), c->have_rt = true;
-    });
+    return traced(c, stream, [&](hipStream_t s) { egr_trace_launch(c, grads_enabled != 0, live_fresh, s); });
 }
 
 int egr_render_views(egr_context *c, const egr_view_batch *b, void *stream) {
@@ -223,18 +228,7 @@ int egr_render_views(egr_context *c, const egr_view_batch *b, void *stream) {
         c->last_error = "libegr_hip: egr_render_views: num_views x samples_per_view must stay below 2^31";
         return 1;
     }
-    if (require_ready(c, true)) return 1;
-    if (c->exact_stats != c->boxes_are_cubes) {
-        c->last_error = "libegr_hip: egr_set_exact_stats changed since the tree was last refitted; call egr_update_bvh or egr_rebuild_bvh first";
-        return 1;
-    }
-    return guarded(c, [&] {
-        hipStream_t s = (hipStream_t)stream;
-        c->stamps_used = 0;
-        if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt0, s));
-        egr_render_views_launch(c, b, live_fresh, s);
-        if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt1, s)), c->have_rt = true;
-    });
+    return traced(c, stream, [&](hipStream_t s) { egr_render_views_launch(c, b, live_fresh, s); });
 }
 
 int egr_train_views(egr_context *c, const egr_train_batch *b, void *stream) {
@@ -249,18 +243,7 @@ int egr_train_views(egr_context *c, const egr_train_batch *b, void *stream) {
         c->last_error = "libegr_hip: egr_train_views: num_views must stay below 2^31";
         return 1;
     }
-    if (require_ready(c, true)) return 1;
-    if (c->exact_stats != c->boxes_are_cubes) {
-        c->last_error = "libegr_hip: egr_set_exact_stats changed since the tree was last refitted; call egr_update_bvh or egr_rebuild_bvh first";
-        return 1;
-    }
-    return guarded(c, [&] {
-        hipStream_t s = (hipStream_t)stream;
-        c->stamps_used = 0;
-        if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt0, s));
-        egr_train_views_launch(c, b, live_fresh, s);
-        if (c->timing) EGR_HIP(hipEventRecord(c->ev_rt1, s)), c->have_rt = true;
-    });
+    return traced(c, stream, [&](hipStream_t s) { egr_train_views_launch(c, b, live_fresh, s); });
 }
 
 int egr_set_batch_frames(egr_context *c, int frames) {

@@ -426,12 +426,12 @@ struct Raytracer : torch::CustomClassHolder {
         Tensor r = R.to(dev, torch::kFloat32).contiguous(), cc = centre.to(dev, torch::kFloat32).contiguous();
         check(egr_set_camera_from_dataset(ctx, r.data_ptr<float>(), cc.data_ptr<float>(), (float)fov, (float)znear, (float)zfar, current_stream()), "set_camera");
     }
+    static constexpr struct { const char *name; int64_t channels; } TARGETS[6] = {{"diffuse", 3}, {"specular", 3}, {"depth", 1}, {"normal", 3}, {"roughness", 1}, {"f0", 3}}; // (the order of the C ABI's six target pointers)
     // the six target images of a training view, channel-major ([C,H,W] contiguous fp32 CUDA tensors; an undefined / empty tensor = absent = zeros), written into
     // the framebuffer's pixel-major target buffers for this context's own tiles in one launch (egr_set_targets_chw)
     void set_targets_chw(c10::optional<Tensor> diffuse, c10::optional<Tensor> specular, c10::optional<Tensor> depth, c10::optional<Tensor> normal, c10::optional<Tensor> roughness,
                          c10::optional<Tensor> f0) {
         const c10::optional<Tensor> *in[6] = {&diffuse, &specular, &depth, &normal, &roughness, &f0};
-        const int64_t ch[6] = {3, 3, 1, 3, 1, 3};
         Tensor keep[6];
         const float *p[6];
         for (int b = 0; b < 6; b++) {
@@ -439,7 +439,7 @@ struct Raytracer : torch::CustomClassHolder {
             if (!in[b]->has_value() || (*in[b])->numel() == 0) continue;
             // (the reference's `buf.copy_(val.moveaxis(0, -1))` raises on any other shape and accepts any device: same here - a [H,W,C] tensor must not be read as [C,H,W])
             const Tensor &t = **in[b];
-            TORCH_CHECK(t.dim() == 3 && t.size(0) == ch[b] && t.size(1) == height && t.size(2) == width, "set_targets_chw: target ", b, " must be a [", ch[b], ",", height, ",", width, "] tensor (channel-major), got ", t.sizes());
+            TORCH_CHECK(t.dim() == 3 && t.size(0) == TARGETS[b].channels && t.size(1) == height && t.size(2) == width, "set_targets_chw: target ", b, " must be a [", TARGETS[b].channels, ",", height, ",", width, "] tensor (channel-major), got ", t.sizes());
             keep[b] = t.to(framebuffer_data->output_rgb.device(), torch::kFloat32).contiguous();
             p[b] = keep[b].data_ptr<float>();
         }
@@ -452,6 +452,15 @@ struct Raytracer : torch::CustomClassHolder {
         if (name == "final" || name == "rgb" || name == "normal" || name == "f0") return 3;
         if (name == "depth" || name == "roughness") return 1;
         return 0;
+    }
+    // The three camera tensors of a batch, validated (`who` = the caller's name in the messages): (R, centers, fovy) as contiguous fp32 tensors on the tracer's device, and V.
+    std::tuple<Tensor, Tensor, Tensor, int64_t> batch_cameras(const char *who, const Tensor &R, const Tensor &centers, const Tensor &fovy) {
+        TORCH_CHECK(R.dim() == 3 && R.size(1) == 3 && R.size(2) == 3, who, ": R must be [V,3,3], got ", R.sizes());
+        const int64_t V = R.size(0);
+        TORCH_CHECK(centers.dim() == 2 && centers.size(0) == V && centers.size(1) == 3, who, ": centers must be [V,3] = [", V, ",3], got ", centers.sizes());
+        TORCH_CHECK(fovy.dim() == 1 && fovy.size(0) == V, who, ": fovy must be [V] = [", V, "], got ", fovy.sizes());
+        const auto dev = framebuffer_data->output_rgb.device();
+        return {R.to(dev, torch::kFloat32).contiguous(), centers.to(dev, torch::kFloat32).contiguous(), fovy.to(dev, torch::kFloat32).contiguous(), V};
     }
     std::vector<Tensor> render_views(Tensor R, Tensor centers, Tensor fovy, double znear, double zfar, int64_t samples_per_view, std::vector<std::string> outputs) {
         const auto opts = framebuffer_data->output_rgb.options();
@@ -467,14 +476,10 @@ struct Raytracer : torch::CustomClassHolder {
     }
     void render_views_into(Tensor R, Tensor centers, Tensor fovy, double znear, double zfar, int64_t samples_per_view, std::vector<std::string> outputs,
                            std::vector<Tensor> buffers) {
-        TORCH_CHECK(R.dim() == 3 && R.size(1) == 3 && R.size(2) == 3, "render_views: R must be [V,3,3], got ", R.sizes());
-        const int64_t V = R.size(0);
-        TORCH_CHECK(centers.dim() == 2 && centers.size(0) == V && centers.size(1) == 3, "render_views: centers must be [V,3] = [", V, ",3], got ", centers.sizes());
-        TORCH_CHECK(fovy.dim() == 1 && fovy.size(0) == V, "render_views: fovy must be [V] = [", V, "], got ", fovy.sizes());
+        const auto [r, cc, fv, V] = batch_cameras("render_views", R, centers, fovy);
         TORCH_CHECK(samples_per_view >= 0 && samples_per_view <= 0x7FFFFFFF, "render_views: samples_per_view out of range");
         TORCH_CHECK(outputs.size() == buffers.size(), "render_views_into: one buffer per output name expected");
         const auto dev = framebuffer_data->output_rgb.device();
-        Tensor r = R.to(dev, torch::kFloat32).contiguous(), cc = centers.to(dev, torch::kFloat32).contiguous(), fv = fovy.to(dev, torch::kFloat32).contiguous();
         egr_view_batch b{};
         b.num_views = (uint32_t)V, b.samples_per_view = (uint32_t)samples_per_view;
         b.rotation_c2w_dataset = r.data_ptr<float>(), b.camera_center = cc.data_ptr<float>(), b.vertical_fov_radians = fv.data_ptr<float>();
@@ -498,25 +503,19 @@ struct Raytracer : torch::CustomClassHolder {
     // the gradient tensors (or the per-launch buffer: one grad launch for the whole batch) as V sequential raytrace() calls with grad mode on would.
     void train_views(Tensor R, Tensor centers, Tensor fovy, double znear, double zfar, c10::optional<Tensor> diffuse, c10::optional<Tensor> specular,
                      c10::optional<Tensor> depth, c10::optional<Tensor> normal, c10::optional<Tensor> roughness, c10::optional<Tensor> f0) {
-        TORCH_CHECK(R.dim() == 3 && R.size(1) == 3 && R.size(2) == 3, "train_views: R must be [V,3,3], got ", R.sizes());
-        const int64_t V = R.size(0);
-        TORCH_CHECK(centers.dim() == 2 && centers.size(0) == V && centers.size(1) == 3, "train_views: centers must be [V,3] = [", V, ",3], got ", centers.sizes());
-        TORCH_CHECK(fovy.dim() == 1 && fovy.size(0) == V, "train_views: fovy must be [V] = [", V, "], got ", fovy.sizes());
+        const auto [r, cc, fv, V] = batch_cameras("train_views", R, centers, fovy);
         const auto dev = framebuffer_data->output_rgb.device();
-        Tensor r = R.to(dev, torch::kFloat32).contiguous(), cc = centers.to(dev, torch::kFloat32).contiguous(), fv = fovy.to(dev, torch::kFloat32).contiguous();
         egr_train_batch b{};
         b.num_views = (uint32_t)V;
         b.rotation_c2w_dataset = r.data_ptr<float>(), b.camera_center = cc.data_ptr<float>(), b.vertical_fov_radians = fv.data_ptr<float>();
         b.znear = (float)znear, b.zfar = (float)zfar;
         const c10::optional<Tensor> *in[6] = {&diffuse, &specular, &depth, &normal, &roughness, &f0};
-        const char *names[6] = {"diffuse", "specular", "depth", "normal", "roughness", "f0"};
-        const int64_t ch[6] = {3, 3, 1, 3, 1, 3};
         const float **slot[6] = {&b.target_diffuse, &b.target_specular, &b.target_depth, &b.target_normal, &b.target_roughness, &b.target_f0};
         for (int k = 0; k < 6; k++) {
             if (!in[k]->has_value() || !(*in[k])->defined() || (*in[k])->numel() == 0) continue;
             const Tensor &t = **in[k];
-            const std::vector<int64_t> want{V, ch[k], height, width};
-            TORCH_CHECK(t.device() == dev && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.sizes() == torch::IntArrayRef(want), "train_views: target '", names[k],
+            const std::vector<int64_t> want{V, TARGETS[k].channels, height, width};
+            TORCH_CHECK(t.device() == dev && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.sizes() == torch::IntArrayRef(want), "train_views: target '", TARGETS[k].name,
                         "' must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " (channel-major) on the tracer's device, got ", t.sizes(), " ", t.scalar_type(), " on ", t.device());
             *slot[k] = t.data_ptr<float>();
         }

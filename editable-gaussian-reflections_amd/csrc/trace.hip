@@ -630,15 +630,29 @@ template <bool CUBE, int TEAM, class F> EGR_DI void team_help_while(const Device
 // ---------------------------------------------------------------------------------------------------------
 // per-launch prologue: Raytracer::raytrace host part (raytracer.cpp:82-86), on the device, no host sync
 // ---------------------------------------------------------------------------------------------------------
-__global__ void k_prologue(DeviceView v, int grads) {
-    int t = threadIdx.x;
+// The control-word resets of the one-block (one-wave) prologue kernels, t = threadIdx.x.
+// Per launch: the counters [0, CW_RESET_END), the diagnostic words and the lines of the two bump counters [CW_DBG, CW_COUNT), then the min / max seeds of CW_DBG3.
+EGR_DI void reset_launch_words(const DeviceView &v, int t) {
     if (t < CW_RESET_END) v.control[t] = 0;
-    for (int w = CW_DBG + t; w < CW_COUNT; w += (int)blockDim.x) v.control[w] = 0; // (diagnostic words: per launch)
-    static_assert(CW_DBG <= CW_HIT_BUMP && CW_HIT_BUMP < CW_COUNT && CW_DBG <= CW_EXT_BUMP && CW_EXT_BUMP < CW_COUNT, "the bump counters lie in the control block's per-launch words");
-    if (t == 0) v.control[CW_HIT_BUMP] = 0, v.control[CW_EXT_BUMP] = 0;
-    if (t < 16) v.control[CW_DBG2 + t] = 0;
-    for (uint32_t q = t; q < EGR_QUEUE_WORDS; q += blockDim.x) v.queues[q] = 0;
+    for (int w = CW_DBG + t; w < CW_COUNT; w += (int)blockDim.x) v.control[w] = 0;
     if (t < 12) v.control[CW_DBG3 + t] = ((t & 3) < 2) ? 0xFFFFFFFFu : 0u;
+}
+// Per chunk of tasks (a single launch is one chunk): fresh task queues of both chains, extension blocks and hit-arena blocks.
+EGR_DI void reset_chunk_words(const DeviceView &v, int t) {
+    for (uint32_t q = t; q < EGR_QUEUE_WORDS; q += blockDim.x) v.queues[q] = 0;
+    if (t == 0) v.control[CW_EXT_BUMP] = 0, v.control[CW_HIT_BUMP] = 0;
+}
+// The lifetime counters at the end of a call that traced `launches` frames (one thread).
+EGR_DI void count_lifetime(const DeviceView &v, uint32_t launches) {
+    unsigned long long rays = 0;
+    for (int s = 0; s < EGR_NSTEPS; s++) rays += *reinterpret_cast<unsigned long long *>(v.control + CW_RAYS + 2 * s);
+    *reinterpret_cast<unsigned long long *>(v.control + CW_LIFE_RAYS) += rays;
+    v.control[CW_LIFE_LAUNCHES] += launches;
+}
+__global__ void k_prologue(DeviceView v, int grads) {
+    const int t = threadIdx.x;
+    reset_launch_words(v, t);
+    reset_chunk_words(v, t);
     if (t == 0) {
         *v.meta.grads_enabled = grads ? 1 : 0;   // metadata.h:29
         *v.meta.total_num_calls += 1;             // metadata.h:30
@@ -648,10 +662,7 @@ __global__ void k_epilogue(DeviceView v, int grads) {
     // raytracer.cpp:91-93 (the reference adds 1 whenever accumulate_samples is set)
     if (threadIdx.x == 0) {
         if (*v.cfg.accumulate_samples) *v.fb.accumulated_sample_count += 1;
-        unsigned long long rays = 0;
-        for (int s = 0; s < EGR_NSTEPS; s++) rays += *reinterpret_cast<unsigned long long *>(v.control + CW_RAYS + 2 * s);
-        *reinterpret_cast<unsigned long long *>(v.control + CW_LIFE_RAYS) += rays;
-        v.control[CW_LIFE_LAUNCHES] += 1;
+        count_lifetime(v, 1u);
     }
 }
 // per-launch live record: activated appearance + (opacity, sigma). Reads the CURRENT parameter tensors, like
@@ -1243,26 +1254,15 @@ __global__ void k_batch_cameras(const float *__restrict__ R, const float *__rest
 // k_prologue for a batch: the per-launch control words, grads_enabled = grads (0: egr_render_views, 1: egr_train_views); total_num_calls stays as it is
 // until k_batch_epilogue (the chunks derive every frame's seed from it).
 __global__ void k_batch_prologue(DeviceView v, int grads) {
-    const int t = threadIdx.x;
-    if (t < CW_RESET_END) v.control[t] = 0;
-    for (int w = CW_DBG + t; w < CW_COUNT; w += (int)blockDim.x) v.control[w] = 0;
-    if (t < 12) v.control[CW_DBG3 + t] = ((t & 3) < 2) ? 0xFFFFFFFFu : 0u;
-    if (t == 0) *v.meta.grads_enabled = grads ? 1 : 0;
+    reset_launch_words(v, threadIdx.x);
+    if (threadIdx.x == 0) *v.meta.grads_enabled = grads ? 1 : 0;
 }
-// every chunk: fresh task queues of both chains, extension blocks and hit-arena blocks (the lists and hits of the previous chunk's tiles are done with:
-// its backward ran before this chunk's forward)
-__global__ void k_batch_chunk_begin(DeviceView v) {
-    const int t = threadIdx.x;
-    for (uint32_t q = t; q < EGR_QUEUE_WORDS; q += blockDim.x) v.queues[q] = 0;
-    if (t == 0) v.control[CW_EXT_BUMP] = 0, v.control[CW_HIT_BUMP] = 0;
-}
+// every chunk (the lists and hits of the previous chunk's tiles are done with: its backward ran before this chunk's forward)
+__global__ void k_batch_chunk_begin(DeviceView v) { reset_chunk_words(v, threadIdx.x); }
 __global__ void k_batch_epilogue(DeviceView v, uint32_t frames) {
     if (threadIdx.x == 0) {
         *v.meta.total_num_calls += (int32_t)frames; // metadata.h:30, once per frame
-        unsigned long long rays = 0;
-        for (int s = 0; s < EGR_NSTEPS; s++) rays += *reinterpret_cast<unsigned long long *>(v.control + CW_RAYS + 2 * s);
-        *reinterpret_cast<unsigned long long *>(v.control + CW_LIFE_RAYS) += rays;
-        v.control[CW_LIFE_LAUNCHES] += frames;
+        count_lifetime(v, frames);
     }
 }
 struct BatchOutputs {
@@ -1444,6 +1444,14 @@ __global__ void k_copy3(const float *__restrict__ src, float *__restrict__ dst, 
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[i];
 }
+
+// The chain kernels of the code object in the order it has always held them - the order of their first use, which this table now is (the compiler
+// reports under profiles/ and the profiling tools list the kernels in it; where a launch names them has no say in it any more).
+[[maybe_unused]] void (*const chain_kernel_order[])(DeviceView) = {
+    k_forward_chain<true, false, 1>, k_forward_chain<true, false, EGR_TEAM>, k_backward_chain<1>, k_forward_chain<true, true, EGR_TEAM>, k_forward_chain<false, true, EGR_TEAM>, k_forward_chain<false, false, EGR_TEAM>,
+    k_forward_chain<true, true, 1>, k_forward_chain<false, true, 1>, k_forward_chain<false, false, 1>, k_backward_chain<EGR_BWD_TEAM>, k_grad_gather<true>, k_grad_gather<false>,
+    k_forward_batch<true, EGR_TEAM>, k_forward_batch<false, EGR_TEAM>, k_forward_batch<true, 1>, k_forward_batch<false, 1>, k_forward_batch_grads<true, EGR_TEAM>, k_forward_batch_grads<false, EGR_TEAM>,
+    k_forward_batch_grads<true, 1>, k_forward_batch_grads<false, 1>, k_backward_batch<EGR_BWD_TEAM>, k_backward_batch<1>};
 
 } // namespace
 
@@ -1627,59 +1635,138 @@ DeviceView egr_make_view(const egr_context *c) {
     return v;
 }
 
-void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s) {
+// ---------------------------------------------------------------------------------------------------------
+// the steps of a launch. egr_trace_launch, egr_render_views_launch and egr_train_views_launch below are sequences of them.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+struct BatchCameras { // the camera arrays of an egr_view_batch / egr_train_batch
+    const float *rotation_c2w_dataset, *camera_center, *vertical_fov_radians;
+    uint32_t views;
+    float znear, zfar;
+};
+template <class B> BatchCameras batch_cameras_of(const B *b) { return {b->rotation_c2w_dataset, b->camera_center, b->vertical_fov_radians, b->num_views, b->znear, b->zfar}; }
+
+// The view of a batch of `views` x `spv` frames: ray state of a chunk of frames, the camera table with the batch's znear / zfar behind its last record.
+DeviceView batch_view(const egr_context *c, uint32_t views, uint32_t spv) {
     DeviceView v = egr_make_view(c);
-    const dim3 block(EGR_WAVE);
+    v.state = c->batch_state, v.state_stride = c->state_stride * c->batch_alloc_frames;
+    v.batch_cams = c->batch_cams, v.batch_spv = spv, v.batch_last_frame = views * spv - 1u;
+    v.cam.znear = c->batch_cams + (size_t)views * EGR_BATCH_CAM_FLOATS, v.cam.zfar = v.cam.znear + 1;
+    return v;
+}
+
+// The per-launch work in front of the chains: control words, stats reset, live records. `cams`: a batch (its camera table is written first, and
+// total_num_calls waits for the batch's epilogue); NULL: a single launch.
+void launch_begin(egr_context *c, const DeviceView &v, bool grads, bool live_fresh, const BatchCameras *cams, hipStream_t s) {
     egr_stamp_begin(c, "prologue+live", s);
-    hipLaunchKernelGGL(k_prologue, dim3(1), dim3(64), 0, s, v, grads ? 1 : 0);
+    if (cams) {
+        hipLaunchKernelGGL(k_batch_cameras, dim3((cams->views + 64u) / 64u), dim3(64), 0, s, cams->rotation_c2w_dataset, cams->camera_center, cams->vertical_fov_radians, cams->views, cams->znear, cams->zfar, c->batch_cams);
+        hipLaunchKernelGGL(k_batch_prologue, dim3(1), dim3(64), 0, s, v, grads ? 1 : 0);
+    } else {
+        hipLaunchKernelGGL(k_prologue, dim3(1), dim3(64), 0, s, v, grads ? 1 : 0);
+    }
     EGR_HIP(hipMemsetAsync(c->stats.num_accumulated_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s)); // stats.h:25-28
     EGR_HIP(hipMemsetAsync(c->stats.num_traversed_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
     // (skipped when the egr_update_bvh_ex(EGR_UPDATE_FUSE_LIVE) just before this launch wrote the same records from the same parameters)
     if (v.n && !live_fresh) hipLaunchKernelGGL(k_live, dim3((v.n + 255) / 256), dim3(256), 0, s, v, grads ? 1 : 0);
     egr_stamp_end(c, s);
+}
+
+// One wave slot per task, at most num_slots: the persistent waves of either chain.
+uint32_t chain_slots(const egr_context *c, uint32_t tasks) { return std::max(1u, std::min(c->num_slots, tasks)); }
+
+// The forward chain over `tasks` tasks (a batch: tasks x the chunk's frames).
+enum class ForwardKernel { single, single_grads, batch, batch_grads };
+void launch_forward_chain(egr_context *c, const DeviceView &v, uint32_t tasks, ForwardKernel kernel, hipStream_t s) {
+    const uint32_t slots = chain_slots(c, tasks);
+    egr_stamp_begin(c, "forward_chain", s);
+    auto launch = [&](auto team_tag, auto cube_tag) {
+        constexpr int T = decltype(team_tag)::value;
+        constexpr bool CUBE = decltype(cube_tag)::value;
+        const dim3 grid((slots + T - 1u) / T), block(EGR_WAVE * T); // (num_slots is a multiple of EGR_TEAM: every wave of a team has its scratch)
+        switch (kernel) {
+        case ForwardKernel::single: hipLaunchKernelGGL((k_forward_chain<false, CUBE, T>), grid, block, 0, s, v); break;
+        case ForwardKernel::single_grads: hipLaunchKernelGGL((k_forward_chain<true, CUBE, T>), grid, block, 0, s, v); break;
+        case ForwardKernel::batch: hipLaunchKernelGGL((k_forward_batch<CUBE, T>), grid, block, 0, s, v); break;
+        case ForwardKernel::batch_grads: hipLaunchKernelGGL((k_forward_batch_grads<CUBE, T>), grid, block, 0, s, v); break;
+        }
+    };
+    auto launch_team = [&](auto team_tag) {
+        if (v.cube_mode) launch(team_tag, std::true_type{});
+        else launch(team_tag, std::false_type{});
+    };
+    // (the chain exists as single-wave workgroups and as teams of EGR_TEAM waves: launches with egr_set_team_help(1) take the teams)
+    if (v.team_help) launch_team(std::integral_constant<int, EGR_TEAM>{});
+    else launch_team(std::integral_constant<int, 1>{});
+    egr_stamp_end(c, s);
+}
+
+// The backward order and the backward chain over the same `tasks` tasks the forward chain just ran. `batch`: the frame is part of the task index.
+void launch_backward_chain(egr_context *c, const DeviceView &v, uint32_t tasks, bool batch, hipStream_t s) {
+    const uint32_t slots = chain_slots(c, tasks);
+    DeviceView ov = v; // k_order_backward sorts every queue chunk of the whole task range, the chunks the backward's wave_next_task hands out
+    ov.num_tasks = tasks;
+    hipLaunchKernelGGL(k_order_backward, dim3(8), dim3(256), 0, s, ov);
+    egr_stamp_begin(c, "backward_chain", s);
+    // (under-filled ranks: the backward chain as teams whose waves without tiles take batches of their mates' bounce hits - gradients are
+    // atomic adds, so no result depends on who sends them; a whole image keeps single-wave workgroups: a team's LDS is only released with its last wave)
+    // (egr_set_team_help(1) takes the teams of both chains: tests/test_hip_parity.py)
+    const bool teams = v.team_help == 1 || (c->world > 1 && (uint64_t)(tasks >> (v.task_shift - 2u)) < 2ull * c->num_slots);
+    const dim3 grid(teams ? (slots + EGR_BWD_TEAM - 1u) / EGR_BWD_TEAM : slots), block(teams ? EGR_WAVE * EGR_BWD_TEAM : EGR_WAVE);
+    if (batch) {
+        if (teams) hipLaunchKernelGGL(k_backward_batch<EGR_BWD_TEAM>, grid, block, 0, s, v);
+        else hipLaunchKernelGGL(k_backward_batch<1>, grid, block, 0, s, v);
+    } else {
+        if (teams) hipLaunchKernelGGL(k_backward_chain<EGR_BWD_TEAM>, grid, block, 0, s, v);
+        else hipLaunchKernelGGL(k_backward_chain<1>, grid, block, 0, s, v);
+    }
+    egr_stamp_end(c, s);
+}
+
+// The last step of a grad launch: the gradient rows to the caller's tensors.
+void launch_grad_gather(egr_context *c, const DeviceView &v, hipStream_t s) {
+    if (!(v.n && (v.num_tasks || c->grad_overwrite))) return; // (a rank without tiles still owes its per-launch buffer a row of zeros)
+    egr_stamp_begin(c, "backward_grad_gather", s);
+    // (per-launch buffer: the FIRST grad launch after the caller consumed the buffer stores, any further one before the next
+    // egr_grad_delta_consumed adds - two launches before a fold never drop the first one's gradients)
+    if (v.grad_overwrite) hipLaunchKernelGGL(k_grad_gather<true>, dim3((v.n + 255u) / 256u), dim3(256), 0, s, v);
+    else hipLaunchKernelGGL(k_grad_gather<false>, dim3((v.n + 255u) / 256u), dim3(256), 0, s, v);
+    egr_stamp_end(c, s);
+    if (c->grad_overwrite) c->delta_pending = true;
+}
+
+// Diagnostic exports: one zeroed device buffer of EGR_NSTEPS x pixels elements of type T, filled by KERNEL, copied to the host.
+template <class T, void (*KERNEL)(DeviceView, T *)> void export_per_step(egr_context *c, void *host_out, hipStream_t s) {
+    DeviceView v = egr_make_view(c);
+    const size_t bytes = (size_t)EGR_NSTEPS * v.num_pixels * sizeof(T);
+    struct DevBuf { // freed on every way out (an EGR_HIP below may throw)
+        T *p = nullptr;
+        ~DevBuf() { if (p) (void)hipFree(p); }
+    } dev;
+    EGR_HIP(hipMalloc((void **)&dev.p, bytes));
+    EGR_HIP(hipMemsetAsync(dev.p, 0, bytes, s));
+    if (v.num_tasks) hipLaunchKernelGGL(KERNEL, dim3(std::min(v.num_tasks, 65535u)), dim3(EGR_WAVE), 0, s, v, dev.p);
+    EGR_HIP(hipMemcpyAsync(host_out, dev.p, bytes, hipMemcpyDeviceToHost, s));
+    EGR_HIP(hipStreamSynchronize(s));
+}
+
+} // namespace
+
+void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s) {
+    const DeviceView v = egr_make_view(c);
+    launch_begin(c, v, grads, live_fresh, nullptr, s);
     if (v.num_tasks) {
-        const dim3 sgrid(std::max(1u, std::min(c->num_slots, v.num_tasks)));
-        egr_stamp_begin(c, "forward_chain", s);
-        // (the chain exists as single-wave workgroups and as teams of EGR_TEAM waves: launches with egr_set_team_help(1) take the teams)
-        auto launch_forward = [&](auto team_tag) {
-            constexpr uint32_t T = (uint32_t) decltype(team_tag)::value;
-            const dim3 fgrid((sgrid.x + T - 1u) / T), fblock(EGR_WAVE * T); // (num_slots is a multiple of EGR_TEAM: every wave of a team has its scratch)
-            if (grads) {
-                if (v.cube_mode) hipLaunchKernelGGL((k_forward_chain<true, true, (int)T>), fgrid, fblock, 0, s, v);
-                else hipLaunchKernelGGL((k_forward_chain<true, false, (int)T>), fgrid, fblock, 0, s, v);
-            } else {
-                if (v.cube_mode) hipLaunchKernelGGL((k_forward_chain<false, true, (int)T>), fgrid, fblock, 0, s, v);
-                else hipLaunchKernelGGL((k_forward_chain<false, false, (int)T>), fgrid, fblock, 0, s, v);
-            }
-        };
-        if (v.team_help) launch_forward(std::integral_constant<int, EGR_TEAM>{});
-        else launch_forward(std::integral_constant<int, 1>{});
-        egr_stamp_end(c, s);
+        launch_forward_chain(c, v, v.num_tasks, grads ? ForwardKernel::single_grads : ForwardKernel::single, s);
         if (grads) {
-            hipLaunchKernelGGL(k_order_backward, dim3(8), dim3(256), 0, s, v);
-            egr_stamp_begin(c, "backward_chain", s);
-            // (under-filled ranks: the backward chain as teams whose waves without tiles take batches of their mates' bounce hits - gradients are
-            // atomic adds, so no result depends on who sends them; a whole image keeps single-wave workgroups: a team's LDS is only released with its last wave)
-            // (egr_set_team_help(1) takes the teams of both chains: tests/test_hip_parity.py)
-            const bool backward_teams = v.team_help == 1 || (c->world > 1 && (uint64_t)(v.num_tasks >> (v.task_shift - 2u)) < 2ull * c->num_slots);
-            if (backward_teams) hipLaunchKernelGGL(k_backward_chain<EGR_BWD_TEAM>, dim3((sgrid.x + EGR_BWD_TEAM - 1u) / EGR_BWD_TEAM), dim3(EGR_WAVE * EGR_BWD_TEAM), 0, s, v);
-            else hipLaunchKernelGGL(k_backward_chain<1>, sgrid, block, 0, s, v);
-            egr_stamp_end(c, s);
+            launch_backward_chain(c, v, v.num_tasks, false, s);
         } else {
             egr_stamp_begin(c, "write_outputs", s);
-            hipLaunchKernelGGL(k_finish, dim3(std::max(1u, std::min(v.num_tasks, 65535u))), block, 0, s, v);
+            hipLaunchKernelGGL(k_finish, dim3(std::max(1u, std::min(v.num_tasks, 65535u))), dim3(EGR_WAVE), 0, s, v);
             egr_stamp_end(c, s);
         }
     }
-    if (grads && v.n && (v.num_tasks || c->grad_overwrite)) { // (a rank without tiles still owes its per-launch buffer a row of zeros)
-        egr_stamp_begin(c, "backward_grad_gather", s);
-        // (per-launch buffer: the FIRST grad launch after the caller consumed the buffer stores, any further one before the next
-        // egr_grad_delta_consumed adds - two launches before a fold never drop the first one's gradients)
-        if (v.grad_overwrite) hipLaunchKernelGGL(k_grad_gather<true>, dim3((v.n + 255u) / 256u), dim3(256), 0, s, v);
-        else hipLaunchKernelGGL(k_grad_gather<false>, dim3((v.n + 255u) / 256u), dim3(256), 0, s, v);
-        egr_stamp_end(c, s);
-        if (c->grad_overwrite) c->delta_pending = true;
-    }
+    if (grads) launch_grad_gather(c, v, s);
     hipLaunchKernelGGL(k_epilogue, dim3(1), dim3(64), 0, s, v, grads ? 1 : 0);
 }
 
@@ -1709,33 +1796,14 @@ void egr_render_views_launch(egr_context *c, const egr_view_batch *b, bool live_
     const uint32_t B = std::min(F, std::max(1u, c->batch_frames));
     egr_batch_reserve(c, B, V);
     if (!c->batch_carry) egr_dev_alloc(c, c->batch_carry, (size_t)EGR_BATCH_CARRY_FLOATS * c->width * c->height);
-    DeviceView v = egr_make_view(c);
-    v.state = c->batch_state, v.state_stride = c->state_stride * c->batch_alloc_frames;
-    v.batch_cams = c->batch_cams, v.batch_spv = b->samples_per_view, v.batch_last_frame = F - 1u;
-    v.cam.znear = c->batch_cams + (size_t)V * EGR_BATCH_CAM_FLOATS, v.cam.zfar = v.cam.znear + 1;
+    DeviceView v = batch_view(c, V, b->samples_per_view);
     const BatchOutputs out{b->final, b->rgb, b->depth, b->normal, b->f0, b->roughness};
-    egr_stamp_begin(c, "prologue+live", s);
-    hipLaunchKernelGGL(k_batch_cameras, dim3((V + 64u) / 64u), dim3(64), 0, s, b->rotation_c2w_dataset, b->camera_center, b->vertical_fov_radians, V, b->znear, b->zfar, c->batch_cams);
-    hipLaunchKernelGGL(k_batch_prologue, dim3(1), dim3(64), 0, s, v, 0);
-    EGR_HIP(hipMemsetAsync(c->stats.num_accumulated_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
-    EGR_HIP(hipMemsetAsync(c->stats.num_traversed_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
-    if (v.n && !live_fresh) hipLaunchKernelGGL(k_live, dim3((v.n + 255) / 256), dim3(256), 0, s, v, 0);
-    egr_stamp_end(c, s);
+    const BatchCameras cams = batch_cameras_of(b);
+    launch_begin(c, v, false, live_fresh, &cams, s);
     for (uint32_t f0 = 0; f0 < F && v.num_tasks; f0 += B) {
         v.batch_frame0 = f0, v.batch_frames = std::min(B, F - f0);
         hipLaunchKernelGGL(k_batch_chunk_begin, dim3(1), dim3(64), 0, s, v);
-        const uint32_t tasks = v.num_tasks * v.batch_frames;
-        const dim3 sgrid(std::max(1u, std::min(c->num_slots, tasks)));
-        egr_stamp_begin(c, "forward_chain", s);
-        auto launch_forward = [&](auto team_tag) {
-            constexpr uint32_t T = (uint32_t) decltype(team_tag)::value;
-            const dim3 fgrid((sgrid.x + T - 1u) / T), fblock(EGR_WAVE * T);
-            if (v.cube_mode) hipLaunchKernelGGL((k_forward_batch<true, (int)T>), fgrid, fblock, 0, s, v);
-            else hipLaunchKernelGGL((k_forward_batch<false, (int)T>), fgrid, fblock, 0, s, v);
-        };
-        if (v.team_help) launch_forward(std::integral_constant<int, EGR_TEAM>{});
-        else launch_forward(std::integral_constant<int, 1>{});
-        egr_stamp_end(c, s);
+        launch_forward_chain(c, v, v.num_tasks * v.batch_frames, ForwardKernel::batch, s);
         egr_stamp_begin(c, "write_outputs", s);
         hipLaunchKernelGGL(k_finish_batch, dim3(std::max(1u, std::min(v.num_tasks, 65535u))), dim3(EGR_WAVE), 0, s, v, out, c->batch_carry);
         egr_stamp_end(c, s);
@@ -1763,82 +1831,24 @@ void egr_train_views_launch(egr_context *c, const egr_train_batch *b, bool live_
         egr_dev_alloc(c, c->train_order, tasks);
         c->train_alloc_frames = B, c->train_blocks_cap = cap;
     }
-    DeviceView v = egr_make_view(c);
-    v.state = c->batch_state, v.state_stride = c->state_stride * c->batch_alloc_frames;
-    v.batch_cams = c->batch_cams, v.batch_spv = 1u, v.batch_last_frame = V - 1u;
-    v.cam.znear = c->batch_cams + (size_t)V * EGR_BATCH_CAM_FLOATS, v.cam.zfar = v.cam.znear + 1;
+    DeviceView v = batch_view(c, V, 1u);
     v.hit_arena = c->train_arena, v.hit_blocks_cap = c->train_blocks_cap, v.task_last_block = c->train_last_block, v.task_cost = c->train_cost, v.bwd_order = c->train_order;
     const float *const tgt[6] = {b->target_diffuse, b->target_specular, b->target_depth, b->target_normal, b->target_roughness, b->target_f0};
     for (int k = 0; k < 6; k++) v.batch_targets[k] = tgt[k];
-    egr_stamp_begin(c, "prologue+live", s);
-    hipLaunchKernelGGL(k_batch_cameras, dim3((V + 64u) / 64u), dim3(64), 0, s, b->rotation_c2w_dataset, b->camera_center, b->vertical_fov_radians, V, b->znear, b->zfar, c->batch_cams);
-    hipLaunchKernelGGL(k_batch_prologue, dim3(1), dim3(64), 0, s, v, 1);
-    EGR_HIP(hipMemsetAsync(c->stats.num_accumulated_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
-    EGR_HIP(hipMemsetAsync(c->stats.num_traversed_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
-    if (v.n && !live_fresh) hipLaunchKernelGGL(k_live, dim3((v.n + 255) / 256), dim3(256), 0, s, v, 1);
-    egr_stamp_end(c, s);
+    const BatchCameras cams = batch_cameras_of(b);
+    launch_begin(c, v, true, live_fresh, &cams, s);
     for (uint32_t f0 = 0; f0 < V && v.num_tasks; f0 += B) {
         v.batch_frame0 = f0, v.batch_frames = std::min(B, V - f0);
         hipLaunchKernelGGL(k_batch_chunk_begin, dim3(1), dim3(64), 0, s, v);
-        const uint32_t tasks = v.num_tasks * v.batch_frames;
-        const dim3 sgrid(std::max(1u, std::min(c->num_slots, tasks)));
-        egr_stamp_begin(c, "forward_chain", s);
-        auto launch_forward = [&](auto team_tag) {
-            constexpr uint32_t T = (uint32_t) decltype(team_tag)::value;
-            const dim3 fgrid((sgrid.x + T - 1u) / T), fblock(EGR_WAVE * T);
-            if (v.cube_mode) hipLaunchKernelGGL((k_forward_batch_grads<true, (int)T>), fgrid, fblock, 0, s, v);
-            else hipLaunchKernelGGL((k_forward_batch_grads<false, (int)T>), fgrid, fblock, 0, s, v);
-        };
-        if (v.team_help) launch_forward(std::integral_constant<int, EGR_TEAM>{});
-        else launch_forward(std::integral_constant<int, 1>{});
-        egr_stamp_end(c, s);
-        DeviceView ov = v; // k_order_backward sorts every queue chunk of the (tasks x frames) range, the chunks the backward's wave_next_task hands out
-        ov.num_tasks = tasks;
-        hipLaunchKernelGGL(k_order_backward, dim3(8), dim3(256), 0, s, ov);
-        egr_stamp_begin(c, "backward_chain", s);
-        // (the team rule of egr_trace_launch, applied to the chunk's tiles)
-        const bool backward_teams = v.team_help == 1 || (c->world > 1 && (uint64_t)(tasks >> (v.task_shift - 2u)) < 2ull * c->num_slots);
-        if (backward_teams) hipLaunchKernelGGL(k_backward_batch<EGR_BWD_TEAM>, dim3((sgrid.x + EGR_BWD_TEAM - 1u) / EGR_BWD_TEAM), dim3(EGR_WAVE * EGR_BWD_TEAM), 0, s, v);
-        else hipLaunchKernelGGL(k_backward_batch<1>, sgrid, dim3(EGR_WAVE), 0, s, v);
-        egr_stamp_end(c, s);
+        launch_forward_chain(c, v, v.num_tasks * v.batch_frames, ForwardKernel::batch_grads, s);
+        launch_backward_chain(c, v, v.num_tasks * v.batch_frames, true, s);
     }
-    if (v.n && (v.num_tasks || c->grad_overwrite)) { // (as egr_trace_launch: a rank without tiles still owes its per-launch buffer a row of zeros)
-        egr_stamp_begin(c, "backward_grad_gather", s);
-        if (v.grad_overwrite) hipLaunchKernelGGL(k_grad_gather<true>, dim3((v.n + 255u) / 256u), dim3(256), 0, s, v);
-        else hipLaunchKernelGGL(k_grad_gather<false>, dim3((v.n + 255u) / 256u), dim3(256), 0, s, v);
-        egr_stamp_end(c, s);
-        if (c->grad_overwrite) c->delta_pending = true;
-    }
+    launch_grad_gather(c, v, s);
     hipLaunchKernelGGL(k_batch_epilogue, dim3(1), dim3(64), 0, s, v, V);
 }
 
-void egr_export_step_hits(egr_context *c, int32_t *host_out, hipStream_t s) {
-    DeviceView v = egr_make_view(c);
-    const size_t bytes = (size_t)EGR_NSTEPS * v.num_pixels * sizeof(int32_t);
-    struct DevBuf { // freed on every way out (an EGR_HIP below may throw)
-        int32_t *p = nullptr;
-        ~DevBuf() { if (p) (void)hipFree(p); }
-    } dev;
-    EGR_HIP(hipMalloc((void **)&dev.p, bytes));
-    EGR_HIP(hipMemsetAsync(dev.p, 0, bytes, s));
-    if (v.num_tasks) hipLaunchKernelGGL(k_export_step_hits, dim3(std::min(v.num_tasks, 65535u)), dim3(EGR_WAVE), 0, s, v, dev.p);
-    EGR_HIP(hipMemcpyAsync(host_out, dev.p, bytes, hipMemcpyDeviceToHost, s));
-    EGR_HIP(hipStreamSynchronize(s));
-}
-
-void egr_export_hit_hash(egr_context *c, uint64_t *host_out, hipStream_t s) {
-    DeviceView v = egr_make_view(c);
-    const size_t bytes = (size_t)EGR_NSTEPS * v.num_pixels * sizeof(uint64_t);
-    struct DevBuf {
-        unsigned long long *p = nullptr;
-        ~DevBuf() { if (p) (void)hipFree(p); }
-    } dev;
-    EGR_HIP(hipMalloc((void **)&dev.p, bytes));
-    EGR_HIP(hipMemsetAsync(dev.p, 0, bytes, s));
-    if (v.num_tasks) hipLaunchKernelGGL(k_export_hit_hash, dim3(std::min(v.num_tasks, 65535u)), dim3(EGR_WAVE), 0, s, v, dev.p);
-    EGR_HIP(hipMemcpyAsync(host_out, dev.p, bytes, hipMemcpyDeviceToHost, s));
-    EGR_HIP(hipStreamSynchronize(s));
-}
+void egr_export_step_hits(egr_context *c, int32_t *host_out, hipStream_t s) { export_per_step<int32_t, k_export_step_hits>(c, host_out, s); }
+void egr_export_hit_hash(egr_context *c, uint64_t *host_out, hipStream_t s) { export_per_step<unsigned long long, k_export_hit_hash>(c, host_out, s); }
 
 void egr_set_camera_launch(egr_context *c, const float *R, const float *centre, float fov, float znear, float zfar, hipStream_t s) {
     hipLaunchKernelGGL(k_set_camera, dim3(1), dim3(64), 0, s, c->cam, R, centre, fov, znear, zfar);

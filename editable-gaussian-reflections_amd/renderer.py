@@ -255,6 +255,15 @@ def render(camera, raytracer: GaussianRaytracer, targets_available=True, force_u
 VIEW_OUTPUTS = ("final", "rgb", "depth", "normal", "roughness", "f0")
 
 
+def _stack_cameras(cameras):
+    """The cameras of a batch as the tensors the batch launches take: R [V,3,3] (dataset c2w rotations), centers [V,3], fovy [V]."""
+    as_t = lambda x: torch.from_numpy(np.asarray(x)).float() if isinstance(x, np.ndarray) else torch.as_tensor(x).float()
+    R = torch.stack([as_t(c.R).cuda() for c in cameras]) if cameras else torch.zeros((0, 3, 3), device="cuda")
+    centers = torch.stack([as_t(c.camera_center).cuda() for c in cameras]) if cameras else torch.zeros((0, 3), device="cuda")
+    fovy = torch.tensor([float(c.FoVy) for c in cameras], dtype=torch.float32, device="cuda")
+    return R, centers, fovy
+
+
 def render_views(cameras, raytracer: GaussianRaytracer, spp=1, outputs=VIEW_OUTPUTS, force_update_bvh=False, znear=0.01, zfar=999.9):
     """Batched no-grad render (egr_render_views): every camera of `cameras` with `spp` accumulated samples, in as few launches as the ray
     state allows. View v equals reset_accumulators() + spp x (`render` of cameras[v] with accumulate_samples = spp > 1) bit for bit when team
@@ -268,10 +277,7 @@ def render_views(cameras, raytracer: GaussianRaytracer, spp=1, outputs=VIEW_OUTP
         outputs = ("final",) + outputs  # (the library always writes it)
     m = raytracer.cuda_module
     with torch.no_grad():
-        as_t = lambda x: torch.from_numpy(np.asarray(x)).float() if isinstance(x, np.ndarray) else torch.as_tensor(x).float()
-        R = torch.stack([as_t(c.R).cuda() for c in cameras]) if cameras else torch.zeros((0, 3, 3), device="cuda")
-        centers = torch.stack([as_t(c.camera_center).cuda() for c in cameras]) if cameras else torch.zeros((0, 3), device="cuda")
-        fovy = torch.tensor([float(c.FoVy) for c in cameras], dtype=torch.float32, device="cuda")
+        R, centers, fovy = _stack_cameras(cameras)
         raytracer._export_param_values()
         if force_update_bvh:
             m.update_bvh(True)
@@ -304,10 +310,7 @@ def train_views(cameras, raytracer: GaussianRaytracer, targets_available=True, z
     m = raytracer.cuda_module
     W, H = raytracer.image_width, raytracer.image_height
     with torch.no_grad():
-        as_t = lambda x: torch.from_numpy(np.asarray(x)).float() if isinstance(x, np.ndarray) else torch.as_tensor(x).float()
-        R = torch.stack([as_t(c.R).cuda() for c in cameras]) if cameras else torch.zeros((0, 3, 3), device="cuda")
-        centers = torch.stack([as_t(c.camera_center).cuda() for c in cameras]) if cameras else torch.zeros((0, 3), device="cuda")
-        fovy = torch.tensor([float(c.FoVy) for c in cameras], dtype=torch.float32, device="cuda")
+        R, centers, fovy = _stack_cameras(cameras)
         targets = []
         for _, attr, ch in TRAIN_TARGETS:
             imgs = [getattr(c, attr, None) if targets_available else None for c in cameras]

@@ -26,6 +26,23 @@ def ren():
     return importlib.import_module(PKG + ".renderer")
 
 
+def views(syn, n, step=0.15):
+    """n cameras inside the synthetic room: the default one, then moved and turned a little, with other fields of view."""
+    base = syn.default_camera()
+    cams = []
+    for i in range(n):
+        eye = base["origin"].astype(np.float64) + np.array([step * i, -step * 2 / 3 * i, step / 3 * i])
+        cams.append(dict(origin=eye.astype(np.float32), c2w=syn.look_at(eye, (1.2 - 0.2 * i, 0.5 + 0.1 * i, -0.9)).astype(np.float32),
+                         fov=np.float32(0.6911 + 0.07 * i), znear=np.float32(0.01), zfar=np.float32(999.9)))
+    return cams
+
+
+def tracer(ren, syn, W=64, H=48, N=3000, seed=5, variant="trained", fwd=8_000_000, bwd=1_000_000, **kw):
+    """A tracer on a synthetic scene of the batch tests' size (the default hit arena is a no-grad render's: grad tests pass their own `bwd`)."""
+    g = syn.make_scene(N, variant, seed=seed)
+    return ren.GaussianRaytracer(ren.GaussianParams(g), W, H, ppll_forward_size=fwd, ppll_backward_size=bwd, **kw)
+
+
 def psnr(a, b):
     mse = float(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2))
     return 150.0 if mse == 0 else 10.0 * np.log10(1.0 / mse)

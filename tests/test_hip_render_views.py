@@ -5,36 +5,13 @@ import importlib
 import numpy as np
 import pytest
 
-from hip_common import BOTH_HELP_MODES, cam_obj, make_pair, psnr, report
+from hip_common import BOTH_HELP_MODES, cam_obj, make_pair, psnr, ren, report, tracer, views  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 PKG = "editable-gaussian-reflections_amd"
 FIELDS = ("final", "rgb", "depth", "normal", "roughness", "f0")
-
-
-@pytest.fixture(scope="module")
-def ren():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU; the product has no CPU fallback")
-    return importlib.import_module(PKG + ".renderer")
-
-
-def views(syn, n):
-    """n cameras inside the synthetic room: the default one, then moved and turned a little, with other fields of view."""
-    base = syn.default_camera()
-    cams = []
-    for i in range(n):
-        eye = base["origin"].astype(np.float64) + np.array([0.15 * i, -0.1 * i, 0.05 * i])
-        cams.append(dict(origin=eye.astype(np.float32), c2w=syn.look_at(eye, (1.2 - 0.2 * i, 0.5 + 0.1 * i, -0.9)).astype(np.float32),
-                         fov=np.float32(0.6911 + 0.07 * i), znear=np.float32(0.01), zfar=np.float32(999.9)))
-    return cams
-
-
-def tracer(ren, syn, W=64, H=48, N=3000, seed=5, **kw):
-    g = syn.make_scene(N, "trained", seed=seed)
-    return ren.GaussianRaytracer(ren.GaussianParams(g), W, H, ppll_forward_size=8_000_000, ppll_backward_size=1_000_000, **kw)
 
 
 def sequential(ren, rt, cams, S, base):

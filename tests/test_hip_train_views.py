@@ -1,36 +1,19 @@
 """Multi-view training launch (egr_train_views / Raytracer.train_views / renderer.train_views): the gradients of V views in one call, held against V
 sequential grad launches into a zeroed gradient buffer and against the fp32 oracle (include/egr_raytracer.h: egr_train_batch). Gradient bars are per
 tensor, relative to that tensor's max |grad|."""
-import importlib
+import functools
 
 import numpy as np
 import pytest
 
-from hip_common import BOTH_HELP_MODES, GRAD_KEYS, cam_obj, generic_targets, hip_grads, make_pair, report
+import hip_common
+from hip_common import BOTH_HELP_MODES, GRAD_KEYS, cam_obj, generic_targets, hip_grads, make_pair, ren, report, views  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-PKG = "editable-gaussian-reflections_amd"
 TARGET_KEYS = ("diffuse", "specular", "depth", "normal", "roughness", "f0")
-
-
-@pytest.fixture(scope="module")
-def ren():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU; the product has no CPU fallback")
-    return importlib.import_module(PKG + ".renderer")
-
-
-def views(syn, n, step=0.15):
-    """n cameras inside the synthetic room: the default one, then moved and turned a little, with other fields of view."""
-    base = syn.default_camera()
-    cams = []
-    for i in range(n):
-        eye = base["origin"].astype(np.float64) + np.array([step * i, -step * 2 / 3 * i, step / 3 * i])
-        cams.append(dict(origin=eye.astype(np.float32), c2w=syn.look_at(eye, (1.2 - 0.2 * i, 0.5 + 0.1 * i, -0.9)).astype(np.float32),
-                         fov=np.float32(0.6911 + 0.07 * i), znear=np.float32(0.01), zfar=np.float32(999.9)))
-    return cams
+tracer = functools.partial(hip_common.tracer, bwd=8_000_000)  # (grad launches: the hit arena of a training configuration)
 
 
 def view_targets(syn, W, H, n):
@@ -40,11 +23,6 @@ def view_targets(syn, W, H, n):
         tg = generic_targets(syn, W, H)
         out.append({k: (v + np.float32(0.07 * i)).astype(np.float32) for k, v in tg.items()})
     return out
-
-
-def tracer(ren, syn, W=64, H=48, N=3000, seed=5, variant="trained", fwd=8_000_000, bwd=8_000_000, **kw):
-    g = syn.make_scene(N, variant, seed=seed)
-    return ren.GaussianRaytracer(ren.GaussianParams(g), W, H, ppll_forward_size=fwd, ppll_backward_size=bwd, **kw)
 
 
 def zero_native(rt):
