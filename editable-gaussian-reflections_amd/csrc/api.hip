@@ -422,6 +422,18 @@ int egr_debug_check_bvh(egr_context *c, void *stream) {
     return rc ? rc : bad;
 }
 
+int egr_debug_get_bvh_state(egr_context *c, float frame[6], uint32_t info[4], void *stream) {
+    if (!c || !frame || !info) return 1;
+    return guarded(c, [&] {
+        EGR_HIP(hipStreamSynchronize((hipStream_t)stream));
+        uint32_t flag = 0;
+        if (c->out_of_frame) EGR_HIP(hipMemcpy(&flag, c->out_of_frame, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        const BvhFrame fr = c->frame;
+        frame[0] = fr.ox, frame[1] = fr.oy, frame[2] = fr.oz, frame[3] = fr.sx, frame[4] = fr.sy, frame[5] = fr.sz;
+        info[0] = flag, info[1] = c->num_wide, info[2] = c->max_depth, info[3] = c->n_built;
+    });
+}
+
 const char *egr_last_error(egr_context *c) { return c ? c->last_error.c_str() : "libegr_hip: null context"; }
 
 } // extern "C"

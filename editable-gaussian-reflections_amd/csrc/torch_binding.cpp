@@ -567,6 +567,13 @@ struct Raytracer : torch::CustomClassHolder {
         check(egr_debug_get_instances(ctx, M.data_ptr<float>(), W.data_ptr<float>(), A.data_ptr<float>(), current_stream()), "debug_instances");
         return {M, W, A};
     }
+    std::tuple<Tensor, Tensor> debug_bvh_state() { // (float32[6]: the build frame's origin xyz and cells per world unit xyz; int64[4]: out_of_frame flag, wide nodes, depth, n built) on the host
+        Tensor f = torch::zeros({6}, torch::kFloat32), i = torch::zeros({4}, torch::kInt64);
+        uint32_t info[4] = {0u, 0u, 0u, 0u};
+        check(egr_debug_get_bvh_state(ctx, f.data_ptr<float>(), info, current_stream()), "debug_bvh_state");
+        for (int k = 0; k < 4; k++) i.data_ptr<int64_t>()[k] = (int64_t)info[k];
+        return {f, i};
+    }
 
     static void bind(torch::Library &m) {
         using Self = c10::intrusive_ptr<Raytracer>;
@@ -643,6 +650,7 @@ struct Raytracer : torch::CustomClassHolder {
             .def("check_bvh", &Raytracer::check_bvh)
             .def("last_error", &Raytracer::last_error)
             .def("debug_instances", &Raytracer::debug_instances)
+            .def("debug_bvh_state", &Raytracer::debug_bvh_state)
             .def("debug_step_hits", &Raytracer::debug_step_hits)
             .def("debug_hit_sequence_hash", &Raytracer::debug_hit_sequence_hash);
     }

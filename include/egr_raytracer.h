@@ -354,6 +354,11 @@ int egr_debug_lean_arith(int device, const float *a, const float *b, float *quot
 /* BVH self-check: every leaf box equals its instance box, every internal box is the union of its children,
  * every visible instance is reachable exactly once. Returns 0 if consistent. Host-side; synchronises. */
 int egr_debug_check_bvh(egr_context *ctx, void *hip_stream);
+/* State of the tree for tests of the refit (read-only; an additive symbol of library version 0.8, egr_version() is unchanged): frame = origin xyz and
+ * scale xyz (cells per world unit) of the 16-bit quantisation frame the last rebuild fixed; info = {out_of_frame flag (1: some box of the last refit left the
+ * frame and carries the -inf / +inf sentinel cells, so the walks run their sentinel decode), wide nodes, depth of the wide tree, gaussian count the tree was
+ * built for}. Host pointers; synchronises. */
+int egr_debug_get_bvh_state(egr_context *ctx, float frame[6], uint32_t info[4], void *hip_stream);
 
 const char *egr_last_error(egr_context *ctx);
 const char *egr_version(void);

@@ -361,6 +361,7 @@ def test_update_bvh_snapshot_semantics(ren, orc, syn, bounces):
     assert psnr(hip_outputs(rt)["output_rgb"][0], ref["output_rgb"][0]) > 60
     with torch.no_grad():
         rt(cam_obj(ren, cam), force_update_bvh=True)
+    assert int(rt.cuda_module.debug_bvh_state()[1][0]) == 1  # the refit did store sentinel cells: the launch above ran the out-of-frame decode
     o.update_bvh()
     ref2 = o.raytrace(False)
     assert psnr(hip_outputs(rt)["output_rgb"][0], ref2["output_rgb"][0]) > 60
