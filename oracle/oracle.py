@@ -2,8 +2,9 @@
 
 TEST INFRASTRUCTURE ONLY: may be imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py. The shipped HIP path never imports this module.
-Parity status: unpinned by the reference (no golden numbers exist upstream for this path);
-pinned by the known-answer / finite-difference / golden-fixture tests in tests/. The finite differences cover the primary step
+Parity status: pinned by the reference's own shader code built for the CPU (oracle/reference.py, tests/test_oracle_vs_reference.py; its outputs
+for the golden scene travel as tests/golden/scene_2k_64_reference.npz, tests/test_reference_fixture.py), and by the known-answer /
+finite-difference / golden-fixture tests in tests/. The finite differences cover the primary step
 (tests/test_oracle_gradients.py) and, through Oracle.set_frozen_chain and frozen_chain_loss, the backward of the bounce steps
 (tests/test_oracle_bounce_gradients.py).
 """
@@ -84,6 +85,7 @@ def lib():
         L.orc_set_camera.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double]
         L.orc_set_gaussians.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 8
         L.orc_set_use_bvh.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.orc_set_inverse_from_transform.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.orc_set_partition.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.orc_set_pixel_mask.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.orc_set_frozen_chain.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
@@ -99,6 +101,11 @@ def lib():
         L.orc_lcg.argtypes = [ctypes.c_void_p]
         L.orc_sample_cook_torrance.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]
         L.orc_cook_torrance_weight.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
+        for name, nptr in (("sample_cook_torrance", 5), ("cook_torrance_weight", 6), ("compute_scaling_factor", 4), ("eval_gaussian", 3),
+                           ("normalize_act", 2), ("backward_normalize_act", 3)):
+            getattr(L, "orc_unit_" + name).argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * nptr
+        L.orc_unit_activation.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        L.orc_unit_activation_backward.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         _lib = L
     return _lib
 
@@ -121,7 +128,7 @@ class Oracle:
     `update_bvh` = snapshot of the instance transforms, `raytrace` = one launch.
     """
 
-    def __init__(self, width, height, double=False, threads=None, use_bvh=True):
+    def __init__(self, width, height, double=False, threads=None, use_bvh=True, inverse_from_transform=False):
         self.L = lib()
         self.W, self.H = int(width), int(height)
         self.double = bool(double)
@@ -130,6 +137,8 @@ class Oracle:
         self.total_num_calls = 0
         self.n = 0
         self.L.orc_set_use_bvh(self.h, int(use_bvh))
+        # W = M^-1 of update_bvh: the analytic diag(1/size) R^T (default), or the fp64 inverse of the rounded 3x4, as oracle/ref_driver.cpp forms it
+        self.L.orc_set_inverse_from_transform(self.h, int(inverse_from_transform))
         if threads is not None:
             self.L.orc_set_threads(int(threads))
         self.set_camera(np.zeros(3), np.eye(3), 1.0, 0.01, 999.9)
@@ -316,6 +325,24 @@ def cook_torrance_weight(N, V, L, roughness, f0):
     w = np.zeros(3)
     lib().orc_cook_torrance_weight(_ptr(_f64(N)), _ptr(_f64(V)), _ptr(_f64(L)), float(roughness), _ptr(_f64(f0)), _ptr(w))
     return w
+
+
+ACTIVATIONS = {"sigmoid": 0, "relu": 1, "clipped_relu": 2, "exp": 3}
+
+
+def unit(name, *arrays, double=False, which=None):
+    """The oracle's small functions over arrays of inputs, in fp32 (every value passes through float) or fp64: name in sample_cook_torrance(N, V,
+    roughness, u[.,2]), cook_torrance_weight(N, V, L, roughness, f0), compute_scaling_factor(opacity, alpha_threshold, exp_power), eval_gaussian(
+    local_hit, exp_power), activation(x) / activation_backward(dL_dy, y) with which in ACTIVATIONS, normalize_act(x[.,4]), backward_normalize_act(
+    dL_dy, x). Returns float64 of the first array's shape (scalars per row for compute_scaling_factor / eval_gaussian)."""
+    arrs = [_f64(a) for a in arrays]
+    per_row = {"sample_cook_torrance": 3, "cook_torrance_weight": 3, "eval_gaussian": 3, "normalize_act": 4, "backward_normalize_act": 4}.get(name, 1)
+    count = arrs[0].size // per_row
+    scalar_out = name in ("compute_scaling_factor", "eval_gaussian")
+    out = np.zeros(count if scalar_out else arrs[0].shape, np.float64)
+    args = [int(double)] + ([ACTIVATIONS[which]] if which is not None else []) + [count] + [_ptr(a) for a in arrs] + [_ptr(out)]
+    getattr(lib(), "orc_unit_" + name)(*args)
+    return out
 
 
 def l1_loss(out, targets, cfg, num_bounces):

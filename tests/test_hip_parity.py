@@ -253,9 +253,8 @@ def test_forward_parity_with_bounces_and_jitter(ren, orc, syn, team_help):
         assert (ref["effective_steps"] > 1).mean() > 0.5  # the bounce steps were really exercised
 
 
-@BOTH_HELP_MODES
-def test_golden_fixture(ren, orc, syn, team_help):
-    z = np.load(os.path.join(GOLD, "scene_2k_64.npz"))
+def _check_golden_fixture(ren, team_help, name):
+    z = np.load(os.path.join(GOLD, name))
     W, H = int(z["W"]), int(z["H"])
     g = {k[2:]: z[k] for k in z.files if k.startswith("g_")}
     cam = {k[4:]: z[k] for k in z.files if k.startswith("cam_")}
@@ -277,6 +276,19 @@ def test_golden_fixture(ren, orc, syn, team_help):
     for k in GRAD_KEYS:
         ref = z["ref_" + k]
         assert np.abs(gr[k] - ref).max() / (np.abs(ref).max() + 1e-30) < 1e-3, k
+
+
+@BOTH_HELP_MODES
+def test_golden_fixture(ren, orc, syn, team_help):
+    """The golden 2k scene against the fp32 CPU oracle's outputs (tests/golden/make_golden_scene.py)."""
+    _check_golden_fixture(ren, team_help, "scene_2k_64.npz")
+
+
+@BOTH_HELP_MODES
+def test_golden_fixture_reference(ren, orc, syn, team_help):
+    """The same scene, launches and bars against what the REFERENCE's own shader code wrote when it was run on the CPU
+    (tests/golden/make_reference_scene.py): the kernels held to the reference's numbers, with no oracle in between."""
+    _check_golden_fixture(ren, team_help, "scene_2k_64_reference.npz")
 
 
 # ------------------------------------------------------------------------------------------------ backward
