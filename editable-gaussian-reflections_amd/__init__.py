@@ -7,10 +7,12 @@ backend: if the native libraries are missing or no GPU is present this fails lou
 """
 import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD_DIR = os.path.join(_HERE, "build")
-GAUSS_TRACER_PATH = os.path.join(BUILD_DIR, "libraytracer.so")
-HIP_LIB_PATH = os.path.join(BUILD_DIR, "libegr_hip.so")
+from .build import lib_paths, variant_dir, variant_name
+
+# The build-time settings that select a variant build (build.py: VARIANT_SETTINGS) select the same library here; none set: the product in build/.
+VARIANT = variant_name(os.environ)
+BUILD_DIR = variant_dir(os.environ)
+HIP_LIB_PATH, GAUSS_TRACER_PATH = lib_paths(os.environ)
 LOADED = False
 
 
@@ -19,6 +21,10 @@ def load_library():
     if not LOADED:
         import torch
 
+        if VARIANT and not (os.path.exists(GAUSS_TRACER_PATH) and os.path.exists(HIP_LIB_PATH)):  # selected but not built: never the product in its place
+            raise RuntimeError(
+                f"variant build '{VARIANT}' is selected by the environment but not built: expected {GAUSS_TRACER_PATH} and {HIP_LIB_PATH}; "
+                "run `tools/build_variant.sh` with the same settings")
         if not (os.path.exists(GAUSS_TRACER_PATH) and os.path.exists(HIP_LIB_PATH)):
             raise RuntimeError(
                 f"native libraries not built: expected {GAUSS_TRACER_PATH} and {HIP_LIB_PATH}; "

@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "egr_internal.hpp"
+#include "egr_diag.hpp"
 #include "egr_device.hpp" // egr_div_rn / egr_sqrt_rn: the debug kernel below runs exactly the functions the hot kernels use
 
 void egr_copy_final_to_denoised(egr_context *c, hipStream_t s);
@@ -86,7 +87,12 @@ template <class F> int traced(egr_context *c, void *stream, F &&launch) {
 
 extern "C" {
 
-const char *egr_version(void) { return "egr-hip 0.8 (gfx950)"; } // 0.8: egr_render_views, egr_set_batch_frames, and (additive, same version) egr_train_views; 0.7: strands removed, egr_set_strands accepts only 1; 0.6: egr_grad_delta_consumed (round 5); 0.4: egr_counters grew (round 3), egr_get_counters_ex, egr_set_rays_per_task; 0.5: egr_set_team_help
+#ifdef EGR_VARIANT_NAME // a variant build (build.py) carries its name after the product's string
+#define EGR_VERSION_SUFFIX " variant " EGR_VARIANT_NAME
+#else
+#define EGR_VERSION_SUFFIX ""
+#endif
+const char *egr_version(void) { return "egr-hip 0.8 (gfx950)" EGR_VERSION_SUFFIX; } // 0.8: egr_render_views, egr_set_batch_frames, and (additive, same version) egr_train_views; 0.7: strands removed, egr_set_strands accepts only 1; 0.6: egr_grad_delta_consumed (round 5); 0.4: egr_counters grew (round 3), egr_get_counters_ex, egr_set_rays_per_task; 0.5: egr_set_team_help
 
 int egr_create(egr_context **out, int device, int width, int height, int64_t ppll_forward_size, int64_t ppll_backward_size) {
     if (!out || width <= 0 || height <= 0) return 1;
@@ -293,27 +299,7 @@ int egr_get_counters_ex(egr_context *c, void *out_raw, size_t out_bytes, void *s
         out->arena_blocks_used = w[CW_HIT_BUMP], out->arena_blocks_cap = c->hit_blocks_cap;
         out->ext_blocks_used = w[CW_EXT_BUMP], out->ext_blocks_cap = c->ext_blocks_cap;
         if (getenv("EGR_DEBUG_EXT")) fprintf(stderr, "[egr] extension blocks used %u of %u, cand_cap %u\n", w[CW_EXT_BUMP], c->ext_blocks_cap, c->cand_cap);
-        if (getenv("EGR_PRINT_TRAVERSAL_STATS")) {
-            for (int k = 0; k < 2; k++)
-                fprintf(stderr, "[egr stats %s] lane node visits %llu, lane leaf-box hits %llu, wave inner iterations %llu, wave outer rounds %llu\n", k ? "bounce" : "primary",
-                        (unsigned long long)u64(CW_DBG + 8 * k), (unsigned long long)u64(CW_DBG + 8 * k + 2), (unsigned long long)u64(CW_DBG + 8 * k + 4), (unsigned long long)u64(CW_DBG + 8 * k + 6));
-            for (int k = 0; k < 3; k++)
-                fprintf(stderr, "[egr stats forward step %d] first wave exit -> last wave exit: %.3f ms\n", k,
-                        (double)(u64(CW_DBG3 + 4 * k + 2) - u64(CW_DBG3 + 4 * k)) / 100e6 * 1e3);
-            fprintf(stderr, "[egr stats team] offers made %u, offers walked by helpers %u (their walk batches: %u), owner walk batches that left >= EGR_DONATE_MIN pairs on the stack %u\n", c->control_host[CW_DBG3 + 12], c->control_host[CW_DBG3 + 13], c->control_host[CW_DBG3 + 14], c->control_host[CW_DBG3 + 15]);
-            for (int k = 0; k < 2; k++)
-                fprintf(stderr, "[egr stats backward %s] wave-cycles(s_memtime) per-hit math %llu, neighbour combine + LDS table %llu, wide adds %llu, table flush %llu; hit rows %llu\n",
-                        k ? "bounce" : "primary", (unsigned long long)u64(CW_DBG2 + 16 + 10 * k), (unsigned long long)u64(CW_DBG2 + 18 + 10 * k),
-                        (unsigned long long)u64(CW_DBG2 + 20 + 10 * k), (unsigned long long)u64(CW_DBG2 + 22 + 10 * k), (unsigned long long)u64(CW_DBG2 + 24 + 10 * k));
-            fprintf(stderr, "[egr stats forward chain] wave-cycles(s_memtime) whole chains (task pull to end) %llu, of which step epilogues %llu\n", (unsigned long long)u64(CW_DBG2 + 12), (unsigned long long)u64(CW_DBG2 + 8));
-            fprintf(stderr, "[egr stats primary composite] wave-cycles(s_memtime) selection scans %llu, arena block %llu, (alpha, record) fetch %llu, pass 1 %llu, appearance pass %llu\n", (unsigned long long)u64(CW_DBG2 + 40), (unsigned long long)u64(CW_DBG2 + 42), (unsigned long long)u64(CW_DBG2 + 44), (unsigned long long)u64(CW_DBG2 + 46), (unsigned long long)u64(CW_DBG2 + 48));
-            fprintf(stderr, "[egr stats primary lists] tiles by their longest candidate list: <=16: %u, <=24: %u, <=32: %u, <=40: %u, <=48: %u, <=64: %u, longer: %u\n", w[CW_DBG2 + 50], w[CW_DBG2 + 51], w[CW_DBG2 + 52], w[CW_DBG2 + 53], w[CW_DBG2 + 54], w[CW_DBG2 + 55], w[CW_DBG2 + 56]);
-            fprintf(stderr, "[egr stats primary leaf filter] leaves before the sphere / pyramid test %llu, wave-cycles in the test %llu\n", (unsigned long long)u64(CW_DBG2 + 38), (unsigned long long)u64(CW_DBG2 + 36));
-            for (int k = 0; k < 2; k++)
-                fprintf(stderr, "[egr stats %s] wave-cycles(s_memtime) traversal %llu composite %llu | of the traversal: leaf evaluation (frustum walk) %llu (slot +8: %llu)\n", k ? "bounce" : "primary",
-                        (unsigned long long)u64(CW_DBG2 + 4 * k), (unsigned long long)u64(CW_DBG2 + 4 * k + 2), (unsigned long long)u64(CW_DBG2 + 8 + 4 * k + 2),
-                        (unsigned long long)u64(CW_DBG2 + 8 + 4 * k));
-        }
+        if (getenv("EGR_PRINT_TRAVERSAL_STATS")) egr_diag_print(w); // (egr_diag.hpp; all zero unless this is an EGR_TRAVERSAL_STATS build)
     });
     if (rc == 0) memcpy(out_raw, &full, out_bytes < sizeof(full) ? out_bytes : sizeof(full));
     return rc;

@@ -35,11 +35,7 @@
     for (;;) {
         const uint32_t tq = wave_next_task(v.queues + 8 * EGR_QUEUE_STRIDE, BATCH ? v.num_tasks * v.batch_frames : v.num_tasks, cur_q, lane);
         if (tq == 0xFFFFFFFFu) break;
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 8 // diagnostic build: stamps of a task's BACKWARD chain in its first pixels (tools/bwd_times.py)
-        const unsigned long long bw_t0 = __builtin_amdgcn_s_memrealtime();
-        unsigned long long bw_t1 = 0ull;
-        uint32_t bw_rows0 = 0u;
-#endif
+        EGR_TIMES(unsigned long long bw_t0 = 0ull, bw_t1 = 0ull; uint32_t bw_rows0 = 0u;) EGR_TIMES_IS(8, bw_t0 = __builtin_amdgcn_s_memrealtime();) // stamps of a task's BACKWARD chain for its first pixels (tools/bwd_times.py)
         // The steps of a tile are independent in the backward (each reads its own arena chain and the forward's state, all gradients are
         // atomic adds), so their order is free: the PRIMARY step goes first and the bounce steps last - the bounce steps' batches are what
         // team mates can take (backward_task.inc), and team mates only have time once their own tiles are through, i.e. late in a heavy tile.
@@ -51,9 +47,7 @@
 #include "backward_task.inc"
             } while (false);
         }
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 8
-        bw_t1 = __builtin_amdgcn_s_memrealtime();
-#endif
+        EGR_TIMES_IS(8, bw_t1 = __builtin_amdgcn_s_memrealtime();)
         for (int step = num_bounces; step >= 1; step--) {
             constexpr bool PRIMARY = false;
             do {
@@ -65,17 +59,14 @@
             for (int s = lane; s < EGR_BQ_FLOATS; s += EGR_WAVE) gt_vals[s] = 0.0f;
             EGR_BWD_SYNC();
         }
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 8
-        {
+        EGR_TIMES_IS(8,
             const unsigned long long bw_t2 = __builtin_amdgcn_s_memrealtime();
             const uint32_t bt = v.bwd_order[tq];
             const TaskGeom btg = task_geom(v, BATCH ? batch_base_task(v, bt) : bt, lane);
             if (btg.inside) {
-                if (lane == 0) v.stats.num_traversed_per_pixel[btg.pixel_id] = (int32_t)(bw_t0 & 0x7FFFFFFFull), v.stats.num_accumulated_per_pixel[btg.pixel_id] = (int32_t)(bw_t2 & 0x7FFFFFFFull);
-                if (lane == 1) v.stats.num_traversed_per_pixel[btg.pixel_id] = (int32_t)(bw_t1 & 0x7FFFFFFFull), v.stats.num_accumulated_per_pixel[btg.pixel_id] = (int32_t)bw_rows0;
-            }
-        }
-#endif
+                if (lane == 0) v.stats.num_traversed_per_pixel[btg.pixel_id] = EGR_STAMP31(bw_t0), v.stats.num_accumulated_per_pixel[btg.pixel_id] = EGR_STAMP31(bw_t2);
+                if (lane == 1) v.stats.num_traversed_per_pixel[btg.pixel_id] = EGR_STAMP31(bw_t1), v.stats.num_accumulated_per_pixel[btg.pixel_id] = (int32_t)bw_rows0;
+            })
     }
     if constexpr (TEAM > 1) {
         // no tiles left: this wave takes batches of bounce hits its team mates have queued until all of them are through

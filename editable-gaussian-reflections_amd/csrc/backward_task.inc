@@ -13,9 +13,7 @@
         uint32_t nhits = (tg.inside && (uint32_t)step < steps_done && blk != 0xFFFFFFFFu) ? f2u(S.ld(SF(step, S_NHITS))) : 0u; // shaders.cu:157-158
         const uint32_t max_hits = wave_max_u32(nhits);
         if (max_hits == 0) continue;
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 8
-        if (PRIMARY) bw_rows0 = max_hits;
-#endif
+        EGR_TIMES_IS(8, if (PRIMARY) bw_rows0 = max_hits;)
 
         // ---- B1: output gradients (backward_pass.cu:80-108); constant along the ray ----------------------
         f3 dL_rgb = mk3(0, 0, 0), dL_n = mk3(0, 0, 0), dL_f0 = mk3(0, 0, 0);
@@ -172,12 +170,7 @@
         f3 prev_rgb = mk3(0, 0, 0), w_rgb = mk3(0, 0, 0), prev_n = mk3(0, 0, 0), w_n = mk3(0, 0, 0), prev_f0 = mk3(0, 0, 0), w_f0 = mk3(0, 0, 0);
         float prev_rough = 0, w_rough = 0, prev_depth = 0, w_depth = 0;
         const uint32_t nblocks = (max_hits + EGR_HIT_BLOCK_ROWS - 1) / EGR_HIT_BLOCK_ROWS;
-#ifdef EGR_TRAVERSAL_STATS // s_memtime per phase of a hit row: [math, neighbour combine + LDS table, wide adds] + the tile's table flush
-        unsigned long long bt_math = 0ull, bt_table = 0ull, bt_wide = 0ull, bt_rows = 0ull;
-#define EGR_BT(x) x
-#else
-#define EGR_BT(x)
-#endif
+        EGR_STATS(unsigned long long bt_math = 0ull, bt_table = 0ull, bt_wide = 0ull, bt_rows = 0ull;) // s_memtime per phase of a hit row: [math, neighbour combine + LDS table, wide adds] + the tile's table flush
         for (uint32_t b = nblocks; b-- > 0;) {
             const float4 *rows = v.hit_arena + (size_t)blk * (EGR_HIT_BLOCK_ROWS + 1) * EGR_WAVE;
             int pf_row = -1; // the row of this block whose arena entry `rec_pf` holds (requested while the row before it was worked off)
@@ -189,7 +182,7 @@
                 bool direct = false, want = false; // want: this lane's contribution looks for a slot of the table
                 uint32_t dpos = 0;
                 float gx[EGR_GT_COMPS]; // this hit's gradient components, PC_* order (what leaves the lane when `direct`: a primary hit without a table slot)
-                EGR_BT(const unsigned long long bt0 = __builtin_amdgcn_s_memtime(); unsigned long long bt1 = bt0; bt_rows++;)
+                EGR_STATS(const unsigned long long bt0 = __builtin_amdgcn_s_memtime(); unsigned long long bt1 = bt0; bt_rows++;)
                 // a row costs two dependent round trips - its arena entry, then the records the entry names: the NEXT row's entry is requested now
                 // (the request comes first and the rare direct load - the first row of a block - completes inside its own branch: with the two the other
                 // way round the compiler cannot tell how many loads are in flight where the entry is first used and waits for all of them)
@@ -249,7 +242,7 @@
                     gx[PC_RGB] = d_rgb.x, gx[PC_RGB + 1] = d_rgb.y, gx[PC_RGB + 2] = d_rgb.z, gx[PC_WEIGHT] = weight;
                     gx[PC_NORMAL] = d_n.x, gx[PC_NORMAL + 1] = d_n.y, gx[PC_NORMAL + 2] = d_n.z;
                     gx[PC_F0] = d_f0.x, gx[PC_F0 + 1] = d_f0.y, gx[PC_F0 + 2] = d_f0.z, gx[PC_ROUGH] = d_rough;
-                    EGR_BT(bt1 = __builtin_amdgcn_s_memtime();)
+                    EGR_STATS(bt1 = __builtin_amdgcn_s_memtime();)
                     // primary hits go through the wave's LDS table (trace.hip: primary_presum here, primary_table_add below, outside this divergent
                     // block: a full table is emptied by the whole wave). (Bounce tiles are incoherent - an LDS table removed only 25 % of the
                     // contributions at 15 ds_add_f32 per hit: bounce_batch sends a hit's 15 components straight to the gradient row as one record.)
@@ -257,7 +250,7 @@
                     want = primary_presum(pos, gx, lane);
                 }
                 direct = primary_table_add(v, want, dpos, gx, gt_keys, gt_vals, gt_claim, stage, lane, records);
-                EGR_BT(const unsigned long long bt2 = __builtin_amdgcn_s_memtime(); bt_math += bt1 - bt0; bt_table += bt2 - bt1;)
+                EGR_STATS(const unsigned long long bt2 = __builtin_amdgcn_s_memtime(); bt_math += bt1 - bt0; bt_table += bt2 - bt1;)
                 if (__ballot(direct) != 0ull) {
                     float lo[15];
 #pragma unroll
@@ -269,16 +262,13 @@
                     wide_add_wave<REC_PRIMARY_Q>(v, direct, dpos, hi, stage);
                     records += 2u * (uint32_t)__popcll(__ballot(direct));
                 }
-                EGR_BT(bt_wide += __builtin_amdgcn_s_memtime() - bt2;)
+                EGR_STATS(bt_wide += __builtin_amdgcn_s_memtime() - bt2;)
             }
             blk = f2u(rows[0].x); // header: previous (older) block of this chain
         }
-        EGR_BT(const unsigned long long bt3 = __builtin_amdgcn_s_memtime();)
+        EGR_STATS(const unsigned long long bt3 = __builtin_amdgcn_s_memtime();)
         records += grad_table_flush(v, gt_keys, gt_vals, stage, lane); // one flush per tile
-#ifdef EGR_TRAVERSAL_STATS
-        if (lane == 0) {
-            unsigned long long *d = reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 16 + (PRIMARY ? 0 : 10));
+        EGR_STATS(if (lane == 0) {
+            unsigned long long *d = diag64(v.control, DG_BWD_MATH_CYC, !PRIMARY);
             atomicAdd(d, bt_math), atomicAdd(d + 1, bt_table), atomicAdd(d + 2, bt_wide), atomicAdd(d + 3, __builtin_amdgcn_s_memtime() - bt3), atomicAdd(d + 4, bt_rows);
-        }
-#endif
-#undef EGR_BT
+        })

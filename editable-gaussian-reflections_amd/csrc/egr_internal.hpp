@@ -121,24 +121,21 @@ struct DeviceView { // everything a kernel needs, passed by value
 #define EGR_BATCH_CAM_FLOATS 16 // per view: origin (3), rows of w2c (9), tanf(fov / 2), pad (3)
 #define EGR_BATCH_CARRY_FLOATS (11 * EGR_NSTEPS) // running sums of a view across a chunk boundary, per pixel and step: rgb 3, depth 1, normal 3, f0 3, roughness 1
 
-enum ControlWord : int {
-    CW_ACCEPTED = 0,    // per-step 64-bit counters: accepted candidates = what the reference inserts into its forward list
-    CW_HIT_BUMP = 128,  // arena block bump allocator: a returning atomic on the path of every eighth compositing batch - ON A CACHE LINE OF ITS OWN (words 128 .. 159,
-                        // after the diagnostic words; it used to be word 8, on the line every wave adds its twelve per-step counters to when it leaves the kernel)
-    CW_STATUS = 9,
+enum ControlWord : int { // (by position)
+    CW_ACCEPTED = 0,       // per-step 64-bit counters: accepted candidates = what the reference inserts into its forward list
     CW_BUCKET_RECORDS = 7, // 64-B gradient records (wide adds) the backward chain sent to the gradient rows in this launch
-    CW_EXT_BUMP = 160,     // candidate-list extension blocks handed out in this launch (its own line too: words 160 .. 191)
-    CW_RAYS = 10,       // per-step 64-bit counters (two words each): rays[3], candidates[3], composited[3]
+    CW_STATUS = 9,
+    CW_RAYS = 10,          // per-step 64-bit counters (two words each): rays[3], candidates[3], composited[3]
     CW_CAND = 16,
     CW_COMP = 22,
-    CW_RESET_END = 28,  // words [0, CW_RESET_END) are zeroed by every launch
-    CW_LIFE_RAYS = 28,  // lifetime totals (since egr_create / egr_reset_lifetime_counters), 64-bit
+    CW_RESET_END = 28,     // words [0, CW_RESET_END) are zeroed by every launch
+    CW_LIFE_RAYS = 28,     // lifetime totals (since egr_create / egr_reset_lifetime_counters), 64-bit
     CW_LIFE_LAUNCHES = 30,
-
-    CW_DBG = 32,        // diagnostic words [CW_DBG, CW_HIT_BUMP): optional traversal statistics (EGR_TRAVERSAL_STATS builds): 8 x 64-bit
-    CW_DBG2 = 48,       // per-phase s_memtime sums: [primary traversal, primary composite, bounce traversal, bounce composite]
-    CW_DBG3 = 112,      // per forward step: min / max wave exit time (s_memrealtime)
-    CW_COUNT = 192      // (k_prologue zeroes [CW_DBG, CW_COUNT) in every launch: the diagnostic words and the lines of the two bump counters)
+                           // words [32, 128): the diagnostic words (egr_diag.hpp: DiagSlot), zeroed by k_prologue in every launch like the two lines below
+    CW_HIT_BUMP = 128,     // arena block bump allocator: a returning atomic on the path of every eighth compositing batch - ON A CACHE LINE OF ITS OWN (words 128 .. 159;
+                           // it used to be word 8, on the line every wave adds its twelve per-step counters to when it leaves the kernel)
+    CW_EXT_BUMP = 160,     // candidate-list extension blocks handed out in this launch (its own line too: words 160 .. 191)
+    CW_COUNT = 192
 };
 
 struct KernelStamp {

@@ -25,14 +25,8 @@
             bcam = v.batch_cams + (size_t)(bframe / v.batch_spv) * EGR_BATCH_CAM_FLOATS;
         }
         const bool last_frame = !BATCH || bframe == v.batch_last_frame; // (stats / random_seeds are "last launch wins" stores)
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 9 // diagnostic build: stamps of the WHOLE chain of a task (start, end of every step) in its first pixels
-        unsigned long long chain_t[EGR_NSTEPS + 1] = {__builtin_amdgcn_s_memrealtime(), 0ull, 0ull, 0ull};
-        uint32_t chain_leaves = 0u;
-#endif
-#ifdef EGR_TRAVERSAL_STATS
-        const unsigned long long tchain0 = __builtin_amdgcn_s_memtime();
-        unsigned long long tepi = 0ull;
-#endif
+        EGR_TIMES(unsigned long long chain_t[EGR_NSTEPS + 1] = {}; uint32_t chain_leaves = 0u;) EGR_TIMES_IS(9, chain_t[0] = __builtin_amdgcn_s_memrealtime();) // stamps of the WHOLE chain of a task (start, end of every step) for its first pixels
+        EGR_STATS(const unsigned long long tchain0 = __builtin_amdgcn_s_memtime(); unsigned long long tepi = 0ull;)
         uint32_t bwd_cost = 0u; // (grad launches) what this tile's backward will cost, roughly in microseconds: 8 per primary hit row, 8 per 64 bounce hits + 2 per bounce hit row
         for (int step = 0; step <= num_bounces; step++) {
             do { // (a `continue` in the step body ends the step)
@@ -48,31 +42,17 @@
             } while (false);
             // R4 / R5 of this step for the tile's rays
             const TaskGeom etg = task_geom(v, tb, lane);
-#ifdef EGR_TRAVERSAL_STATS
-            const unsigned long long tepi0 = __builtin_amdgcn_s_memtime();
-#endif
+            EGR_STATS(const unsigned long long tepi0 = __builtin_amdgcn_s_memtime();)
             if (etg.inside) step_epilogue_lane(v, step, GRADS, num_bounces, etg, state_of(v, tq, lane), last_frame);
-#ifdef EGR_TRAVERSAL_STATS
-            tepi += __builtin_amdgcn_s_memtime() - tepi0;
-#endif
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 9
-            chain_t[step + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
+            EGR_STATS(tepi += __builtin_amdgcn_s_memtime() - tepi0;)
+            EGR_TIMES_IS(9, chain_t[step + 1] = __builtin_amdgcn_s_memrealtime();)
         }
         if (GRADS && lane == 0) v.task_cost[tq] = bwd_cost;
-#ifdef EGR_TRAVERSAL_STATS
-        if (lane == 0) { // CW_DBG2 + 8: step epilogues, + 12: whole chains (task pull to task end)
-            atomicAdd(reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 8), tepi);
-            atomicAdd(reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 12), __builtin_amdgcn_s_memtime() - tchain0);
-        }
-#endif
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 9
-        {
+        EGR_STATS(if (lane == 0) atomicAdd(diag64(v.control, DG_EPILOGUE_CYC), tepi), atomicAdd(diag64(v.control, DG_CHAIN_CYC), __builtin_amdgcn_s_memtime() - tchain0);)
+        EGR_TIMES_IS(9,
             const TaskGeom ctg = task_geom(v, tb, lane);
-            if (lane <= EGR_NSTEPS && ctg.inside) v.stats.num_traversed_per_pixel[ctg.pixel_id] = (int32_t)(chain_t[lane] & 0x7FFFFFFFull);
-            if (lane == 4 && ctg.inside) v.stats.num_traversed_per_pixel[ctg.pixel_id] = (int32_t)chain_leaves;
-        }
-#endif
+            if (lane <= EGR_NSTEPS && ctg.inside) v.stats.num_traversed_per_pixel[ctg.pixel_id] = EGR_STAMP31(chain_t[lane]);
+            if (lane == 4 && ctg.inside) v.stats.num_traversed_per_pixel[ctg.pixel_id] = (int32_t)chain_leaves;)
     }
     wave_sync();
     if (lane < EGR_NSTEPS) {

@@ -33,14 +33,8 @@
         }
         if (__ballot(active) == 0ull) continue;
 
-#ifdef EGR_TRAVERSAL_STATS
-        const unsigned long long tm0 = __builtin_amdgcn_s_memtime();
-#endif
-#ifdef EGR_TASK_TIMES
-        const unsigned long long tt0 = __builtin_amdgcn_s_memrealtime();
-        uint32_t tt_batches = 0u, tt_evals = 0u, tt_offers = 0u, tt_tall = 0u;
-        unsigned long long tt_wait = 0ull;
-#endif
+        EGR_STATS(const unsigned long long tm0 = __builtin_amdgcn_s_memtime();)
+        EGR_TIMES(const unsigned long long tt0 = __builtin_amdgcn_s_memrealtime(); uint32_t tt_batches = 0u, tt_evals = 0u, tt_offers = 0u, tt_tall = 0u; unsigned long long tt_wait = 0ull;)
         // ---- R2: traversal + candidate evaluation (shaders.cu:9-75) -------------------------------------
         // Primary tiles: ONE frustum per tile - the walk collects the leaves the tile's pyramid meets, then every lane tests its own ray against
         // them, one leaf after the other (records through the scalar cache). Bounce tiles: PAIRS - the walk queues (ray, leaf) pairs in LDS,
@@ -73,11 +67,7 @@
         double full_Td = 1.0;
         float full_T = 1.0f;
         bool overflow = false;
-#ifdef EGR_TRAVERSAL_STATS
-        uint32_t st_visits = 0, st_leafhits = 0, st_inner = 0, st_outer = 0;
-        unsigned long long st_eval_cycles = 0ull, st_batch_cycles = 0ull;
-        uint32_t st_batches = 0u;
-#endif
+        EGR_STATS(uint32_t st_visits = 0, st_leafhits = 0, st_inner = 0, st_outer = 0, st_batches = 0u; unsigned long long st_eval_cycles = 0ull, st_batch_cycles = 0ull;)
         int seg = 0;                 // which of the three walked segments is active (see the walk below)
         float seg_lo, seg_hi;
         auto evaluate = [&](uint32_t prim, const float4 &w0, const float4 &w1, const float4 &w2, auto a2src, const f3 &lo_pre) {
@@ -227,9 +217,7 @@
                     const bool do_eval = nl >= (uint32_t)EGR_WAVE || (top == 0u && nl > 0u);
                     if (!do_eval && top == 0u) break;
                     if (do_eval) {
-#ifdef EGR_TRAVERSAL_STATS
-                        const unsigned long long te0 = __builtin_amdgcn_s_memtime();
-#endif
+                        EGR_STATS(const unsigned long long te0 = __builtin_amdgcn_s_memtime();)
                         // First the leaves themselves, ONE LANE PER LEAF: a gaussian's box is a loose bound of a rotated ellipsoid (up to 1.7 radii
                         // along a pyramid side's normal, plus the cells of the quantisation), and every leaf that reaches the loop below costs the
                         // whole candidate test in all 64 lanes. The leaf's bounding SPHERE (bvh.hip: centre, squared radius) is tested against the
@@ -237,10 +225,7 @@
                         // compacted in place. Conservative: an accepted candidate's response point lies inside the ellipsoid, hence inside the
                         // sphere, and on one of the tile's rays, hence inside the pyramid.
                         if (narrow_u) {
-#ifdef EGR_TRAVERSAL_STATS
-                            const unsigned long long tf0 = __builtin_amdgcn_s_memtime();
-                            st_batches += nl;
-#endif
+                            EGR_STATS(const unsigned long long tf0 = __builtin_amdgcn_s_memtime(); st_batches += nl;)
                             uint32_t nk = 0u;
                             for (uint32_t base = 0u; base < nl; base += (uint32_t)EGR_WAVE) {
                                 const uint32_t nb = min(nl - base, (uint32_t)EGR_WAVE);
@@ -260,13 +245,9 @@
                                 wave_sync();
                             }
                             nl = nk;
-#ifdef EGR_TRAVERSAL_STATS
-                            st_batch_cycles += __builtin_amdgcn_s_memtime() - tf0;
-#endif
+                            EGR_STATS(st_batch_cycles += __builtin_amdgcn_s_memtime() - tf0;)
                         }
-#if defined(EGR_TASK_TIMES) && EGR_TASK_TIMES == 9
-                        chain_leaves += nl; // (diagnostic: the leaves this tile's primary step evaluates - is it a predictor of the chain's duration?)
-#endif
+                        EGR_TIMES_IS(9, chain_leaves += nl;) // (the leaves this tile's primary step evaluates - is it a predictor of the chain's duration?)
                         if (nl != 0u) {
                         // ONE instance of the candidate test for every leaf (not one per unrolled slot): bit-identical gaussians then get
                         // bit-identical distances wherever they sit - an ulp between two copies of a duplicated object decides what the
@@ -300,9 +281,7 @@
                             pn_next = lbuf[min(i + 2u, nl - 1u)];
                             n0 = load_f4_uniform(v.inst_w, 4 * pn), n1 = load_f4_uniform(v.inst_w, 4 * pn + 1), n2 = load_f4_uniform(v.inst_w, 4 * pn + 2), n3 = load_f4_uniform(v.inst_w, 4 * pn + 3);
                             nlo = llo[min(i + 1u, nl - 1u)];
-#ifdef EGR_TRAVERSAL_STATS
-                            st_leafhits += ray_ok ? 1u : 0u, st_outer += (lane == 0);
-#endif
+                            EGR_STATS(st_leafhits += ray_ok ? 1u : 0u, st_outer += (lane == 0);)
                             if (ray_ok) evaluate(p, w0, w1, w2, a2, lo_pre);
 #if defined(__HIP_DEVICE_COMPILE__)
                             // (the NEXT record is in flight during the test above. Its unused dwords - the W rows' fourth components, half of the live
@@ -314,9 +293,7 @@
                         }
                         nl = 0u;
                         wave_sync(); // the buffer is refilled below
-#ifdef EGR_TRAVERSAL_STATS
-                        st_eval_cycles += __builtin_amdgcn_s_memtime() - te0;
-#endif
+                        EGR_STATS(st_eval_cycles += __builtin_amdgcn_s_memtime() - te0;)
                         if (top == 0u) break;
                     }
                     // (EGR_FPOP x 8 nodes per iteration: lane group g takes the g-th, (g + 8)-th ... node from the top; their lines are requested together)
@@ -330,14 +307,10 @@
                         if (top > (uint32_t)EGR_PSTK && e >= (uint32_t)EGR_PSTK) node = __hip_atomic_load(ugstk + (e - EGR_PSTK), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (rare)
                         sl_[u] = wnodes[(size_t)node * EGR_WIDTH + m]; // (a group beyond the popped nodes re-reads the bottom node and is turned into an empty slot)
                         if (!(gi < npop)) sl_[u].w = EGR_EMPTY_SLOT;
-#ifdef EGR_TRAVERSAL_STATS
-                        st_visits += (m == 0u && gi < npop) ? 1u : 0u;
-#endif
+                        EGR_STATS(st_visits += (m == 0u && gi < npop) ? 1u : 0u;)
                     }
                     top -= npop;
-#ifdef EGR_TRAVERSAL_STATS
-                    st_inner += (lane == 0);
-#endif
+                    EGR_STATS(st_inner += (lane == 0);)
                     wave_sync(); // the stack reads above come before the pushes below
 #pragma unroll
                     for (int u = 0; u < EGR_FPOP; u++) {
@@ -377,22 +350,14 @@
             if (!sentinels && seg == 0) pair_walk<false, true, CUBE, TEAM>(v, fc, wsh, wsh, team, wv, scratch0, gstk, step, seg, seg_lo, seg_hi, near_plane, top, g_over, wst);
             else if (sentinels) pair_walk<true, false, CUBE, TEAM>(v, fc, wsh, wsh, team, wv, scratch0, gstk, step, seg, seg_lo, seg_hi, near_plane, top, g_over, wst);
             else pair_walk<false, false, CUBE, TEAM>(v, fc, wsh, wsh, team, wv, scratch0, gstk, step, seg, seg_lo, seg_hi, near_plane, top, g_over, wst);
-#ifdef EGR_TASK_TIMES
-            tt_batches += wst.inner, tt_evals += wst.outer, tt_offers += wst.offers, tt_tall += wst.tall;
-#endif
-#ifdef EGR_TRAVERSAL_STATS
-            st_visits += wst.visits, st_leafhits += wst.leafhits, st_inner += wst.inner, st_outer += wst.outer;
-            if (lane == 0 && (wst.offers | wst.tall)) atomicAdd(v.control + CW_DBG3 + 12, wst.offers), atomicAdd(v.control + CW_DBG3 + 15, wst.tall);
-#endif
+            EGR_TIMES(tt_batches += wst.inner, tt_evals += wst.outer, tt_offers += wst.offers, tt_tall += wst.tall;)
+            EGR_STATS(st_visits += wst.visits, st_leafhits += wst.leafhits, st_inner += wst.inner, st_outer += wst.outer;)
+            EGR_STATS(if (lane == 0 && (wst.offers | wst.tall)) atomicAdd(v.control + DG_TEAM_OFFERS, wst.offers), atomicAdd(v.control + DG_TEAM_TALL, wst.tall);)
             if (TEAM > 1 && v.team_help) {
                 // pairs of this walk that team mates took: until they are worked off this wave is a helper itself (theirs are the likeliest offers)
-#ifdef EGR_TASK_TIMES
-                const unsigned long long tw0 = __builtin_amdgcn_s_memrealtime();
-#endif
+                EGR_TIMES(const unsigned long long tw0 = __builtin_amdgcn_s_memrealtime();)
                 team_help_while<CUBE, TEAM>(v, fc, wsh_all, team, wv, blockIdx.x * (uint32_t)TEAM, g_over, [&]() { return uniform_u32(lds_peek(&team.busy[wv])) != 0u; });
-#ifdef EGR_TASK_TIMES
-                tt_wait += __builtin_amdgcn_s_memrealtime() - tw0;
-#endif
+                EGR_TIMES(tt_wait += __builtin_amdgcn_s_memrealtime() - tw0;)
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); // the helpers' list entries
             }
             if (__ballot(g_over) != 0ull) overflow = true;
@@ -416,7 +381,7 @@
             for (uint32_t k = nbase; k < cnt; k++) full_Td *= 1.0 - (double)v.ext_vals[(size_t)ext * EGR_EXT_BLOCK + (k - v.cand_cap)].x;
         }
         full_T = (float)full_Td;
-#ifdef EGR_DEBUG_PIXEL // diagnostic build: the candidate list of one pixel (step 0)
+#ifdef EGR_DEBUG_PIXEL // diagnostic build (egr_diag.hpp): the candidate list of one pixel (step 0)
         if (active && step == 0 && tg.pixel_id == (uint32_t)EGR_DEBUG_PIXEL) {
             printf("[pixel %u] cnt %u traversed %u full_T %.9g\n", tg.pixel_id, cnt, traversed, (double)full_T);
             for (uint32_t k = 0; k < cnt && k < v.cand_cap; k++) printf("   k %u t %.9g (%08x) alpha %.9g pos %u gid %u\n", k, (double)keys[EGR_KEY_AT(lane, k)], f2u(keys[EGR_KEY_AT(lane, k)]), (double)vals[EGR_VAL_AT(lane, k)].x, f2u(vals[EGR_VAL_AT(lane, k)].y), v.gid_of_pos[f2u(vals[EGR_VAL_AT(lane, k)].y)]);
@@ -432,23 +397,14 @@
             }
         }
 #endif
-#ifdef EGR_TRAVERSAL_STATS
-        const unsigned long long tm1 = __builtin_amdgcn_s_memtime();
-        if (step == 0) { // histogram of the longest candidate list of a primary tile: <= 16, 24, 32, 40, 48, 64, more
-            const uint32_t cm = wave_max_u32(active ? cnt : 0u);
-            const int bin = cm <= 16u ? 0 : cm <= 24u ? 1 : cm <= 32u ? 2 : cm <= 40u ? 3 : cm <= 48u ? 4 : cm <= 64u ? 5 : 6;
-            if (lane == 0) atomicAdd(v.control + CW_DBG2 + 50 + bin, 1u);
-        }
-        {
-            uint32_t a = wave_sum_u32(st_visits), b = wave_sum_u32(st_leafhits), c2 = wave_sum_u32(st_inner), d = wave_sum_u32(st_outer);
-            if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 8 + 4 * (step > 0) + 2), st_eval_cycles);
-            if (lane == 0 && st_batches) atomicAdd(reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 36), st_batch_cycles), atomicAdd(reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 38), (unsigned long long)st_batches);
-            if (lane == 0) add64(v.control, CW_DBG + 8 * (step > 0), a), add64(v.control, CW_DBG + 8 * (step > 0) + 2, b), add64(v.control, CW_DBG + 8 * (step > 0) + 4, c2), add64(v.control, CW_DBG + 8 * (step > 0) + 6, d);
-        }
-#endif
-#ifdef EGR_TASK_TIMES
-        const unsigned long long tt_mid = __builtin_amdgcn_s_memrealtime(); // end of the walk / start of the depth selection
-#endif
+        EGR_STATS(const unsigned long long tm1 = __builtin_amdgcn_s_memtime(); {
+            const uint32_t cm = wave_max_u32(active ? cnt : 0u); // (primary tiles: the histogram of their longest candidate list)
+            const unsigned long long a = wave_sum_u32(st_visits), b = wave_sum_u32(st_leafhits), c2 = wave_sum_u32(st_inner), d = wave_sum_u32(st_outer);
+            if (lane == 0 && step == 0) atomicAdd(v.control + DG_LIST_HIST + (cm <= 16u ? 0 : cm <= 24u ? 1 : cm <= 32u ? 2 : cm <= 40u ? 3 : cm <= 48u ? 4 : cm <= 64u ? 5 : 6), 1u);
+            if (lane == 0 && st_batches) atomicAdd(diag64(v.control, DG_FILTER_CYC), st_batch_cycles), atomicAdd(diag64(v.control, DG_FILTER_LEAVES), (unsigned long long)st_batches);
+            if (lane == 0) atomicAdd(diag64(v.control, DG_LEAF_EVAL_CYC, step > 0), st_eval_cycles), atomicAdd(diag64(v.control, DG_VISITS, step > 0), a), atomicAdd(diag64(v.control, DG_LEAF_HITS, step > 0), b), atomicAdd(diag64(v.control, DG_WALK_ITERS, step > 0), c2), atomicAdd(diag64(v.control, DG_EVAL_ROUNDS, step > 0), d);
+        })
+        EGR_TIMES(const unsigned long long tt_mid = __builtin_amdgcn_s_memrealtime();) // end of the walk / start of the depth selection
         // ---- R3: depth-ordered compositing (forward_pass.cu:48-137) --------------------------------------
         f3 c_rgb = mk3(0, 0, 0), c_n = mk3(0, 0, 0), c_f0 = mk3(0, 0, 0);
         float c_rough = 0.0f, c_depth = 0.0f, T = 1.0f;
@@ -462,14 +418,9 @@
             // Depth order in batches of 8 (= one arena block): ONE scan over the lane's key column keeps the 8 strict
             // successors of (t_prev, k_prev) in (t, k) lexicographic order in registers (sorted insertion, static indices),
             // then the batch is composited front to back. The old "one scan per composited hit" cost Kc+1 passes.
-#ifdef EGR_TRAVERSAL_STATS
-            unsigned long long tc_scan = 0ull, tc_alloc = 0ull, tc_av = 0ull, tc_p1 = 0ull, tc_app = 0ull;
-#define EGR_TC(x) x
-#else
-#define EGR_TC(x)
-#endif
+            EGR_STATS(unsigned long long tc_scan = 0ull, tc_alloc = 0ull, tc_av = 0ull, tc_p1 = 0ull, tc_app = 0ull;)
             for (uint32_t it = 0;; it += EGR_HIT_BLOCK_ROWS) {
-                EGR_TC(const unsigned long long tcs0 = __builtin_amdgcn_s_memtime();)
+                EGR_STATS(const unsigned long long tcs0 = __builtin_amdgcn_s_memtime();)
                 float kt[8];
                 uint32_t ki[8];
 #pragma unroll
@@ -530,7 +481,7 @@
                     for (; k < cnt; k++) consider(v.ext_keys[(size_t)ext * EGR_EXT_BLOCK + (k - v.cand_cap)], k); // the extension block (rare)
                     if (ki[0] == 0xFFFFFFFFu || !(kt[0] < far_plane)) running = false; // :81, :91-93
                 }
-                EGR_TC(const unsigned long long tcs1 = __builtin_amdgcn_s_memtime(); tc_scan += tcs1 - tcs0;)
+                EGR_STATS(const unsigned long long tcs1 = __builtin_amdgcn_s_memtime(); tc_scan += tcs1 - tcs0;)
                 if (__ballot(running) == 0ull) break;
                 if (GRADS && recording) { // one arena block per batch per wave
                     // (blocks are taken from the arena's bump counter EGR_ARENA_CHUNK at a time and handed out from the wave's own run: every batch used to wait
@@ -551,7 +502,7 @@
                 }
                 // the batch's eight (alpha, record) pairs are fetched together (a fetch for a hit the ray never reaches - it may stop at
                 // the transmittance threshold - reads valid memory and is dropped): one dependent round trip instead of eight
-                EGR_TC(const unsigned long long tcs2 = __builtin_amdgcn_s_memtime(); tc_alloc += tcs2 - tcs1;)
+                EGR_STATS(const unsigned long long tcs2 = __builtin_amdgcn_s_memtime(); tc_alloc += tcs2 - tcs1;)
                 float2 av_[8];
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
@@ -569,10 +520,7 @@
                 asm volatile("" ::"v"(av_[0].x), "v"(av_[0].y), "v"(av_[1].x), "v"(av_[1].y), "v"(av_[2].x), "v"(av_[2].y), "v"(av_[3].x), "v"(av_[3].y));
                 asm volatile("" ::"v"(av_[4].x), "v"(av_[4].y), "v"(av_[5].x), "v"(av_[5].y), "v"(av_[6].x), "v"(av_[6].y), "v"(av_[7].x), "v"(av_[7].y));
 #endif
-#ifdef EGR_TRAVERSAL_STATS
-                const unsigned long long tcs3 = __builtin_amdgcn_s_memtime();
-                tc_av += tcs3 - tcs2;
-#endif
+                EGR_STATS(const unsigned long long tcs3 = __builtin_amdgcn_s_memtime(); tc_av += tcs3 - tcs2;)
                 float wj[8];
                 uint32_t pj[8], runm = 0u;
 #pragma unroll
@@ -597,7 +545,7 @@
                         if (T < transmittance_threshold || nhits >= EGR_MAX_COMPOSITED_PER_RAY) running = false; // :131-134, :55
                     }
                 }
-                EGR_TC(const unsigned long long tcs4 = __builtin_amdgcn_s_memtime(); tc_p1 += tcs4 - tcs3;)
+                EGR_STATS(const unsigned long long tcs4 = __builtin_amdgcn_s_memtime(); tc_p1 += tcs4 - tcs3;)
 #pragma unroll
                 for (int g4 = 0; g4 < 8; g4 += 4) {
                     float4 A0[4], A1[4];
@@ -623,18 +571,12 @@
                         }
                     }
                 }
-#ifdef EGR_TRAVERSAL_STATS
-                asm volatile("" ::"v"(c_rough));
-                tc_app += __builtin_amdgcn_s_memtime() - tcs4;
-#endif
+                EGR_STATS(asm volatile("" ::"v"(c_rough)); tc_app += __builtin_amdgcn_s_memtime() - tcs4;)
             }
-#ifdef EGR_TRAVERSAL_STATS
-            if (lane == 0 && step == 0) {
-                unsigned long long *d = reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 40);
+            EGR_STATS(if (lane == 0 && step == 0) {
+                unsigned long long *d = diag64(v.control, DG_COMP_SCAN_CYC);
                 atomicAdd(d, tc_scan), atomicAdd(d + 1, tc_alloc), atomicAdd(d + 2, tc_av), atomicAdd(d + 3, tc_p1), atomicAdd(d + 4, tc_app);
-            }
-#endif
-#undef EGR_TC
+            })
             if (GRADS) {
                 // arena exhausted: forward results stay exact, backward skips this task (status flag is raised)
                 if (lane == 0) v.task_last_block[chain_head] = recording ? last_block : 0xFFFFFFFFu;
@@ -643,15 +585,7 @@
         }
         if (overflow && active) atomicOr(v.control + CW_STATUS, EGR_STATUS_CANDIDATE_OVERFLOW);
 
-#ifdef EGR_TRAVERSAL_STATS
-        {
-            const unsigned long long tm2 = __builtin_amdgcn_s_memtime();
-            if (lane == 0) {
-                atomicAdd(reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 4 * (step > 0)), tm1 - tm0);
-                atomicAdd(reinterpret_cast<unsigned long long *>(v.control + CW_DBG2 + 4 * (step > 0) + 2), tm2 - tm1);
-            }
-        }
-#endif
+        EGR_STATS(if (lane == 0) atomicAdd(diag64(v.control, DG_TRAVERSAL_CYC, step > 0), tm1 - tm0), atomicAdd(diag64(v.control, DG_COMPOSITE_CYC, step > 0), __builtin_amdgcn_s_memtime() - tm1);)
         // ---- raw step results; R4/R5 (tail renormalisation, bounce sampling) follow in step_epilogue_lane (egr_epilogue.hpp),
         // which is compiled without fma contraction (see the note there).
         if (active) {
@@ -667,17 +601,13 @@
                 else v.stats.num_traversed_per_pixel[tg.pixel_id] += (int32_t)traversed; // forward_pass.cu:46
             }
         }
-#ifdef EGR_TASK_TIMES // diagnostic build: the tile's first pixel carries the task's start / end time of one step (which must be the last)
-        if (step == EGR_TASK_TIMES && lane == 0 && tg.inside) {
-            v.stats.num_traversed_per_pixel[tg.pixel_id] = (int32_t)(tt0 & 0x7FFFFFFFull); // start / end, 10 ns ticks
-            v.stats.num_accumulated_per_pixel[tg.pixel_id] = (int32_t)(__builtin_amdgcn_s_memrealtime() & 0x7FFFFFFFull);
-        }
-        if (step == EGR_TASK_TIMES && lane == 1 && tg.inside) v.stats.num_traversed_per_pixel[tg.pixel_id] = (int32_t)(tt_mid & 0x7FFFFFFFull); // (second pixel: walk / selection boundary)
-        if (step == EGR_TASK_TIMES && tg.inside) { // pixels 2 .. 4: the owner's walk batches / evaluation batches, offers made / batches that left a tall stack, ticks waited for helpers / longest candidate list
+        EGR_TIMES(if (step == EGR_TASK_TIMES && tg.inside) { // the tile's first pixel carries the task's start / end time of one step (which must be the last), 10 ns ticks; the second the walk / selection boundary;
+            // pixels 2 .. 4: the owner's walk batches / evaluation batches, offers made / batches that left a tall stack, ticks waited for helpers / longest candidate list
+            if (lane == 0) v.stats.num_traversed_per_pixel[tg.pixel_id] = EGR_STAMP31(tt0), v.stats.num_accumulated_per_pixel[tg.pixel_id] = EGR_STAMP31(__builtin_amdgcn_s_memrealtime());
+            if (lane == 1) v.stats.num_traversed_per_pixel[tg.pixel_id] = EGR_STAMP31(tt_mid);
             const uint32_t cmax = wave_max_u32(active ? cnt : 0u);
             tt_batches = (uint32_t)__shfl((int)tt_batches, 0), tt_evals = (uint32_t)__shfl((int)tt_evals, 0), tt_offers = (uint32_t)__shfl((int)tt_offers, 0), tt_tall = (uint32_t)__shfl((int)tt_tall, 0);
             if (lane == 2) v.stats.num_traversed_per_pixel[tg.pixel_id] = (int32_t)tt_batches, v.stats.num_accumulated_per_pixel[tg.pixel_id] = (int32_t)tt_evals;
             if (lane == 3) v.stats.num_traversed_per_pixel[tg.pixel_id] = (int32_t)tt_offers, v.stats.num_accumulated_per_pixel[tg.pixel_id] = (int32_t)tt_tall;
             if (lane == 4) v.stats.num_traversed_per_pixel[tg.pixel_id] = (int32_t)tt_wait, v.stats.num_accumulated_per_pixel[tg.pixel_id] = (int32_t)cmax;
-        }
-#endif
+        })

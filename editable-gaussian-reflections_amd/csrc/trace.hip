@@ -35,6 +35,7 @@
 #include <vector>
 
 #define EGR_CONTRACT_AFTER_EPILOGUE
+#include "egr_diag.hpp"
 #include "egr_epilogue.hpp" // (includes egr_state.hpp) the step epilogue, for the fused per-tile chain
 
 #ifndef EGR_GPOP
@@ -310,10 +311,7 @@ template <int TEAM> struct TeamShared {
     uint32_t ctx[TEAM][5];     // the walk wave w's offers belong to: step | seg << 8, seg_lo, seg_hi, near plane, the wave whose rays these are
     uint32_t box[TEAM][EGR_BOX];
 };
-#if defined(EGR_TRAVERSAL_STATS) || defined(EGR_TASK_TIMES)
-#define EGR_WALK_STATS 1
-#endif
-struct WalkStats { // diagnostic builds (EGR_TRAVERSAL_STATS, EGR_TASK_TIMES)
+struct WalkStats { // diagnostic builds (egr_diag.hpp: EGR_WALK)
     uint32_t visits = 0, leafhits = 0, inner = 0, outer = 0;
     uint32_t offers = 0, tall = 0; // team: offers made, walk batches that left the stack at EGR_DONATE_MIN pairs or more
 };
@@ -384,10 +382,7 @@ EGR_DI void pair_eval_append(const DeviceView &v, const FwdConst &fc, WalkShared
         const float4 q0 = rays.rayp[er][0], q1 = rays.rayp[er][1];
         res = test_candidate<CUBE, SEG0>(fc, step, seg, near_plane, mk3(q0.x, q0.y, q0.z), mk3(q0.w, q1.x, q1.y), pidx, w0, w1, w2, w3, t, alpha);
     }
-#ifdef EGR_WALK_STATS
-    st.leafhits += have ? 1u : 0u;
-    st.outer += (lane == 0);
-#endif
+    EGR_WALK(st.leafhits += have ? 1u : 0u; st.outer += (lane == 0);)
     if (res == 1 || res == 2) atomicAdd(&rays.gtrav[er], 1u);
     uint32_t at = 0u;
     if (res == 2) at = atomicAdd(&rays.gcnt[er], 1u);
@@ -506,10 +501,7 @@ EGR_DI void pair_walk(const DeviceView &v, const FwdConst &fc, WalkShared &mine,
                 if (!(grp + 8u * (uint32_t)u < npop)) sl_[u].w = EGR_EMPTY_SLOT;
             }
             top -= npop;
-#ifdef EGR_WALK_STATS
-            st.visits += (m == 0u) ? min(npop > grp ? (npop - grp + 7u) / 8u : 0u, (uint32_t)EGR_GPOP) : 0u;
-            st.inner += (lane == 0);
-#endif
+            EGR_WALK(st.visits += (m == 0u) ? min(npop > grp ? (npop - grp + 7u) / 8u : 0u, (uint32_t)EGR_GPOP) : 0u; st.inner += (lane == 0);)
         }
         wave_sync(); // the reads of both buffers above come before the pushes below
         // ---------------- work off: evaluation batch
@@ -543,9 +535,7 @@ EGR_DI void pair_walk(const DeviceView &v, const FwdConst &fc, WalkShared &mine,
             }
         }
         wave_sync();
-#ifdef EGR_WALK_STATS
-        st.tall += (lane == 0 && top >= (uint32_t)EGR_DONATE_MIN) ? 1u : 0u;
-#endif
+        EGR_WALK(st.tall += (lane == 0 && top >= (uint32_t)EGR_DONATE_MIN) ? 1u : 0u;)
         if constexpr (TEAM > 1) {
             // a team mate looks for work and this stack is long: its lower half goes on offer
             if (uniform_u32(hungry_seen) != 0u && top >= (uint32_t)EGR_DONATE_MIN && top <= (uint32_t)EGR_PSTK && uniform_u32(lds_peek(&team.box_count[self])) == 0u) {
@@ -566,9 +556,7 @@ EGR_DI void pair_walk(const DeviceView &v, const FwdConst &fc, WalkShared &mine,
                 top -= give;
                 wave_sync();
                 if (lane == 0) lds_poke(&team.box_count[self], give | (lds_peek(&team.ctx[self][4]) << 16));
-#ifdef EGR_WALK_STATS
-                st.offers += (lane == 0);
-#endif
+                EGR_WALK(st.offers += (lane == 0);)
             }
         }
     }
@@ -609,9 +597,7 @@ template <bool CUBE, int TEAM> EGR_DI bool team_help(const DeviceView &v, const 
         WalkStats st;
         pair_walk<true, false, CUBE, TEAM>(v, fc, mine, wsh[owner], team, wv, scratch0, gstk, step, seg, u2f(c1), u2f(c2), u2f(c3), k, g_over, st);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); // the list entries written for the owner
-#ifdef EGR_WALK_STATS
-        if (lane == 0) atomicAdd(v.control + CW_DBG3 + 13, 1u), atomicAdd(v.control + CW_DBG3 + 14, st.inner);
-#endif
+        EGR_WALK(if (lane == 0) atomicAdd(v.control + DG_TEAM_HELPED, 1u), atomicAdd(v.control + DG_TEAM_HELP_ITERS, st.inner);)
         if (lane == 0) atomicSub(&team.busy[owner], 1u), atomicAdd(&team.hungry, 1u);
         return true;
     }
@@ -631,11 +617,11 @@ template <bool CUBE, int TEAM, class F> EGR_DI void team_help_while(const Device
 // per-launch prologue: Raytracer::raytrace host part (raytracer.cpp:82-86), on the device, no host sync
 // ---------------------------------------------------------------------------------------------------------
 // The control-word resets of the one-block (one-wave) prologue kernels, t = threadIdx.x.
-// Per launch: the counters [0, CW_RESET_END), the diagnostic words and the lines of the two bump counters [CW_DBG, CW_COUNT), then the min / max seeds of CW_DBG3.
+// Per launch: the counters [0, CW_RESET_END), the diagnostic words and the lines of the two bump counters [DG_BEGIN, CW_COUNT), then the min / max seeds of DG_STEP_EXIT.
 EGR_DI void reset_launch_words(const DeviceView &v, int t) {
     if (t < CW_RESET_END) v.control[t] = 0;
-    for (int w = CW_DBG + t; w < CW_COUNT; w += (int)blockDim.x) v.control[w] = 0;
-    if (t < 12) v.control[CW_DBG3 + t] = ((t & 3) < 2) ? 0xFFFFFFFFu : 0u;
+    for (int w = DG_BEGIN + t; w < CW_COUNT; w += (int)blockDim.x) v.control[w] = 0;
+    if (t < 12) v.control[DG_STEP_EXIT + t] = ((t & 3) < 2) ? 0xFFFFFFFFu : 0u;
 }
 // Per chunk of tasks (a single launch is one chunk): fresh task queues of both chains, extension blocks and hit-arena blocks.
 EGR_DI void reset_chunk_words(const DeviceView &v, int t) {

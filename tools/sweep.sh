@@ -1,12 +1,11 @@
 #!/bin/bash
-# Usage (GPU box): tools/sweep.sh <tag> "ENV1=a ENV2=b" "ENV1=c" ...   - rebuild trace.hip with each build-time setting and bench it
+# Usage (GPU box): tools/sweep.sh <tag> "ENV1=a ENV2=b" "ENV1=c" ...   - build the variant of each build-time setting and bench it
 RUNS=${EGR_RUNS_DIR:-runs}  # results go to $RUNS/<tag> (runs/ is kept out of git)
 TAG=$1; shift
 mkdir -p $RUNS/$TAG
 for CFG in "$@"; do
   NAME=$(echo "$CFG" | tr ' =' '__')
-  touch editable-gaussian-reflections_amd/csrc/trace.hip editable-gaussian-reflections_amd/csrc/bvh.hip
-  env $CFG python -c "import importlib; importlib.import_module('editable-gaussian-reflections_amd.build').build_all()" > $RUNS/$TAG/build_$NAME.log 2>&1 || { echo "$CFG: BUILD FAILED"; tail -5 $RUNS/$TAG/build_$NAME.log; continue; }
+  env $CFG tools/build_variant.sh > $RUNS/$TAG/build_$NAME.log 2>&1 || { echo "$CFG: BUILD FAILED"; tail -5 $RUNS/$TAG/build_$NAME.log; continue; }
   env $CFG python bench.py --full --no-cpu-baseline --steps 60 --warmup 40 ${SWEEP_ARGS:---no-second-variant} > $RUNS/$TAG/bench_$NAME.json 2> $RUNS/$TAG/bench_$NAME.err
   python - <<PY
 import json

@@ -5,8 +5,7 @@ TAG=$1; shift
 mkdir -p $RUNS/$TAG
 for CFG in "$@"; do
   NAME=$(echo "$CFG" | tr ' =' '__')
-  touch editable-gaussian-reflections_amd/csrc/trace.hip
-  env $CFG python -c "import importlib; importlib.import_module('editable-gaussian-reflections_amd.build').build_all()" > $RUNS/$TAG/build_$NAME.log 2>&1 || { echo "$CFG: BUILD FAILED"; tail -5 $RUNS/$TAG/build_$NAME.log; continue; }
+  env $CFG tools/build_variant.sh > $RUNS/$TAG/build_$NAME.log 2>&1 || { echo "$CFG: BUILD FAILED"; tail -5 $RUNS/$TAG/build_$NAME.log; continue; }
   env $CFG python bench.py --full --no-cpu-baseline --steps 60 --warmup 40 ${SWEEP_ARGS} > $RUNS/$TAG/bench_$NAME.json 2> $RUNS/$TAG/bench_$NAME.err
   python - <<PY
 import json

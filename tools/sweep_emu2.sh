@@ -3,8 +3,7 @@
 RUNS=${EGR_RUNS_DIR:-runs}  # results go to $RUNS/<tag> (runs/ is kept out of git)
 TAG=$1; W=$2; B=$3; shift 4
 mkdir -p $RUNS/$TAG
-touch editable-gaussian-reflections_amd/csrc/trace.hip
-env $B python -c "import importlib; importlib.import_module('editable-gaussian-reflections_amd.build').build_all()" > $RUNS/$TAG/build.log 2>&1 || { echo "BUILD FAILED"; tail -5 $RUNS/$TAG/build.log; exit 1; }
+env $B tools/build_variant.sh > $RUNS/$TAG/build.log 2>&1 || { echo "BUILD FAILED"; tail -5 $RUNS/$TAG/build.log; exit 1; }
 for R in "$@"; do for V in init trained; do
     env $B $R python bench.py --full --no-cpu-baseline --no-second-variant --steps 60 --warmup 40 --primary-steps 0 --emulate-world $W --variant $V 2>/dev/null | tail -1 > $RUNS/$TAG/emu.json
     python - <<PY

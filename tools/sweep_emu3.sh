@@ -4,8 +4,7 @@ RUNS=${EGR_RUNS_DIR:-runs}  # results go to $RUNS/<tag> (runs/ is kept out of gi
 TAG=$1; W=$2; shift 2
 mkdir -p $RUNS/$TAG
 for B in "$@"; do
-  touch editable-gaussian-reflections_amd/csrc/trace.hip
-  env $B python -c "import importlib; importlib.import_module('editable-gaussian-reflections_amd.build').build_all()" > $RUNS/$TAG/build.log 2>&1 || { echo "$B: BUILD FAILED"; tail -5 $RUNS/$TAG/build.log; continue; }
+  env $B tools/build_variant.sh > $RUNS/$TAG/build.log 2>&1 || { echo "$B: BUILD FAILED"; tail -5 $RUNS/$TAG/build.log; continue; }
   for V in init trained; do for rep in 1 2; do
     env $B python bench.py --full --no-cpu-baseline --no-second-variant --steps 60 --warmup 40 --primary-steps 0 --emulate-world $W --variant $V 2>/dev/null | tail -1 > $RUNS/$TAG/emu.json
     python - <<PY

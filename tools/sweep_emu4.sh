@@ -1,15 +1,15 @@
 #!/bin/bash
 # Usage (GPU box): tools/sweep_emu4.sh <tag> "<worlds>" "BUILDENV1" "BUILDENV2" ... - rank 0 of emulated partitions (team help on) per build-time setting, both
-# clouds, two runs each; "-" = the library as it is, "run:VAR=x" = an environment setting of the run (neither rebuilds)
+# clouds, two runs each; "-" = the product, "run:VAR=x" = an environment setting of the run (neither builds)
 RUNS=${EGR_RUNS_DIR:-runs}  # results go to $RUNS/<tag> (runs/ is kept out of git)
 TAG=$1; WORLDS=$2; shift 2
 mkdir -p $RUNS/$TAG
 for B in "$@"; do
   E=""
-  if [ "${B#run:}" != "$B" ]; then E="${B#run:}"  # "run:VAR=x": an environment setting of the RUN, no rebuild
+  if [ "${B#run:}" != "$B" ]; then E="${B#run:}"  # "run:VAR=x": an environment setting of the RUN, no build
   elif [ "$B" != "-" ]; then
-    touch editable-gaussian-reflections_amd/csrc/trace.hip
-    env $B python -c "import importlib; importlib.import_module('editable-gaussian-reflections_amd.build').build_all()" > $RUNS/$TAG/build.log 2>&1 || { echo "$B: BUILD FAILED"; tail -5 $RUNS/$TAG/build.log; continue; }
+    env $B tools/build_variant.sh > $RUNS/$TAG/build.log 2>&1 || { echo "$B: BUILD FAILED"; tail -5 $RUNS/$TAG/build.log; continue; }
+    E="$B"  # (the run loads the build its settings select)
   fi
   for W in $WORLDS; do for V in init trained; do for rep in 1 2; do
     env $E python bench.py --full --no-cpu-baseline --no-second-variant --steps 60 --warmup 40 --primary-steps 0 --emulate-world $W --variant $V 2>/dev/null | tail -1 > $RUNS/$TAG/emu.json
