@@ -45,6 +45,15 @@ egr_view_batch = _struct("egr_view_batch", [("num_views", C.c_uint32), ("samples
 TRAIN_BATCH_TARGETS = ("target_diffuse", "target_specular", "target_depth", "target_normal", "target_roughness", "target_f0")
 egr_train_batch = _struct("egr_train_batch", [("num_views", C.c_uint32), ("rotation_c2w_dataset", _F), ("camera_center", _F), ("vertical_fov_radians", _F),
                                               ("znear", C.c_float), ("zfar", C.c_float)] + [(k, _F) for k in TRAIN_BATCH_TARGETS])
+EGR_MAX_PRUNE_ARRAYS = 32
+EGR_PRUNE_ROWS_PER_WG = 1024
+egr_prune_array = _struct("egr_prune_array", [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_uint32)])
+
+
+def prune_workspace_bytes(n):
+    """EGR_PRUNE_WORKSPACE_BYTES(n) of the header: 16 wave ballots (8 bytes) + 1 count (4 bytes) per EGR_PRUNE_ROWS_PER_WG rows."""
+    return ((n + EGR_PRUNE_ROWS_PER_WG - 1) // EGR_PRUNE_ROWS_PER_WG) * (16 * 8 + 4)
+
 
 _lib = None
 
@@ -84,6 +93,11 @@ def lib(path=None):
         L.egr_train_views.argtypes = [P, C.POINTER(egr_train_batch), P]
         L.egr_get_counters.argtypes = [P, C.POINTER(egr_counters), P]
         L.egr_get_counters_ex.argtypes = [P, P, C.c_size_t, P]
+        # fused prune (csrc/prune.hip): device, n, total_weight, divisor, min_weight, points, cam_centers, cam_znear, num_cams, remove_mask, src_index, count, workspace, stream
+        L.egr_prune_select.argtypes = [C.c_int, C.c_uint32, P, C.c_float, C.c_float, P, P, P, C.c_uint32, P, P, P, P, P]
+        L.egr_prune_gather.argtypes = [C.c_int, C.POINTER(egr_prune_array), C.c_int, C.c_uint32, P, C.c_uint32, P]  # device, table, entries, n, src_index, count, stream
+        L.egr_prune_last_error.argtypes = []
+        L.egr_prune_last_error.restype = C.c_char_p
         L.egr_last_error.argtypes = [P]
         L.egr_last_error.restype = C.c_char_p
         L.egr_version.restype = C.c_char_p

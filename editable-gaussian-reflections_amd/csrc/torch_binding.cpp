@@ -702,6 +702,90 @@ static void fused_adam_step(std::vector<torch::Tensor> params, std::vector<torch
     TORCH_CHECK(rc == 0, egr_fused_step_last_error());
 }
 
+// Fused prune, part 1 (egr_prune_select, csrc/prune.hip): which rows survive. Every criterion is optional (None = skipped) but at least one of
+// total_weight [N] / [N,1], points [N,3], remove_mask [N] (uint8 or bool) must be given - it fixes N. Returns (src_index int32 [N]: the first `count`
+// entries are the kept rows, ascending; count int32 [1]) on the device, asynchronously: reading `count` is the caller's one synchronisation.
+static std::tuple<Tensor, Tensor> prune_select(const c10::optional<Tensor> &total_weight, double divisor, double min_weight, const c10::optional<Tensor> &points,
+                                               const c10::optional<Tensor> &cam_centers, const c10::optional<Tensor> &cam_znear, const c10::optional<Tensor> &remove_mask) {
+    auto given = [](const c10::optional<Tensor> &t) { return t.has_value() && t->defined(); };
+    int64_t n = -1;
+    c10::Device dev(torch::kCUDA);
+    auto rows = [&](const Tensor &t, const char *what) {
+        TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() >= 1, "prune_select: ", what, " must be a contiguous GPU tensor");
+        TORCH_CHECK(n < 0 || (t.size(0) == n && t.device() == dev), "prune_select: ", what, " has ", t.size(0), " rows on ", t.device(), ", expected ", n, " on ", dev);
+        n = t.size(0), dev = t.device();
+    };
+    const float *tw = nullptr, *pts = nullptr, *cc = nullptr, *cz = nullptr;
+    const uint8_t *mask = nullptr;
+    int64_t num_cams = 0;
+    if (given(total_weight)) {
+        rows(*total_weight, "total_weight");
+        TORCH_CHECK(total_weight->scalar_type() == torch::kFloat32 && total_weight->numel() == n, "prune_select: total_weight must be fp32 [N] or [N,1]");
+        tw = total_weight->data_ptr<float>();
+    }
+    if (given(points)) {
+        rows(*points, "points");
+        TORCH_CHECK(points->scalar_type() == torch::kFloat32 && points->dim() == 2 && points->size(1) == 3, "prune_select: points must be fp32 [N,3]");
+        pts = points->data_ptr<float>();
+    }
+    if (given(remove_mask)) {
+        rows(*remove_mask, "remove_mask");
+        TORCH_CHECK((remove_mask->scalar_type() == torch::kUInt8 || remove_mask->scalar_type() == torch::kBool) && remove_mask->numel() == n, "prune_select: remove_mask must be uint8 or bool [N]");
+        mask = reinterpret_cast<const uint8_t *>(remove_mask->data_ptr());
+    }
+    TORCH_CHECK(n >= 0, "prune_select: one of total_weight, points, remove_mask is required (it fixes the number of rows)");
+    TORCH_CHECK(given(cam_centers) == given(cam_znear), "prune_select: cam_centers and cam_znear go together");
+    if (given(cam_centers)) {
+        TORCH_CHECK(pts != nullptr, "prune_select: the camera criterion needs points");
+        num_cams = cam_znear->numel();
+        TORCH_CHECK(cam_centers->is_cuda() && cam_centers->device() == dev && cam_centers->scalar_type() == torch::kFloat32 && cam_centers->is_contiguous() && cam_centers->dim() == 2 &&
+                        cam_centers->size(0) == num_cams && cam_centers->size(1) == 3,
+                    "prune_select: cam_centers must be a contiguous fp32 [C,3] tensor on the points' device");
+        TORCH_CHECK(cam_znear->is_cuda() && cam_znear->device() == dev && cam_znear->scalar_type() == torch::kFloat32 && cam_znear->is_contiguous() && cam_znear->dim() == 1,
+                    "prune_select: cam_znear must be a contiguous fp32 [C] tensor on the points' device");
+        cc = cam_centers->data_ptr<float>(), cz = cam_znear->data_ptr<float>();
+    }
+    TORCH_CHECK(n <= (int64_t)0xFFFFFFFFll, "prune_select: too many rows");
+    const auto i32 = torch::dtype(torch::kInt32).device(dev);
+    Tensor src_index = torch::empty({n}, i32), count = torch::zeros({1}, i32);
+    if (n == 0) return {src_index, count}; // (no rows: count 0, nothing to launch)
+    Tensor workspace = torch::empty({(int64_t)(EGR_PRUNE_WORKSPACE_BYTES(n) + 7) / 8}, torch::dtype(torch::kInt64).device(dev)); // (freed stream-ordered by the caching allocator)
+    const int rc = egr_prune_select(dev.index(), (uint32_t)n, tw, (float)divisor, (float)min_weight, pts, cc, cz, (uint32_t)num_cams, mask,
+                                    reinterpret_cast<uint32_t *>(src_index.data_ptr<int32_t>()), reinterpret_cast<uint32_t *>(count.data_ptr<int32_t>()),
+                                    workspace.data_ptr(), current_stream());
+    TORCH_CHECK(rc == 0, egr_prune_last_error());
+    return {src_index, count};
+}
+// Fused prune, part 2 (egr_prune_gather): out[k] = src[k][src_index[:count]] for every tensor of `src` - contiguous GPU tensors of 4-byte elements (fp32,
+// int32) with the same leading size - as one launch per EGR_MAX_PRUNE_ARRAYS tensors over the same index list. The outputs are new tensors of the source's
+// dtype and trailing shape with `count` rows.
+static std::vector<Tensor> prune_gather(std::vector<Tensor> src, const Tensor &src_index, int64_t count) {
+    TORCH_CHECK(src_index.is_cuda() && src_index.scalar_type() == torch::kInt32 && src_index.is_contiguous() && src_index.dim() == 1, "prune_gather: src_index must be the int32 list of prune_select");
+    TORCH_CHECK(count >= 0 && count <= src_index.numel(), "prune_gather: count must be in 0..", src_index.numel());
+    std::vector<Tensor> out;
+    if (src.empty()) return out;
+    const int64_t n = src[0].dim() >= 1 ? src[0].size(0) : -1;
+    TORCH_CHECK(n == src_index.numel(), "prune_gather: the tensors need the ", src_index.numel(), " rows the index list was selected from");
+    std::vector<egr_prune_array> table;
+    for (const Tensor &t : src) {
+        TORCH_CHECK(t.is_cuda() && t.device() == src_index.device() && t.is_contiguous() && t.element_size() == 4 && t.dim() >= 1 && t.size(0) == n,
+                    "prune_gather: contiguous GPU tensors of 4-byte elements with the same leading size are required");
+        auto shape = t.sizes().vec();
+        shape[0] = count;
+        out.push_back(torch::empty(shape, t.options()));
+        const int64_t width = n ? t.numel() / n : 1;
+        if (width == 0) continue; // (a [N,0] tensor has no elements to move)
+        table.push_back(egr_prune_array{t.data_ptr(), out.back().data_ptr(), (uint32_t)width});
+    }
+    if (n == 0 || count == 0) return out; // (empty tensors have no storage to hand to the library)
+    for (size_t k0 = 0; k0 < table.size(); k0 += EGR_MAX_PRUNE_ARRAYS) {
+        const int rc = egr_prune_gather(src_index.get_device(), table.data() + k0, (int)std::min<size_t>(EGR_MAX_PRUNE_ARRAYS, table.size() - k0), (uint32_t)n,
+                                        reinterpret_cast<const uint32_t *>(src_index.data_ptr<int32_t>()), (uint32_t)count, current_stream());
+        TORCH_CHECK(rc == 0, egr_prune_last_error());
+    }
+    return out;
+}
+
 // unit-test hook (egr_debug_lean_arith): (a / b, sqrt(a)) as the hot kernels' division and square root compute them
 static std::tuple<torch::Tensor, torch::Tensor> debug_lean_arith(const torch::Tensor &a, const torch::Tensor &b) {
     TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.numel() == b.numel(), "debug_lean_arith: two GPU tensors of one size expected");
@@ -717,6 +801,10 @@ TORCH_LIBRARY(egr, m) {
           "float[] clamp_min, float[] clamp_max, float[] log_decay, int step, float beta1, float beta2, float eps, int[] group_steps=[]) -> ()",
           &fused_adam_step);
     m.def("debug_lean_arith(Tensor a, Tensor b) -> (Tensor, Tensor)", &debug_lean_arith);
+    m.def("prune_select(Tensor? total_weight, float divisor, float min_weight, Tensor? points, Tensor? cam_centers, Tensor? cam_znear, Tensor? remove_mask) -> "
+          "(Tensor src_index, Tensor count)",
+          &prune_select);
+    m.def("prune_gather(Tensor[] src, Tensor src_index, int count) -> Tensor[]", &prune_gather);
 }
 
 TORCH_LIBRARY(raytracer, m) {

@@ -34,6 +34,28 @@ def expon_lr(step, lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_s
     return float(rate)
 
 
+def _camera_spheres(cam_centers, cam_znear, device):
+    """(centers [C,3], znear [C]) as contiguous fp32 tensors on `device` for torch.ops.egr.prune_select, or (None, None) without cameras. `cam_znear`
+    may be one number for all cameras."""
+    if cam_centers is None:
+        return None, None
+    centers = torch.as_tensor(cam_centers, dtype=torch.float32, device=device).reshape(-1, 3).contiguous()
+    znear = torch.as_tensor(cam_znear, dtype=torch.float32, device=device).reshape(-1)
+    if znear.numel() == 1 and centers.shape[0] != 1:
+        znear = znear.expand(centers.shape[0])
+    return centers, znear.contiguous()
+
+
+@torch.no_grad()
+def filter_points_near_cameras(points, cam_centers, cam_znear):
+    """The far-field candidate filter of add_farfield_points (`points[~scene.select_points_to_prune_near_cameras(points)]`): the rows of `points`
+    [N,3] (fp32, GPU) outside every camera's znear sphere, in their old order - one select, one read-back, one gather."""
+    points = points.contiguous()
+    centers, znear = _camera_spheres(cam_centers, cam_znear, points.device)
+    src_index, count = torch.ops.egr.prune_select(None, 1.0, 0.0, points, centers, znear, None)
+    return torch.ops.egr.prune_gather([points], src_index, int(count.item()))[0]
+
+
 class FusedTrainStep:
     """`step()` = import + scale decay + Adam + clamps + both zero_grads + export, one kernel over all eight groups.
 
@@ -61,11 +83,47 @@ class FusedTrainStep:
         train.py:238-249 prunes BETWEEN render() and optimizer.step(): upstream the raytracer gradients of that iteration were
         already added to the old parameters' `.grad`, which prune_points replaces by zeros, so the step that follows sees a zero
         gradient. Here the import happens inside the fused step, so the iteration's raytracer gradients are dropped now
-        (resize() would otherwise keep their first rows, misaligned with the pruned model)."""
+        (resize() would otherwise keep their first rows, misaligned with the pruned model).
+        `prune_and_rebuild` is this whole sequence - criteria, parameters, moments, zeroing, rebuild - as one call that cannot go out of step."""
         for name in self.exp_avg:
             self.exp_avg[name] = self.exp_avg[name][keep_mask].contiguous()
             self.exp_avg_sq[name] = self.exp_avg_sq[name][keep_mask].contiguous()
         self.rt.zero_grad()
+
+    @torch.no_grad()
+    def prune_and_rebuild(self, min_weight=0.0, interval=1, cam_centers=None, cam_znear=None, remove_mask=None, extra=()):
+        """The pruning step of train.py:238-249 as ONE call (csrc/prune.hip): select + compact + resize + rebuild with one host read-back.
+        A row is removed if `total_weight / interval < min_weight` (the native total_weight; IEEE fp32 division, strict `<`: NaN and +inf stay), or
+        if it lies inside a camera's znear sphere (`|xyz - cam_centers[c]| < cam_znear[c]` for any c: scene.select_points_to_prune_near_cameras;
+        cam_centers [C,3], cam_znear [C] or one number), or if `remove_mask` (bool / uint8 [N]) marks it. With `train_views` pass interval * V.
+        `extra`: further per-row tensors of the caller's model (4-byte elements, e.g. upstream's `_round_counter`); they come back compacted.
+        Leaves bit for bit what `pc.prune_points(mask); self.prune(~mask); total_weight.zero_(); rt.rebuild_bvh()` leaves for the same mask: kept rows
+        in their old order in the 8 parameters (fresh zero `.grad`) and the 16 moments, the iteration's raytracer gradients dropped, total_weight
+        restarted, the tree rebuilt. The result depends on the inputs alone, so the ranks of a partition - which all hold the same all-reduced
+        total_weight - keep identical clouds. Returns (n_kept, [compacted extra tensors]); raises ValueError, before anything is touched, if no row
+        would survive."""
+        pc, g = self.pc, self.rt.cuda_module.get_gaussians()
+        xyz = pc._xyz
+        centers, znear = _camera_spheres(cam_centers, cam_znear, xyz.device)
+        if remove_mask is not None:
+            remove_mask = torch.as_tensor(remove_mask, device=xyz.device).contiguous()
+        src_index, count = torch.ops.egr.prune_select(g.total_weight, float(interval), float(min_weight), xyz, centers, znear, remove_mask)
+        n_kept = int(count.item())  # the one synchronisation
+        if n_kept == 0:
+            raise ValueError("prune_and_rebuild: no gaussian would survive (nothing was changed)")
+        attrs = [attr for _, attr, _ in GROUPS]
+        names = [name for name, _, _ in GROUPS]
+        extra = list(extra)
+        out = torch.ops.egr.prune_gather([getattr(pc, a) for a in attrs] + [self.exp_avg[n] for n in names] + [self.exp_avg_sq[n] for n in names] + extra,
+                                         src_index, n_kept)
+        for k, attr in enumerate(attrs):
+            out[k].grad = torch.zeros_like(out[k])
+            setattr(pc, attr, out[k])
+        for k, name in enumerate(names):
+            self.exp_avg[name], self.exp_avg_sq[name] = out[8 + k], out[16 + k]
+        self.rt.rebuild_bvh()  # resize + export + full build
+        self.rt.cuda_module.get_gaussians().grad_flat.zero_()  # resize kept the first rows of the old gradients and weights: the gradients in flight are dropped, total_weight restarts
+        return n_kept, out[24:]
 
     @torch.no_grad()
     def extend(self, n_new):

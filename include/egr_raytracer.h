@@ -394,6 +394,47 @@ int egr_fused_adam_step(int device, const egr_param_group *groups, int num_group
                         double eps, void *hip_stream);
 const char *egr_fused_step_last_error(void);
 
+/* ---- Fused prune (not in the reference as one call; additive symbols of library version 0.8, egr_version() is unchanged): what train.py:238-245,
+ * scene/scene.py:88-105 (select_points_to_prune_near_cameras) and scene/gaussian_model.py:478-531 (prune_points / _prune_optimizer) do with one
+ * nonzero + index pair per tensor, as a SELECT - criteria + stable scan - and ONE out-of-place GATHER over all arrays (csrc/prune.hip).
+ *
+ * egr_prune_select: row i of n is REMOVED if any of up to three optional criteria holds -
+ *   weight        total_weight[i] / divisor < min_weight, evaluated in that form: IEEE fp32 division, strict `<` - a row whose quotient EQUALS
+ *                 min_weight is kept, and so are NaN and +inf (-inf goes). total_weight == NULL skips the criterion.
+ *   near a camera sqrt(dx^2 + dy^2 + dz^2) < cam_znear[c] in fp32 for ANY of num_cams cameras (d = points[i] - cam_centers[c]; strict: znear 0 removes
+ *                 nothing, a point AT a centre goes when znear > 0). points = [n][3], cam_centers = [num_cams][3], cam_znear = [num_cams]; any number
+ *                 of cameras (staged through LDS in chunks). points == NULL or num_cams == 0 skips the criterion.
+ *   caller's mask remove_mask[i] != 0 (uint8 [n]). NULL skips it.
+ * Outputs (device): src_index[0 .. count) = the KEPT row numbers in ASCENDING order - this order is what makes a gather equal to `tensor[keep]` - the rest
+ * of src_index [n] is not written; count [1] = their number. workspace: EGR_PRUNE_WORKSPACE_BYTES(n) bytes of device memory, 8-byte aligned, owned by the
+ * caller (the library allocates nothing) and free for reuse once the stream has passed the call.
+ * Three launches, asynchronous on the stream; the stream order between them is the only dependency between workgroups (no workgroup ever waits for
+ * another), and the result depends on nothing but the inputs: ranks that hold the same all-reduced total_weight select the same rows.
+ * ONE synchronisation belongs to a prune, and it is the caller's: reading `count` back before sizing the gather's outputs.
+ * Arguments are validated BEFORE any HIP call (NULL src_index / count, n > 2^26 - the tree's own limit -, cameras without their arrays, a missing or
+ * misaligned workspace): returns non-zero, egr_prune_last_error() says why. n == 0 returns 0 and touches nothing: there are no rows, `count` is 0 by
+ * definition and is not written.
+ *
+ * egr_prune_gather: dst[r * width + c] = src[src_index[r] * width + c] for r < count, for each of 1..EGR_MAX_PRUNE_ARRAYS table entries in one launch.
+ * Elements are 4-byte words moved as bits (fp32 and int32 alike; NaN payloads survive). n = rows of every src (count <= n <= 2^26). OUT OF PLACE ONLY:
+ * a dst range [count][width] that touches any src range [n][width] (src == dst included) or another dst is refused - stable compaction in place is not
+ * safe in parallel. Also refused before any HIP call: a NULL table / src / dst / src_index, width 0, more than EGR_MAX_PRUNE_ARRAYS entries.
+ * count == 0 returns 0 and launches nothing. Asynchronous on the stream. */
+#define EGR_MAX_PRUNE_ARRAYS 32
+#define EGR_PRUNE_ROWS_PER_WG 1024u /* rows one workgroup of the select covers: 16 wave ballots (8 bytes each) + 1 count (4 bytes) of workspace */
+#define EGR_PRUNE_WORKSPACE_BYTES(n) ((((size_t)(n) + EGR_PRUNE_ROWS_PER_WG - 1) / EGR_PRUNE_ROWS_PER_WG) * (16 * 8 + 4))
+typedef struct egr_prune_array {
+    const void *src; /* [n][width] 4-byte elements                  */
+    void *dst;       /* [count][width], must not overlap any src    */
+    uint32_t width;  /* elements per row, >= 1                      */
+} egr_prune_array;
+int egr_prune_select(int device, uint32_t n, const float *total_weight, float divisor, float min_weight, const float *points,
+                     const float *cam_centers, const float *cam_znear, uint32_t num_cams, const uint8_t *remove_mask, uint32_t *src_index,
+                     uint32_t *count, void *workspace, void *hip_stream);
+int egr_prune_gather(int device, const egr_prune_array *arrays, int num_arrays, uint32_t n, const uint32_t *src_index, uint32_t count,
+                     void *hip_stream);
+const char *egr_prune_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif
