@@ -49,6 +49,22 @@ EGR_MAX_PRUNE_ARRAYS = 32
 EGR_PRUNE_ROWS_PER_WG = 1024
 egr_prune_array = _struct("egr_prune_array", [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_uint32)])
 
+# scene editing (csrc/edit.hip): selection objects (host), edit records (device) and the two tables of eight arrays
+EGR_MAX_EDIT_OBJECTS = 32
+EGR_EDIT_SEL_CYLINDER, EGR_EDIT_SEL_EVERYTHING, EGR_EDIT_SEL_RANGE_F0, EGR_EDIT_SEL_RANGE_ROUGHNESS, EGR_EDIT_SEL_RANGE_DIFFUSE, EGR_EDIT_SEL_ZRANGE = 1, 2, 4, 8, 16, 32
+EGR_EDIT_ROUGHNESS, EGR_EDIT_DIFFUSE, EGR_EDIT_F0, EGR_EDIT_TRANSFORM, EGR_EDIT_REMOVED, EGR_EDIT_ROUGHNESS_OVERRIDE = 1, 2, 4, 8, 16, 32
+_F3 = C.c_float * 3
+egr_edit_object = _struct("egr_edit_object", [("box_min", _F3), ("box_max", _F3), ("sub_min", _F3), ("range_lo", _F3), ("range_hi", _F3), ("flags", C.c_uint32),
+                                              ("exclude", C.c_uint32)])
+egr_edit_colour = _struct("egr_edit_colour", [("override_rgb", _F3), ("override_w", C.c_float), ("hue", C.c_float), ("s_shift", C.c_float), ("s_mult", C.c_float),
+                                              ("v_shift", C.c_float), ("v_mult", C.c_float)])
+egr_edit_record = _struct("egr_edit_record", [("flags", C.c_uint32), ("roughness_base", C.c_float), ("roughness_shift", C.c_float), ("roughness_mult", C.c_float),
+                                              ("diffuse", egr_edit_colour), ("f0", egr_edit_colour), ("translate", _F3), ("centre", _F3), ("scale", C.c_float),
+                                              ("log_scale", C.c_float), ("R", C.c_float * 9), ("q", C.c_float * 4)])
+EDIT_ARRAYS = ("scale", "rotation", "mean", "opacity", "rgb", "normal", "roughness", "f0")  # the export order of gaussian_raytracer.py:41-50
+EDIT_ARRAY_WIDTHS = (3, 4, 3, 1, 3, 3, 1, 3)
+egr_edit_arrays = _struct("egr_edit_arrays", [(k, C.c_void_p) for k in EDIT_ARRAYS])
+
 
 def prune_workspace_bytes(n):
     """EGR_PRUNE_WORKSPACE_BYTES(n) of the header: 16 wave ballots (8 bytes) + 1 count (4 bytes) per EGR_PRUNE_ROWS_PER_WG rows."""
@@ -98,6 +114,11 @@ def lib(path=None):
         L.egr_prune_gather.argtypes = [C.c_int, C.POINTER(egr_prune_array), C.c_int, C.c_uint32, P, C.c_uint32, P]  # device, table, entries, n, src_index, count, stream
         L.egr_prune_last_error.argtypes = []
         L.egr_prune_last_error.restype = C.c_char_p
+        # scene editing (csrc/edit.hip): device, n, xyz, f0, roughness, diffuse, objects (host), num_objects, mask, stream
+        L.egr_edit_select.argtypes = [C.c_int, C.c_uint32, P, P, P, P, C.POINTER(egr_edit_object), C.c_uint32, P, P]
+        L.egr_edit_apply.argtypes = [C.c_int, C.c_uint32, C.POINTER(egr_edit_arrays), C.POINTER(egr_edit_arrays), P, P, C.c_uint32, P]  # device, n, src, dst, mask, records (device), num_records, stream
+        L.egr_edit_last_error.argtypes = []
+        L.egr_edit_last_error.restype = C.c_char_p
         L.egr_last_error.argtypes = [P]
         L.egr_last_error.restype = C.c_char_p
         L.egr_version.restype = C.c_char_p

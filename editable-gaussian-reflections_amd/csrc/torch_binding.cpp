@@ -786,6 +786,60 @@ static std::vector<Tensor> prune_gather(std::vector<Tensor> src, const Tensor &s
     return out;
 }
 
+// Scene editing, part 1 (egr_edit_select, csrc/edit.hip): the membership mask of up to 32 objects. `objects`: a CPU int32 tensor [K, 17] holding K
+// egr_edit_object records as bits (editing.py packs them); xyz fp32 [N,3] on the GPU; f0 [N,3], roughness [N,1], diffuse [N,3] only where an object has
+// that property range. Returns int32 [N] (bit k = row belongs to object k) on the current stream, no host synchronisation.
+static Tensor edit_select(const Tensor &xyz, const c10::optional<Tensor> &f0, const c10::optional<Tensor> &roughness, const c10::optional<Tensor> &diffuse, const Tensor &objects) {
+    TORCH_CHECK(xyz.is_cuda() && xyz.scalar_type() == torch::kFloat32 && xyz.is_contiguous() && xyz.dim() == 2 && xyz.size(1) == 3, "edit_select: xyz must be a contiguous fp32 [N,3] GPU tensor");
+    const int64_t n = xyz.size(0);
+    TORCH_CHECK(n <= (int64_t)1 << 26, "edit_select: n exceeds 2^26 rows (the limit of the tree)");
+    TORCH_CHECK(!objects.is_cuda() && objects.scalar_type() == torch::kInt32 && objects.is_contiguous() && objects.dim() == 2 &&
+                    objects.size(1) == (int64_t)(sizeof(egr_edit_object) / 4),
+                "edit_select: objects must be a contiguous CPU int32 [K,", sizeof(egr_edit_object) / 4, "] tensor (egr_edit_object records)");
+    TORCH_CHECK(objects.size(0) <= EGR_MAX_EDIT_OBJECTS, "edit_select: at most ", EGR_MAX_EDIT_OBJECTS, " objects");
+    auto ptr = [&](const c10::optional<Tensor> &t, int64_t width, const char *what) -> const float * {
+        if (!t.has_value() || !t->defined()) return nullptr;
+        TORCH_CHECK(t->is_cuda() && t->device() == xyz.device() && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->numel() == n * width,
+                    "edit_select: ", what, " must be a contiguous fp32 [N,", width, "] tensor on xyz's device");
+        return t->data_ptr<float>();
+    };
+    const float *pf0 = ptr(f0, 3, "f0"), *pr = ptr(roughness, 1, "roughness"), *pd = ptr(diffuse, 3, "diffuse");
+    Tensor mask = torch::empty({n}, torch::dtype(torch::kInt32).device(xyz.device()));
+    if (n == 0) return mask; // (no rows: nothing to launch)
+    const int rc = egr_edit_select(xyz.get_device(), (uint32_t)n, xyz.data_ptr<float>(), pf0, pr, pd, reinterpret_cast<const egr_edit_object *>(objects.data_ptr<int32_t>()),
+                                   (uint32_t)objects.size(0), reinterpret_cast<uint32_t *>(mask.data_ptr<int32_t>()), current_stream());
+    TORCH_CHECK(rc == 0, egr_edit_last_error());
+    return mask;
+}
+// Scene editing, part 2 (egr_edit_apply): edit and export in one launch. `src` / `dst`: eight contiguous fp32 GPU tensors each, in the export order
+// scale [N,3], rotation [N,4], mean [N,3], opacity [N,1], rgb [N,3], normal [N,3], roughness [N,1], f0 [N,3]; dst[k] may be src[k] itself. `mask`: the int32 [N]
+// tensor of edit_select; `records`: a GPU int32 tensor [K, 43] holding K egr_edit_record records as bits. Current stream, no host synchronisation.
+static void edit_apply(std::vector<Tensor> src, std::vector<Tensor> dst, const Tensor &mask, const Tensor &records) {
+    static const int64_t width[8] = {3, 4, 3, 1, 3, 3, 1, 3};
+    TORCH_CHECK(src.size() == 8 && dst.size() == 8, "edit_apply: src and dst are eight tensors each (scale, rotation, mean, opacity, rgb, normal, roughness, f0)");
+    TORCH_CHECK(src[0].dim() >= 1, "edit_apply: tensors with rows are required");
+    const int64_t n = src[0].size(0);
+    TORCH_CHECK(n <= (int64_t)1 << 26, "edit_apply: n exceeds 2^26 rows (the limit of the tree)");
+    const auto dev = src[0].device();
+    egr_edit_arrays s{}, d{};
+    float **sp = &s.scale, **dp = &d.scale;
+    for (int k = 0; k < 8; k++) {
+        for (const Tensor *t : {&src[k], &dst[k]})
+            TORCH_CHECK(t->is_cuda() && t->device() == dev && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->dim() >= 1 && t->size(0) == n && t->numel() == n * width[k],
+                        "edit_apply: tensor ", k, " must be a contiguous fp32 [N,", width[k], "] GPU tensor");
+        sp[k] = src[k].data_ptr<float>(), dp[k] = dst[k].data_ptr<float>();
+    }
+    TORCH_CHECK(records.is_cuda() && records.device() == dev && records.scalar_type() == torch::kInt32 && records.is_contiguous() && records.dim() == 2 &&
+                    records.size(1) == (int64_t)(sizeof(egr_edit_record) / 4) && records.size(0) <= EGR_MAX_EDIT_OBJECTS,
+                "edit_apply: records must be a contiguous GPU int32 [K <= 32,", sizeof(egr_edit_record) / 4, "] tensor (egr_edit_record records)");
+    TORCH_CHECK(mask.is_cuda() && mask.device() == dev && mask.scalar_type() == torch::kInt32 && mask.is_contiguous() && mask.dim() == 1 && mask.size(0) == n,
+                "edit_apply: mask must be the int32 [N] tensor of edit_select");
+    if (n == 0) return; // (empty tensors have no storage to hand to the library)
+    const int rc = egr_edit_apply(dev.index(), (uint32_t)n, &s, &d, reinterpret_cast<const uint32_t *>(mask.data_ptr<int32_t>()),
+                                  records.size(0) ? reinterpret_cast<const egr_edit_record *>(records.data_ptr<int32_t>()) : nullptr, (uint32_t)records.size(0), current_stream());
+    TORCH_CHECK(rc == 0, egr_edit_last_error());
+}
+
 // unit-test hook (egr_debug_lean_arith): (a / b, sqrt(a)) as the hot kernels' division and square root compute them
 static std::tuple<torch::Tensor, torch::Tensor> debug_lean_arith(const torch::Tensor &a, const torch::Tensor &b) {
     TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.numel() == b.numel(), "debug_lean_arith: two GPU tensors of one size expected");
@@ -805,6 +859,8 @@ TORCH_LIBRARY(egr, m) {
           "(Tensor src_index, Tensor count)",
           &prune_select);
     m.def("prune_gather(Tensor[] src, Tensor src_index, int count) -> Tensor[]", &prune_gather);
+    m.def("edit_select(Tensor xyz, Tensor? f0, Tensor? roughness, Tensor? diffuse, Tensor objects) -> Tensor", &edit_select);
+    m.def("edit_apply(Tensor[] src, Tensor[] dst, Tensor mask, Tensor records) -> ()", &edit_apply);
 }
 
 TORCH_LIBRARY(raytracer, m) {

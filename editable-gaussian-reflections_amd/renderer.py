@@ -64,7 +64,7 @@ class GaussianParams:
             t.grad = torch.zeros_like(t)
             setattr(self, name, t)
 
-    # getters read by _export_param_values (gaussian_raytracer.py:41-50); an EditableGaussianModel overrides these
+    # getters read by _export_param_values (gaussian_raytracer.py:41-50); editing.EditableGaussians overrides these
     get_scaling = property(lambda s: torch.exp(s._scaling))
     _get_scaling = property(lambda s: s._scaling)
     _get_rotation = property(lambda s: s._rotation)
@@ -136,6 +136,9 @@ class GaussianRaytracer:
     @torch.no_grad()
     def _export_param_values(self):  # gaussian_raytracer.py:41-50 (same order)
         g = self.cuda_module.get_gaussians()
+        if hasattr(self.pc, "export_edited"):  # editing.EditableGaussians: edit and export in one launch (csrc/edit.hip)
+            self.pc.export_edited(g)
+            return
         # the eight copy_ calls upstream, as one multi-tensor launch (same order, same semantics)
         torch._foreach_copy_([g.scale, g.rotation, g.mean, g.opacity, g.rgb, g.normal, g.roughness, g.f0],
                              [self.pc._get_scaling, self.pc._get_rotation, self.pc.get_xyz, self.pc._opacity, self.pc.get_diffuse, self.pc.get_normal,

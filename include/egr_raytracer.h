@@ -435,6 +435,101 @@ int egr_prune_gather(int device, const egr_prune_array *arrays, int num_arrays, 
                      void *hip_stream);
 const char *egr_prune_last_error(void);
 
+/* ---- Scene editing (additive symbols of library version 0.8, egr_version() is unchanged): the reference's EditableGaussianModel
+ * (scene/editable_gaussian_model.py: make_editable's selections and the seven getter overrides) as a SELECT that writes one bitmask per row and ONE
+ * pass that applies every object's edit and writes the tracer's eight native arrays - edit and export in one launch (csrc/edit.hip).
+ *
+ * egr_edit_select: mask[i] bit k = row i belongs to objects[k], k < num_objects <= EGR_MAX_EDIT_OBJECTS, evaluated on the UNEDITED raw parameters:
+ *   shape      box: box_min <= p <= box_max on all three axes, BOTH ENDS INCLUSIVE, exact fp32 comparisons. EGR_EDIT_SEL_CYLINDER: the ellipse inscribed
+ *              in the box's xy extent - ((x - cx) / hx)^2 + ((y - cy) / hy)^2 <= 1 with c = 0.5 (min + max), h = 0.5 (max - min) in fp32 - and
+ *              box_min.z <= z <= box_max.z. EGR_EDIT_SEL_EVERYTHING: every row, whatever else the object says.
+ *   ranges     EGR_EDIT_SEL_RANGE_F0 / _ROUGHNESS / _DIFFUSE: the mean over the channels of the RAW parameter ((a + b + c) / 3 in fp32; one channel: the
+ *              value itself) lies in [range_lo[j], range_hi[j]], both ends inclusive (j = 0 f0, 1 roughness, 2 diffuse). With EGR_EDIT_SEL_ZRANGE a row
+ *              inside the sub-box [sub_min, box_max] (inclusive) is exempt from every range test. The reference also lists "metalness", an attribute its
+ *              model does not have: there is no such range here.
+ *   exclude    bit j set: rows inside the SHAPE (box or cylinder, not the ranges) of objects[j] are taken out.
+ * `objects` is HOST memory (it travels as a kernel argument: no upload); xyz [n][3]; f0 [n][3], roughness [n][1], diffuse [n][3] may be NULL unless an
+ * object has the matching range flag. One launch, asynchronous on the stream.
+ *
+ * egr_edit_apply: one pass over the n rows. Reads the eight raw arrays of `src` and `mask`, applies records[k] for every set bit k in ascending k -
+ * EACH ON THE RESULT OF THE ONE BEFORE - and writes the eight arrays of `dst`. `records` is DEVICE memory ([num_records] egr_edit_record, staged in LDS).
+ * A row whose mask has no bit below num_records set, and every group of a record whose flag is clear, is copied BIT FOR BIT (NaN payloads, -0, denormals).
+ * Everything that depends on the edit alone is precomputed by the caller (editing.py does it in fp64): the kernel contains no trigonometry.
+ *   EGR_EDIT_ROUGHNESS  r = clamp(roughness_mult * (base + roughness_shift), 0, 1), base = roughness_base with EGR_EDIT_ROUGHNESS_OVERRIDE, else r
+ *                       (the caller stores override^2 and |shift|: the reference's copysign(shift, shift^2))
+ *   EGR_EDIT_DIFFUSE / EGR_EDIT_F0 (egr_edit_colour): x = lerp(x, override_rgb, override_w) in torch's two-branch form; RGB -> HSV by the hexcone
+ *                       formula (v = max, s = (max - min) / (max + 1e-8), sector of the FIRST channel that attains the max, achromatic hue 0, hue in
+ *                       radians in [0, 2 pi)); h = (h + hue) mod 2 pi >= 0; s = clamp(s_mult * (s + s_shift), 0, 1); v = max(v_mult * (v + v_shift), 0);
+ *                       HSV -> RGB by the six-sector table
+ *   EGR_EDIT_TRANSFORM  p += translate; p = (p - centre) * scale + centre; p = R (p - centre) + centre; normal = R normal; scale_raw += log_scale;
+ *                       rotation = q (x) (rotation / |rotation|), a Hamilton product in (w, x, y, z). R is row-major.
+ *   EGR_EDIT_REMOVED    opacity = -1e8 (what the reference's destructive remove_object leaves; here the raw opacity is untouched)
+ * IN PLACE OR DISJOINT: dst->X may be the very pointer src->X (the work is row-local) or must not touch it; any other overlap - a dst range with another
+ * array's src, with another dst, with the mask or the records - is refused. One launch, asynchronous on the stream, no host synchronisation.
+ *
+ * Both validate BEFORE any HIP call (a NULL output or required input, more than EGR_MAX_EDIT_OBJECTS objects / records, n > 2^26 - the tree's own limit -,
+ * a range flag without its array, partial overlap): non-zero is returned, egr_edit_last_error() says why, nothing was touched. n == 0 returns 0. */
+#define EGR_MAX_EDIT_OBJECTS 32
+#define EGR_EDIT_SEL_CYLINDER 1u
+#define EGR_EDIT_SEL_EVERYTHING 2u
+#define EGR_EDIT_SEL_RANGE_F0 4u
+#define EGR_EDIT_SEL_RANGE_ROUGHNESS 8u
+#define EGR_EDIT_SEL_RANGE_DIFFUSE 16u
+#define EGR_EDIT_SEL_ZRANGE 32u
+#define EGR_EDIT_ROUGHNESS 1u
+#define EGR_EDIT_DIFFUSE 2u
+#define EGR_EDIT_F0 4u
+#define EGR_EDIT_TRANSFORM 8u
+#define EGR_EDIT_REMOVED 16u
+#define EGR_EDIT_ROUGHNESS_OVERRIDE 32u
+typedef struct egr_edit_object {
+    float box_min[3];
+    float box_max[3];
+    float sub_min[3];   /* EGR_EDIT_SEL_ZRANGE: lower corner of the exempt sub-box, box_min + (box_max - box_min) * zrange */
+    float range_lo[3];  /* f0, roughness, diffuse */
+    float range_hi[3];
+    uint32_t flags;     /* EGR_EDIT_SEL_*                                       */
+    uint32_t exclude;   /* bit j: subtract the shape of objects[j]              */
+} egr_edit_object;
+typedef struct egr_edit_colour {
+    float override_rgb[3];
+    float override_w;
+    float hue;          /* pi * hue_shift, radians */
+    float s_shift;
+    float s_mult;
+    float v_shift;
+    float v_mult;
+} egr_edit_colour;
+typedef struct egr_edit_record {
+    uint32_t flags;          /* EGR_EDIT_*: which groups are active          */
+    float roughness_base;    /* override^2                                   */
+    float roughness_shift;   /* |shift|                                      */
+    float roughness_mult;
+    egr_edit_colour diffuse;
+    egr_edit_colour f0;
+    float translate[3];
+    float centre[3];         /* box centre + translate                       */
+    float scale;             /* > 0                                          */
+    float log_scale;         /* log(scale)                                   */
+    float R[9];              /* Rodrigues' rotation, row-major               */
+    float q[4];              /* the same rotation as a quaternion (w, x, y, z) */
+} egr_edit_record;
+typedef struct egr_edit_arrays { /* the export order of gaussian_raytracer.py:41-50 */
+    float *scale;     /* [n][3] raw (log) */
+    float *rotation;  /* [n][4] */
+    float *mean;      /* [n][3] */
+    float *opacity;   /* [n][1] raw */
+    float *rgb;       /* [n][3] */
+    float *normal;    /* [n][3] */
+    float *roughness; /* [n][1] */
+    float *f0;        /* [n][3] */
+} egr_edit_arrays;
+int egr_edit_select(int device, uint32_t n, const float *xyz, const float *f0, const float *roughness, const float *diffuse,
+                    const egr_edit_object *objects, uint32_t num_objects, uint32_t *mask, void *hip_stream);
+int egr_edit_apply(int device, uint32_t n, const egr_edit_arrays *src, const egr_edit_arrays *dst, const uint32_t *mask,
+                   const egr_edit_record *records, uint32_t num_records, void *hip_stream);
+const char *egr_edit_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif
