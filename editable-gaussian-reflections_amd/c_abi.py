@@ -71,6 +71,21 @@ def prune_workspace_bytes(n):
     return ((n + EGR_PRUNE_ROWS_PER_WG - 1) // EGR_PRUNE_ROWS_PER_WG) * (16 * 8 + 4)
 
 
+EGR_EVAL_PIXELS_PER_WG = 2048
+
+
+def eval_workspace_bytes(num_views, height, width):
+    """EGR_EVAL_WORKSPACE_BYTES(V, H, W) of the header: one partial of 9 fp64 sums per workgroup of EGR_EVAL_PIXELS_PER_WG pixels and view."""
+    return num_views * ((height * width + EGR_EVAL_PIXELS_PER_WG - 1) // EGR_EVAL_PIXELS_PER_WG) * (9 * 8)
+
+
+def eval_metrics(num_views, height, width, final, rgb, target_final, target_diffuse, target_specular, sse, psnr, workspace, display=None, device=0, stream=0):
+    """egr_eval_metrics on integer device addresses (include/egr_raytracer.h has the shapes; None = NULL). `workspace`: eval_workspace_bytes() bytes, 8-byte aligned."""
+    L = lib()
+    if L.egr_eval_metrics(device, num_views, height, width, final, rgb, target_final, target_diffuse, target_specular, sse, psnr, display, workspace, C.c_void_p(stream)) != 0:
+        raise RuntimeError(L.egr_eval_last_error().decode())
+
+
 _lib = None
 
 
@@ -119,6 +134,11 @@ def lib(path=None):
         L.egr_edit_apply.argtypes = [C.c_int, C.c_uint32, C.POINTER(egr_edit_arrays), C.POINTER(egr_edit_arrays), P, P, C.c_uint32, P]  # device, n, src, dst, mask, records (device), num_records, stream
         L.egr_edit_last_error.argtypes = []
         L.egr_edit_last_error.restype = C.c_char_p
+        L.egr_denoise_views.argtypes = [P, C.c_uint32, P, P, C.c_size_t, P, P]  # ctx, num_views, final, normal, normal_view_stride (floats), denoised, stream
+        # fused evaluation metrics (csrc/eval.hip): device, V, H, W, final, rgb, target_final, target_diffuse, target_specular, sse, psnr, display, workspace, stream
+        L.egr_eval_metrics.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P, P, P, P, P, P, P]
+        L.egr_eval_last_error.argtypes = []
+        L.egr_eval_last_error.restype = C.c_char_p
         L.egr_last_error.argtypes = [P]
         L.egr_last_error.restype = C.c_char_p
         L.egr_version.restype = C.c_char_p
@@ -191,6 +211,10 @@ class RawRaytracer:
 
     def denoise(self):  # :96
         self._check(self.L.egr_denoise(self.ctx, self.stream))
+
+    def denoise_views(self, num_views, final, normal, normal_view_stride, denoised):
+        """egr_denoise_views: integer device addresses of final [V][H][W][3], the guide (view v at normal + v * normal_view_stride floats) and the output."""
+        self._check(self.L.egr_denoise_views(self.ctx, num_views, final, normal, normal_view_stride, denoised, self.stream))
 
     def counters(self):  # synchronises the stream; the sized call: the library never writes more than THIS mirror of the struct holds
         c = egr_counters()

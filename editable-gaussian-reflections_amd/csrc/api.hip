@@ -12,6 +12,7 @@
 
 void egr_copy_final_to_denoised(egr_context *c, hipStream_t s);
 void egr_denoise_atrous(egr_context *c, hipStream_t s); // denoise.hip
+void egr_denoise_views_atrous(egr_context *c, uint32_t num_views, const float *final, const float *normal, size_t normal_view_stride, float *denoised, hipStream_t s); // denoise.hip
 void egr_export_step_hits(egr_context *c, int32_t *host_out, hipStream_t s); // trace.hip
 void egr_export_hit_hash(egr_context *c, uint64_t *host_out, hipStream_t s); // trace.hip
 void egr_upload_targets(egr_context *c, const float *const chw[6], hipStream_t s); // trace.hip
@@ -127,6 +128,7 @@ void egr_destroy(egr_context *c) {
     (void)hipDeviceSynchronize();
     egr_trace_free(c);
     egr_bvh_free(c);
+    egr_dev_free(c, c->denoise_views_tmp);
     for (auto &k : c->stamps) (void)hipEventDestroy(k.start), (void)hipEventDestroy(k.stop);
     if (c->ev_rt0) (void)hipEventDestroy(c->ev_rt0), (void)hipEventDestroy(c->ev_rt1), (void)hipEventDestroy(c->ev_ub0), (void)hipEventDestroy(c->ev_ub1);
     delete c;
@@ -274,6 +276,28 @@ int egr_denoise(egr_context *c, void *stream) {
     return guarded(c, [&] {
         if (c->denoise_mode == 0) egr_copy_final_to_denoised(c, (hipStream_t)stream); // EGR_DENOISE=0: plain copy
         else egr_denoise_atrous(c, (hipStream_t)stream);
+    });
+}
+
+int egr_denoise_views(egr_context *c, uint32_t num_views, const float *final, const float *normal, size_t normal_view_stride, float *denoised, void *stream) {
+    if (!c) return 1;
+    // ---- validation: before any HIP call
+    const size_t n = (size_t)c->width * c->height * 3;
+    auto refuse = [&](const char *what) {
+        c->last_error = std::string("libegr_hip: egr_denoise_views: ") + what;
+        return 1;
+    };
+    if (num_views == 0 || num_views > 65535u) return refuse("num_views must be in 1..65535");
+    if (!final || !normal || !denoised) return refuse("final, normal and denoised must be non-NULL");
+    if (normal_view_stride < n) return refuse("normal_view_stride is smaller than one image (H * W * 3 floats)");
+    const uintptr_t f0 = (uintptr_t)final, d0 = (uintptr_t)denoised, g0 = (uintptr_t)normal;
+    const size_t bytes = (size_t)num_views * n * sizeof(float), gbytes = ((size_t)(num_views - 1) * normal_view_stride + n) * sizeof(float);
+    if (f0 < d0 + bytes && d0 < f0 + bytes) return refuse("final and denoised overlap: the filter runs out of place");
+    if (g0 < d0 + bytes && d0 < g0 + gbytes) return refuse("normal and denoised overlap: every pass reads the guide");
+    return guarded(c, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        if (c->denoise_mode == 0) EGR_HIP(hipMemcpyAsync(denoised, final, bytes, hipMemcpyDeviceToDevice, s)); // EGR_DENOISE=0: plain copy
+        else egr_denoise_views_atrous(c, num_views, final, normal, normal_view_stride, denoised, s);
     });
 }
 

@@ -17,10 +17,13 @@ namespace {
 constexpr float SIGMA_COLOR = 0.6f;  // colour tolerance of the first pass (halved every pass)
 constexpr float SIGMA_NORMAL = 0.3f; // normal tolerance (all passes)
 
-__global__ void __launch_bounds__(256) k_atrous(int W, int H, int hole, float inv_sc2, float inv_sn2, const float *__restrict__ src,
-                                                const float *__restrict__ normal, float *__restrict__ dst) {
+// One view per blockIdx.z: view v reads src + v * src_stride and normal + v * normal_stride and writes dst + v * dst_stride (strides in floats; the
+// framebuffer's own denoise is the one-view launch with strides 0). The tap arithmetic below is the only statement of the filter.
+__global__ void __launch_bounds__(256) k_atrous(int W, int H, int hole, float inv_sc2, float inv_sn2, const float *__restrict__ src, size_t src_stride,
+                                                const float *__restrict__ normal, size_t normal_stride, float *__restrict__ dst, size_t dst_stride) {
     const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (x >= W || y >= H) return;
+    src += blockIdx.z * src_stride, normal += blockIdx.z * normal_stride, dst += blockIdx.z * dst_stride;
     const size_t p = ((size_t)y * W + x) * 3;
     const float cr = src[p], cg = src[p + 1], cb = src[p + 2];
     const float nx = normal[p], ny = normal[p + 1], nz = normal[p + 2];
@@ -61,7 +64,30 @@ void egr_denoise_atrous(egr_context *c, hipStream_t s) {
     for (int pass = 0; pass < 5; pass++) {
         float *dst = pass == 4 ? c->fb.output_denoised : tmp[pass & 1];
         hipLaunchKernelGGL(k_atrous, grid, block, 0, s, W, H, 1 << pass, 1.0f / (sigma_c * sigma_c), 1.0f / (SIGMA_NORMAL * SIGMA_NORMAL), src,
-                           (const float *)c->fb.output_normal, dst);
+                           (size_t)0, (const float *)c->fb.output_normal, (size_t)0, dst, (size_t)0);
+        src = dst;
+        sigma_c *= 0.5f;
+    }
+}
+
+// egr_denoise_views: the same five passes on the caller's [V][H][W][3] buffers, every view of a pass in one launch. One temporary per view, the context's own
+// (grown on demand): final -> denoised -> tmp -> denoised -> tmp -> denoised.
+void egr_denoise_views_atrous(egr_context *c, uint32_t num_views, const float *final, const float *normal, size_t normal_view_stride, float *denoised, hipStream_t s) {
+    const int W = c->width, H = c->height;
+    const size_t n = (size_t)W * H * 3;
+    if (c->denoise_views_cap < num_views) {
+        egr_dev_free(c, c->denoise_views_tmp); // (hipFree waits for the device: no earlier launch still reads it)
+        c->denoise_views_cap = 0;
+        egr_dev_alloc(c, c->denoise_views_tmp, (size_t)num_views * n);
+        c->denoise_views_cap = num_views;
+    }
+    const float *src = final;
+    const dim3 grid((W + 31) / 32, (H + 7) / 8, num_views), block(256);
+    float sigma_c = SIGMA_COLOR;
+    for (int pass = 0; pass < 5; pass++) {
+        float *dst = (pass & 1) ? c->denoise_views_tmp : denoised;
+        hipLaunchKernelGGL(k_atrous, grid, block, 0, s, W, H, 1 << pass, 1.0f / (sigma_c * sigma_c), 1.0f / (SIGMA_NORMAL * SIGMA_NORMAL), src, n, normal,
+                           normal_view_stride, dst, n);
         src = dst;
         sigma_c *= 0.5f;
     }

@@ -237,6 +237,9 @@ struct egr_context {
     // device memory this context holds (egr_counters::device_bytes): every allocation goes through egr_dev_alloc / egr_dev_free
     std::unordered_map<void *, size_t> alloc_sizes;
     size_t device_bytes = 0;
+    // batched denoise (egr_denoise_views): one W*H*3 ping-pong image per view, grown on demand, freed by egr_destroy
+    float *denoise_views_tmp = nullptr;
+    uint32_t denoise_views_cap = 0; // views it holds
 };
 
 inline void egr_dev_alloc_raw(egr_context *c, void **p, size_t bytes) {

@@ -9,6 +9,7 @@
 //
 // "torch::kCUDA" below is PyTorch's device name for HIP devices on ROCm builds, not a compatibility layer.
 #include <ATen/ATen.h>
+#include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/custom_class.h>
 #include <torch/library.h>
@@ -521,6 +522,25 @@ struct Raytracer : torch::CustomClassHolder {
         }
         check(egr_train_views(ctx, &b, current_stream()), "train_views");
     }
+    // batched denoise (egr_denoise_views): final [V,H,W,3] and its guide normal - render_views' [V,3,H,W,3] buffer (step 0 is the guide) or a packed [V,H,W,3] -
+    // as contiguous fp32 tensors on the tracer's device. Returns a new [V,H,W,3] tensor; each view is bit-equal to denoise() on a framebuffer that holds the same
+    // final / normal. The framebuffer is not touched.
+    Tensor denoise_views(Tensor final, Tensor normal) {
+        const auto dev = framebuffer_data->output_rgb.device();
+        TORCH_CHECK(final.dim() == 4 && final.size(1) == height && final.size(2) == width && final.size(3) == 3, "denoise_views: final must be [V,", height, ",", width, ",3], got ", final.sizes());
+        const int64_t V = final.size(0);
+        const bool steps = normal.dim() == 5;
+        const std::vector<int64_t> want = steps ? std::vector<int64_t>{V, EGR_NUM_STEPS, height, width, 3} : std::vector<int64_t>{V, height, width, 3};
+        TORCH_CHECK(normal.sizes() == torch::IntArrayRef(want), "denoise_views: normal must be [V,3,H,W,3] or [V,H,W,3] with V = ", V, ", got ", normal.sizes());
+        for (const Tensor *t : {&final, &normal})
+            TORCH_CHECK(t->device() == dev && t->scalar_type() == torch::kFloat32 && t->is_contiguous(), "denoise_views: contiguous fp32 tensors on the tracer's device expected");
+        Tensor out = torch::empty_like(final);
+        if (V == 0) return out;
+        check(egr_denoise_views(ctx, (uint32_t)V, final.data_ptr<float>(), normal.data_ptr<float>(), (size_t)((steps ? EGR_NUM_STEPS : 1) * height * width * 3), out.data_ptr<float>(),
+                                current_stream()),
+              "denoise_views");
+        return out;
+    }
     void set_batch_frames(int64_t n) { TORCH_CHECK(n >= 1 && n <= 0x7FFFFFFF && egr_set_batch_frames(ctx, (int)n) == 0, "set_batch_frames: a frame count >= 1 expected"); }
     void set_rays_per_task(int64_t n) { TORCH_CHECK(egr_set_rays_per_task(ctx, (int)n) == 0, "set_rays_per_task: 0 (automatic), 16, 32 or 64 expected"); }
     void set_team_help(bool on) { TORCH_CHECK(egr_set_team_help(ctx, on ? 1 : 0) == 0, "set_team_help failed"); }
@@ -635,6 +655,7 @@ struct Raytracer : torch::CustomClassHolder {
             .def("render_views", &Raytracer::render_views)
             .def("render_views_into", &Raytracer::render_views_into)
             .def("train_views", &Raytracer::train_views)
+            .def("denoise_views", &Raytracer::denoise_views)
             .def("set_batch_frames", &Raytracer::set_batch_frames)
             .def("set_exact_stats", &Raytracer::set_exact_stats)
             .def("set_strands", &Raytracer::set_strands)
@@ -840,6 +861,35 @@ static void edit_apply(std::vector<Tensor> src, std::vector<Tensor> dst, const T
     TORCH_CHECK(rc == 0, egr_edit_last_error());
 }
 
+// Fused evaluation metrics (egr_eval_metrics, csrc/eval.hip): final [V,H,W,3], rgb [V,3,H,W,3] (None when both of its targets are) and the channel-major targets
+// [V,3,H,W] (None: the pass is skipped and reports NaN) as contiguous fp32 GPU tensors. Returns (sse fp64 [V,3,3], psnr fp64 [V,3,2], display fp32 [V,3,2,3,H,W] -
+// or an empty tensor without want_display; a skipped pass reads NaN there) on the device, two launches on the current stream, no host synchronisation.
+static std::tuple<Tensor, Tensor, Tensor> eval_metrics(const Tensor &final, const c10::optional<Tensor> &rgb, const c10::optional<Tensor> &target_final,
+                                                       const c10::optional<Tensor> &target_diffuse, const c10::optional<Tensor> &target_specular, bool want_display) {
+    TORCH_CHECK(final.is_cuda() && final.scalar_type() == torch::kFloat32 && final.is_contiguous() && final.dim() == 4 && final.size(3) == 3, "eval_metrics: final must be a contiguous fp32 [V,H,W,3] GPU tensor");
+    const int64_t V = final.size(0), H = final.size(1), W = final.size(2);
+    TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && H <= 0x7FFFFFFF && W <= 0x7FFFFFFF, "eval_metrics: at least one view and one pixel are required");
+    const auto dev = final.device();
+    const c10::DeviceGuard guard(dev); // the outputs, the workspace and current_stream() belong to final's device, which need not be the current one
+    auto ptr = [&](const c10::optional<Tensor> &t, std::vector<int64_t> want, const char *what) -> const float * {
+        if (!t.has_value() || !t->defined()) return nullptr;
+        TORCH_CHECK(t->is_cuda() && t->device() == dev && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->sizes() == torch::IntArrayRef(want), "eval_metrics: ", what,
+                    " must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " on final's device, got ", t->sizes());
+        return t->data_ptr<float>();
+    };
+    const float *prgb = ptr(rgb, {V, EGR_NUM_STEPS, H, W, 3}, "rgb");
+    const float *tf = ptr(target_final, {V, 3, H, W}, "target_final"), *td = ptr(target_diffuse, {V, 3, H, W}, "target_diffuse"), *ts = ptr(target_specular, {V, 3, H, W}, "target_specular");
+    const auto f64 = torch::dtype(torch::kFloat64).device(dev);
+    Tensor sse = torch::empty({V, 3, 3}, f64), psnr = torch::empty({V, 3, 2}, f64);
+    Tensor display = torch::empty({0}, final.options());
+    if (want_display) display = (tf && td && ts) ? torch::empty({V, 3, 2, 3, H, W}, final.options()) : torch::full({V, 3, 2, 3, H, W}, NAN, final.options());
+    Tensor workspace = torch::empty({(int64_t)(EGR_EVAL_WORKSPACE_BYTES(V, H, W) / 8)}, f64); // (freed stream-ordered by the caching allocator)
+    const int rc = egr_eval_metrics(dev.index(), (uint32_t)V, (uint32_t)H, (uint32_t)W, final.data_ptr<float>(), prgb, tf, td, ts, sse.data_ptr<double>(), psnr.data_ptr<double>(),
+                                    want_display ? display.data_ptr<float>() : nullptr, workspace.data_ptr(), current_stream());
+    TORCH_CHECK(rc == 0, egr_eval_last_error());
+    return {sse, psnr, display};
+}
+
 // unit-test hook (egr_debug_lean_arith): (a / b, sqrt(a)) as the hot kernels' division and square root compute them
 static std::tuple<torch::Tensor, torch::Tensor> debug_lean_arith(const torch::Tensor &a, const torch::Tensor &b) {
     TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.numel() == b.numel(), "debug_lean_arith: two GPU tensors of one size expected");
@@ -861,6 +911,9 @@ TORCH_LIBRARY(egr, m) {
     m.def("prune_gather(Tensor[] src, Tensor src_index, int count) -> Tensor[]", &prune_gather);
     m.def("edit_select(Tensor xyz, Tensor? f0, Tensor? roughness, Tensor? diffuse, Tensor objects) -> Tensor", &edit_select);
     m.def("edit_apply(Tensor[] src, Tensor[] dst, Tensor mask, Tensor records) -> ()", &edit_apply);
+    m.def("eval_metrics(Tensor final, Tensor? rgb, Tensor? target_final, Tensor? target_diffuse, Tensor? target_specular, bool want_display=False) -> "
+          "(Tensor sse, Tensor psnr, Tensor display)",
+          &eval_metrics);
 }
 
 TORCH_LIBRARY(raytracer, m) {

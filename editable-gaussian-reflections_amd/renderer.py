@@ -267,13 +267,9 @@ def _stack_cameras(cameras):
     return R, centers, fovy
 
 
-def render_views(cameras, raytracer: GaussianRaytracer, spp=1, outputs=VIEW_OUTPUTS, force_update_bvh=False, znear=0.01, zfar=999.9):
-    """Batched no-grad render (egr_render_views): every camera of `cameras` with `spp` accumulated samples, in as few launches as the ray
-    state allows. View v equals reset_accumulators() + spp x (`render` of cameras[v] with accumulate_samples = spp > 1) bit for bit when team
-    help is off; the framebuffer is not touched, total_num_calls advances by len(cameras) * spp. Returns one SimpleNamespace per view with the
-    CHW fields of `render` (rgb [3,3,H,W], final [1,3,H,W], depth / roughness [3,1,H,W], normal / f0 [3,3,H,W]); fields not in `outputs`
-    are None. Parameters are exported (and the tree refitted with `force_update_bvh`) as by `GaussianRaytracer.__call__`. A partitioned
-    tracer renders the whole image on the calling rank (eval_mode="full_image")."""
+def render_views_raw(cameras, raytracer: GaussianRaytracer, spp=1, outputs=VIEW_OUTPUTS, force_update_bvh=False, znear=0.01, zfar=999.9):
+    """The launch of `render_views`, returning the batch buffers themselves: dict name -> tensor in the framebuffer's layout with a leading V (final
+    [V,H,W,3], the others [V,3,H,W,c]); "final" is always among them. `evaluation.evaluate_views` feeds them to the batched denoise and the fused metrics."""
     cameras = list(cameras)
     outputs = tuple(outputs)
     if "final" not in outputs:
@@ -289,7 +285,18 @@ def render_views(cameras, raytracer: GaussianRaytracer, spp=1, outputs=VIEW_OUTP
             bufs = m.render_views(R, centers, fovy, float(os.getenv("ZNEAR", znear)), float(os.getenv("ZFAR", zfar)), int(spp), list(outputs))
         finally:
             raytracer._set_full_image(False)
-    got = dict(zip(outputs, bufs))
+    return dict(zip(outputs, bufs))
+
+
+def render_views(cameras, raytracer: GaussianRaytracer, spp=1, outputs=VIEW_OUTPUTS, force_update_bvh=False, znear=0.01, zfar=999.9):
+    """Batched no-grad render (egr_render_views): every camera of `cameras` with `spp` accumulated samples, in as few launches as the ray
+    state allows. View v equals reset_accumulators() + spp x (`render` of cameras[v] with accumulate_samples = spp > 1) bit for bit when team
+    help is off; the framebuffer is not touched, total_num_calls advances by len(cameras) * spp. Returns one SimpleNamespace per view with the
+    CHW fields of `render` (rgb [3,3,H,W], final [1,3,H,W], depth / roughness [3,1,H,W], normal / f0 [3,3,H,W]); fields not in `outputs`
+    are None. Parameters are exported (and the tree refitted with `force_update_bvh`) as by `GaussianRaytracer.__call__`. A partitioned
+    tracer renders the whole image on the calling rank (eval_mode="full_image")."""
+    cameras = list(cameras)
+    got = render_views_raw(cameras, raytracer, spp, outputs, force_update_bvh, znear, zfar)
     views = []
     for v in range(len(cameras)):
         f = lambda k: got[k][v].moveaxis(-1, 1) if k in got else None

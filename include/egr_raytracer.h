@@ -175,6 +175,18 @@ int egr_set_targets_chw(egr_context *ctx, const float *diffuse, const float *spe
  * -> output_denoised). The OptiX AI denoiser is a closed network; the stand-in is an edge-avoiding a-trous wavelet filter with
  * the same inputs and output (csrc/denoise.hip; parity with OptiX is unpinned). Env EGR_DENOISE=0 at creation: plain copy. */
 int egr_denoise(egr_context *ctx, void *hip_stream);
+/* Batched denoise on caller buffers (not in the reference; an additive symbol of library version 0.8, egr_version() is unchanged): the filter of
+ * egr_denoise - five a-trous passes with holes 1 to 16, the same weights - on V images of the context's size, all views of a pass in ONE launch (5 launches
+ * for V views). View v reads final + v * H*W*3 and the guide normal + v * normal_view_stride (in floats: 3*H*W*3 for egr_view_batch.normal, whose step 0 is
+ * the guide; H*W*3 for a packed [V][H][W][3] array) and writes denoised + v * H*W*3. Per pixel the arithmetic is that of egr_denoise, so a view's result is
+ * bit-equal to egr_denoise on a framebuffer that holds the same final / normal. The framebuffer is not touched (output_denoised included). Honours the
+ * context's denoise mode (env EGR_DENOISE=0 at creation: plain copy). The ping-pong memory (one image per view) is the context's own: grown on demand, freed
+ * with the context, counted in egr_counters.device_bytes. Refused BEFORE any HIP call, with an egr_last_error message: num_views == 0 (or > 65535), a NULL
+ * pointer, final or normal overlapping denoised (the filter runs out of place), a stride smaller than one image. Asynchronous on the stream. */
+int egr_denoise_views(egr_context *ctx, uint32_t num_views, const float *final /* [V][H][W][3] */,
+                      const float *normal /* view v's guide = normal + v * normal_view_stride, [H][W][3] */,
+                      size_t normal_view_stride /* in floats; 3*H*W*3 for render_views' normal buffer: the guide is step 0 */,
+                      float *denoised /* [V][H][W][3] */, void *hip_stream);
 
 /* Multi-GPU image partition (not in the reference): this context only traces the 16x16-pixel macro tiles it owns;
  * default rank 0 of 1 = whole image. Ownership: the macro tiles (index m = my * ceil(width / 16) + mx) are sorted along a Z-curve over
@@ -529,6 +541,41 @@ int egr_edit_select(int device, uint32_t n, const float *xyz, const float *f0, c
 int egr_edit_apply(int device, uint32_t n, const egr_edit_arrays *src, const egr_edit_arrays *dst, const uint32_t *mask,
                    const egr_edit_record *records, uint32_t num_records, void *hip_stream);
 const char *egr_edit_last_error(void);
+
+/* ---- Fused evaluation metrics (not in the reference as one call; additive symbols of library version 0.8, egr_version() is unchanged): what train.py:103-134
+ * (training_report) and render.py:216-228 followed by metrics.py do per test view with six tone-mapping chains and three reductions, for V views in TWO
+ * launches (csrc/eval.hip). Context-free like egr_prune_* and egr_edit_*.
+ *
+ * Three passes per view, prediction against ground truth, as the reference defines them:
+ *   0 final     final [V][H][W][3] (the denoised or the plain final image)       against target_final    (original_image)
+ *   1 diffuse   rgb[v][0], rgb = [V][3][H][W][3] per-step radiance               against target_diffuse  (diffuse_image)
+ *   2 specular  rgb[v][1] + rgb[v][2] (one fp32 add: rgb[1:].sum(0))             against target_specular (specular_image)
+ * The targets are channel-major [V][3][H][W]; a pass whose target is NULL is skipped and its results are NaN (rgb may be NULL when both of its passes are).
+ * Both sides go through D(x) = clamp(tonemap(x), 0, 1) with the filmic tonemap of utils/tonemapping.py:1-5: nan_to_num(posinf = 999999999.9) - NaN becomes 0,
+ * -inf the most negative float -, x (6.2 x + 0.5) / (x (6.2 x + 1.7) + 0.06), ** 1.3; every operation rounded to fp32 on its own, as torch evaluates it.
+ * NaN propagates as in torch: NaN -> 0, +inf -> 1, but -inf, 3e38 (inf / inf) and every negative input (a negative quotient under the power) -> NaN, and the
+ * clamp keeps a NaN.
+ * Outputs (device):
+ *   sse     [V][3 passes][3 channels] fp64: the sum over the pixels of ((double)D(pred) - (double)D(gt))^2. A NaN pixel makes its (view, pass, channel) sum NaN
+ *           and no other.
+ *   psnr    [V][3 passes][2] fp64, from sse on the device: [0] = the reference's number, psnr(a, b).mean() of utils/image_utils.py:19-21 on CHW images - a
+ *           per-CHANNEL mse, 20 log10(1 / sqrt(mse_c)), then the mean over the three channels (its view(img.shape[0], -1) quirk kept; +inf for mse 0);
+ *           [1] = 10 log10(1 / mse) over all three channels (torchmetrics' PeakSignalNoiseRatio(data_range = 1) of metrics.py) - on the unquantised floats,
+ *           where metrics.py measures images after a PNG round trip.
+ *   display [V][3 passes][2][3][H][W] fp32 or NULL: D(pred) and D(gt), channel-major - what save_image / format_image receive. A skipped pass is not written.
+ * k_eval_partial (grid: EGR_EVAL_BLOCKS x V workgroups of 256 threads) keeps 9 fp64 sums per thread, reduces them over the wave and the workgroup and stores
+ * one partial per workgroup in `workspace`; k_eval_finish (one workgroup per view) adds the partials in a fixed order. No float atomics, no workgroup waits
+ * for another: the result depends on the inputs alone and is the same bit for bit on every run and rank.
+ * workspace: EGR_EVAL_WORKSPACE_BYTES(V, H, W) bytes of device memory, 8-byte aligned, owned by the caller, free for reuse once the stream has passed the call.
+ * Refused BEFORE any HIP call (non-zero, egr_eval_last_error() says why): V == 0 (or > 65535), H or W == 0, a NULL final / sse / psnr / workspace, a misaligned
+ * workspace, a diffuse or specular target without rgb, an output that overlaps an input or another output. Asynchronous on the stream. */
+#define EGR_EVAL_PIXELS_PER_WG 2048u /* pixels one workgroup of k_eval_partial covers: one partial (9 fp64 sums) of workspace */
+#define EGR_EVAL_BLOCKS(H, W) (((size_t)(H) * (size_t)(W) + EGR_EVAL_PIXELS_PER_WG - 1) / EGR_EVAL_PIXELS_PER_WG)
+#define EGR_EVAL_WORKSPACE_BYTES(V, H, W) ((size_t)(V) * EGR_EVAL_BLOCKS(H, W) * (9 * 8))
+int egr_eval_metrics(int device, uint32_t num_views, uint32_t height, uint32_t width, const float *final, const float *rgb, const float *target_final,
+                     const float *target_diffuse, const float *target_specular, double *sse, double *psnr, float *display, void *workspace,
+                     void *hip_stream);
+const char *egr_eval_last_error(void);
 
 #ifdef __cplusplus
 }
