@@ -86,6 +86,64 @@ def eval_metrics(num_views, height, width, final, rgb, target_final, target_diff
         raise RuntimeError(L.egr_eval_last_error().decode())
 
 
+# the dense-init cloud (csrc/initcloud.hip): a hash table of voxels in three caller-owned device buffers
+EGR_VOXEL_STATUS_WORDS = 8
+EGR_VOXEL_MIN_CAPACITY, EGR_VOXEL_MAX_CAPACITY = 1024, 1 << 31
+EGR_VOXEL_COORD_HALF_RANGE = 1 << 20
+VOXEL_STATUS = ("occupied", "pixels_added", "pixels_dropped", "pixels_without_slot", "largest_count", "rows")  # status[0..5]
+
+
+def voxel_pair_bytes(max_rows):
+    """EGR_VOXEL_PAIR_BYTES(max_rows) of the header: two (int64 key, uint32 slot) arrays, rounded up to 16 bytes."""
+    return (max_rows * 24 + 15) & ~15
+
+
+def voxel_pack_keys(coords):
+    """The table's key of signed voxel coordinates [..., 3] (numpy or anything np.asarray takes): (x + 2^20) << 42 | (y + 2^20) << 21 | (z + 2^20), int64. Its
+    integer order is the lexicographic order of the signed triples. Coordinates outside [-2^20, 2^20) raise."""
+    import numpy as np
+
+    c = np.asarray(coords).astype(np.int64)
+    if c.shape[-1] != 3 or (c.size and (c.min() < -EGR_VOXEL_COORD_HALF_RANGE or c.max() >= EGR_VOXEL_COORD_HALF_RANGE)):
+        raise ValueError("voxel_pack_keys: [..., 3] coordinates in [-2^20, 2^20) are required")
+    b = c + EGR_VOXEL_COORD_HALF_RANGE
+    return (b[..., 0] << 42) | (b[..., 1] << 21) | b[..., 2]
+
+
+def voxel_unpack_keys(keys):
+    """The inverse of voxel_pack_keys: int64 [...] -> int32 [..., 3]."""
+    import numpy as np
+
+    k = np.asarray(keys).astype(np.int64)
+    return (np.stack([k >> 42, (k >> 21) & 0x1FFFFF, k & 0x1FFFFF], axis=-1) - EGR_VOXEL_COORD_HALF_RANGE).astype(np.int32)
+
+
+def voxel_accumulate(keys, acc, status, cap, num_views, height, width, c2w, origin, view_size, depth, colour=None, colour_u8=None, colour_table=None, voxel_scale=400.0,
+                     colour_max=32768.0, positions_out=None, device=0, stream=0):
+    """egr_voxel_accumulate on integer device addresses (include/egr_raytracer.h has the shapes; None = NULL)."""
+    L = lib()
+    if L.egr_voxel_accumulate(device, keys, acc, status, cap, num_views, height, width, c2w, origin, view_size, depth, colour, colour_u8, colour_table, voxel_scale, colour_max,
+                              positions_out, C.c_void_p(stream)) != 0:
+        raise RuntimeError(L.egr_voxel_last_error().decode())
+
+
+def voxel_rehash(keys, acc, status, cap, src_keys, src_acc, src_cap, device=0, stream=0):
+    """egr_voxel_rehash on integer device addresses."""
+    L = lib()
+    if L.egr_voxel_rehash(device, keys, acc, status, cap, src_keys, src_acc, src_cap, C.c_void_p(stream)) != 0:
+        raise RuntimeError(L.egr_voxel_last_error().decode())
+
+
+def voxel_extract(keys, acc, status, cap, min_count, voxel_scale, max_rows, coords, points, colors, counts, workspace, workspace_bytes, device=0, stream=0):
+    """egr_voxel_extract on integer device addresses; `workspace`: egr_voxel_extract_workspace_bytes(device, max_rows) bytes, 16-byte aligned. Synchronises the stream once.
+    Returns (n, largest count)."""
+    L = lib()
+    host = (C.c_uint64 * 2)()
+    if L.egr_voxel_extract(device, keys, acc, status, cap, min_count, voxel_scale, max_rows, coords, points, colors, counts, host, workspace, workspace_bytes, C.c_void_p(stream)) != 0:
+        raise RuntimeError(L.egr_voxel_last_error().decode())
+    return int(host[0]), int(host[1])
+
+
 _lib = None
 
 
@@ -139,6 +197,16 @@ def lib(path=None):
         L.egr_eval_metrics.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P, P, P, P, P, P, P]
         L.egr_eval_last_error.argtypes = []
         L.egr_eval_last_error.restype = C.c_char_p
+        # the dense-init cloud (csrc/initcloud.hip). accumulate: device, keys, acc, status, cap, V, H, W, c2w, origin, view_size, depth, colour, colour_u8, colour_table,
+        # voxel_scale, colour_max, positions_out, stream
+        L.egr_voxel_accumulate.argtypes = [C.c_int, P, P, P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P, P, P, P, C.c_double, C.c_double, P, P]
+        L.egr_voxel_rehash.argtypes = [C.c_int, P, P, P, C.c_uint64, P, P, C.c_uint64, P]  # device, keys, acc, status, cap, src_keys, src_acc, src_cap, stream
+        L.egr_voxel_extract_workspace_bytes.argtypes = [C.c_int, C.c_uint64]
+        L.egr_voxel_extract_workspace_bytes.restype = C.c_size_t
+        # extract: device, keys, acc, status, cap, min_count, voxel_scale, max_rows, coords, points, colors, counts, host_rows_and_largest, workspace, workspace_bytes, stream
+        L.egr_voxel_extract.argtypes = [C.c_int, P, P, P, C.c_uint64, C.c_uint32, C.c_double, C.c_uint64, P, P, P, P, C.POINTER(C.c_uint64 * 2), P, C.c_size_t, P]
+        L.egr_voxel_last_error.argtypes = []
+        L.egr_voxel_last_error.restype = C.c_char_p
         L.egr_last_error.argtypes = [P]
         L.egr_last_error.restype = C.c_char_p
         L.egr_version.restype = C.c_char_p

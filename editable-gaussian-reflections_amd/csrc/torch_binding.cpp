@@ -890,6 +890,80 @@ static std::tuple<Tensor, Tensor, Tensor> eval_metrics(const Tensor &final, cons
     return {sse, psnr, display};
 }
 
+// The dense-init cloud (egr_voxel_*, csrc/initcloud.hip). The table is three caller-owned GPU tensors: keys int64 [cap] (filled with -1), acc int64 [cap,4] and
+// status int64 [8] (zeroed). voxel_accumulate adds V views in one launch: c2w fp64 [V,3,3], origin fp64 [V,3], view_size fp64 [V] (the caller's host fp64 camera
+// set-up, uploaded), depth fp32 [V,H,W], colour fp32 or uint8 [V,H,W,3] (uint8 with the 256-entry fp32 table), positions_out fp64 [V,H,W,3] or None.
+// Current stream, no host synchronisation.
+static void voxel_table_check(const char *fn, const Tensor &keys, const Tensor &acc, const Tensor &status) {
+    TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64 && keys.is_contiguous() && keys.dim() == 1, fn, ": keys must be a contiguous int64 [cap] GPU tensor");
+    TORCH_CHECK(acc.is_cuda() && acc.device() == keys.device() && acc.scalar_type() == torch::kInt64 && acc.is_contiguous() && acc.dim() == 2 && acc.size(0) == keys.size(0) && acc.size(1) == 4,
+                fn, ": acc must be a contiguous int64 [cap,4] tensor on the device of keys");
+    TORCH_CHECK(status.is_cuda() && status.device() == keys.device() && status.scalar_type() == torch::kInt64 && status.is_contiguous() && status.numel() == EGR_VOXEL_STATUS_WORDS,
+                fn, ": status must be a contiguous int64 [", EGR_VOXEL_STATUS_WORDS, "] tensor on the device of keys");
+}
+static void voxel_accumulate(const Tensor &keys, const Tensor &acc, const Tensor &status, const Tensor &c2w, const Tensor &origin, const Tensor &view_size, const Tensor &depth,
+                             const Tensor &colour, const c10::optional<Tensor> &colour_table, double voxel_scale, double colour_max, const c10::optional<Tensor> &positions_out) {
+    voxel_table_check("voxel_accumulate", keys, acc, status);
+    const auto dev = keys.device();
+    const c10::DeviceGuard guard(dev);
+    TORCH_CHECK(depth.is_cuda() && depth.device() == dev && depth.scalar_type() == torch::kFloat32 && depth.is_contiguous() && depth.dim() == 3, "voxel_accumulate: depth must be a contiguous fp32 [V,H,W] tensor on the table's device");
+    const int64_t V = depth.size(0), H = depth.size(1), W = depth.size(2);
+    TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && V <= 65535 && H <= (1 << 20) && W <= (1 << 20), "voxel_accumulate: at least one view and one pixel are required");
+    auto f64 = [&](const Tensor &t, std::vector<int64_t> want, const char *what) -> const double * {
+        TORCH_CHECK(t.is_cuda() && t.device() == dev && t.scalar_type() == torch::kFloat64 && t.is_contiguous() && t.sizes() == torch::IntArrayRef(want), "voxel_accumulate: ", what,
+                    " must be a contiguous fp64 tensor ", torch::IntArrayRef(want), " on the table's device, got ", t.sizes());
+        return t.data_ptr<double>();
+    };
+    const double *pc2w = f64(c2w, {V, 3, 3}, "c2w"), *porigin = f64(origin, {V, 3}, "origin"), *pview = f64(view_size, {V}, "view_size");
+    const bool u8 = colour.scalar_type() == torch::kUInt8;
+    TORCH_CHECK(colour.is_cuda() && colour.device() == dev && (u8 || colour.scalar_type() == torch::kFloat32) && colour.is_contiguous() && colour.sizes() == torch::IntArrayRef({V, H, W, 3}),
+                "voxel_accumulate: colour must be a contiguous fp32 or uint8 [V,H,W,3] tensor on the table's device");
+    const float *table = nullptr;
+    if (u8) {
+        TORCH_CHECK(colour_table.has_value() && colour_table->defined() && colour_table->is_cuda() && colour_table->device() == dev && colour_table->scalar_type() == torch::kFloat32 &&
+                        colour_table->is_contiguous() && colour_table->numel() == 256,
+                    "voxel_accumulate: uint8 colours need colour_table, a contiguous fp32 [256] tensor on the table's device");
+        table = colour_table->data_ptr<float>();
+    }
+    double *pos = nullptr;
+    if (positions_out.has_value() && positions_out->defined()) pos = const_cast<double *>(f64(*positions_out, {V, H, W, 3}, "positions_out"));
+    const int rc = egr_voxel_accumulate(dev.index(), keys.data_ptr<int64_t>(), acc.data_ptr<int64_t>(), status.data_ptr<int64_t>(), (uint64_t)keys.size(0), (uint32_t)V, (uint32_t)H,
+                                        (uint32_t)W, pc2w, porigin, pview, depth.data_ptr<float>(), u8 ? nullptr : colour.data_ptr<float>(), u8 ? colour.data_ptr<uint8_t>() : nullptr,
+                                        table, voxel_scale, colour_max, pos, current_stream());
+    TORCH_CHECK(rc == 0, egr_voxel_last_error());
+}
+// Growth: every occupied slot of (src_keys, src_acc) is inserted into the initialised table (keys, acc); the slots it claims are added to status[0].
+static void voxel_rehash(const Tensor &keys, const Tensor &acc, const Tensor &status, const Tensor &src_keys, const Tensor &src_acc) {
+    voxel_table_check("voxel_rehash", keys, acc, status);
+    voxel_table_check("voxel_rehash", src_keys, src_acc, status);
+    TORCH_CHECK(src_keys.device() == keys.device(), "voxel_rehash: both tables must be on one device");
+    const c10::DeviceGuard guard(keys.device());
+    const int rc = egr_voxel_rehash(keys.device().index(), keys.data_ptr<int64_t>(), acc.data_ptr<int64_t>(), status.data_ptr<int64_t>(), (uint64_t)keys.size(0), src_keys.data_ptr<int64_t>(),
+                                    src_acc.data_ptr<int64_t>(), (uint64_t)src_keys.size(0), current_stream());
+    TORCH_CHECK(rc == 0, egr_voxel_last_error());
+}
+// The voxels with count >= min_count in the order of torch.unique(dim=0): (coords int32 [n,3], points fp32 [n,3], colors fp32 [n,3], counts int32 [n], the largest
+// count of the table). max_rows bounds n (the table's occupied slots always do). ONE host synchronisation: the read-back of n.
+static std::tuple<Tensor, Tensor, Tensor, Tensor, int64_t> voxel_extract(const Tensor &keys, const Tensor &acc, const Tensor &status, int64_t min_count, double voxel_scale, int64_t max_rows) {
+    voxel_table_check("voxel_extract", keys, acc, status);
+    TORCH_CHECK(min_count >= 0 && min_count <= 0xFFFFFFFFll, "voxel_extract: min_count must be in 0..2^32-1");
+    TORCH_CHECK(max_rows >= 1 && max_rows <= keys.size(0), "voxel_extract: max_rows must be in 1..cap");
+    const auto dev = keys.device();
+    const c10::DeviceGuard guard(dev);
+    const auto i32 = torch::dtype(torch::kInt32).device(dev), f32 = torch::dtype(torch::kFloat32).device(dev);
+    Tensor coords = torch::empty({max_rows, 3}, i32), points = torch::empty({max_rows, 3}, f32), colors = torch::empty({max_rows, 3}, f32), counts = torch::empty({max_rows}, i32);
+    const size_t bytes = egr_voxel_extract_workspace_bytes(dev.index(), (uint64_t)max_rows);
+    TORCH_CHECK(bytes != 0, egr_voxel_last_error());
+    Tensor workspace = torch::empty({(int64_t)((bytes + 15) / 16) * 2}, torch::dtype(torch::kInt64).device(dev)); // (the caching allocator aligns to 512 bytes)
+    uint64_t host[2] = {0, 0};
+    const int rc = egr_voxel_extract(dev.index(), keys.data_ptr<int64_t>(), acc.data_ptr<int64_t>(), status.data_ptr<int64_t>(), (uint64_t)keys.size(0), (uint32_t)min_count, voxel_scale,
+                                     (uint64_t)max_rows, coords.data_ptr<int32_t>(), points.data_ptr<float>(), colors.data_ptr<float>(), counts.data_ptr<int32_t>(), host,
+                                     workspace.data_ptr(), (size_t)workspace.numel() * 8, current_stream());
+    TORCH_CHECK(rc == 0, egr_voxel_last_error());
+    const int64_t n = (int64_t)host[0];
+    return {coords.narrow(0, 0, n), points.narrow(0, 0, n), colors.narrow(0, 0, n), counts.narrow(0, 0, n), (int64_t)host[1]};
+}
+
 // unit-test hook (egr_debug_lean_arith): (a / b, sqrt(a)) as the hot kernels' division and square root compute them
 static std::tuple<torch::Tensor, torch::Tensor> debug_lean_arith(const torch::Tensor &a, const torch::Tensor &b) {
     TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.numel() == b.numel(), "debug_lean_arith: two GPU tensors of one size expected");
@@ -914,6 +988,13 @@ TORCH_LIBRARY(egr, m) {
     m.def("eval_metrics(Tensor final, Tensor? rgb, Tensor? target_final, Tensor? target_diffuse, Tensor? target_specular, bool want_display=False) -> "
           "(Tensor sse, Tensor psnr, Tensor display)",
           &eval_metrics);
+    m.def("voxel_accumulate(Tensor keys, Tensor acc, Tensor status, Tensor c2w, Tensor origin, Tensor view_size, Tensor depth, Tensor colour, Tensor? colour_table, "
+          "float voxel_scale, float colour_max, Tensor? positions_out=None) -> ()",
+          &voxel_accumulate);
+    m.def("voxel_rehash(Tensor keys, Tensor acc, Tensor status, Tensor src_keys, Tensor src_acc) -> ()", &voxel_rehash);
+    m.def("voxel_extract(Tensor keys, Tensor acc, Tensor status, int min_count, float voxel_scale, int max_rows) -> "
+          "(Tensor coords, Tensor points, Tensor colors, Tensor counts, int largest_count)",
+          &voxel_extract);
 }
 
 TORCH_LIBRARY(raytracer, m) {

@@ -27,7 +27,8 @@ class GaussianParams:
     with the reference's attribute names). `cfg` carries the nine values pushed into the native config."""
 
     def __init__(self, g, device="cuda", cfg=None):
-        t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32, device=device).contiguous()
+        # numpy arrays, or tensors on any device (initialization.gaussians_from_cloud): copied, never aliased
+        t = lambda a: (a.detach().to(device, torch.float32).clone() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a), dtype=torch.float32, device=device)).contiguous()
         self._xyz, self._opacity, self._scaling, self._rotation = t(g["mean"]), t(g["opacity"]), t(g["scale"]), t(g["rotation"])
         self._diffuse, self._normal, self._roughness, self._f0 = t(g["rgb"]), t(g["normal"]), t(g["roughness"]), t(g["f0"])
         for p in self.parameters():

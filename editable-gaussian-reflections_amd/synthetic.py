@@ -141,3 +141,61 @@ def plus_x_camera(fov=0.6911):
     """Origin at 0 looking along +x with z up."""
     return dict(origin=np.zeros(3, np.float32), c2w=look_at((0, 0, 0), (1, 0, 0)).astype(np.float32), fov=np.float32(fov),
                 znear=np.float32(0.01), zfar=np.float32(999.9))
+
+
+def room_depth(origin, dirs):
+    """Distance along unit rays `dirs` [..., 3] from `origin` (inside the room) to the nearest of the room's six walls and three spheres, in fp64: the
+    analytic depth image of the scene `make_scene` samples."""
+    o = np.asarray(origin, np.float64)
+    d = np.asarray(dirs, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t_wall = np.where(d > 0, (ROOM_HALF - o) / d, np.where(d < 0, (-ROOM_HALF - o) / d, np.inf)).min(axis=-1)
+    t = t_wall
+    for c, r in SPHERES:
+        oc = o - np.asarray(c, np.float64)
+        b = (d * oc).sum(-1)
+        disc = b * b - ((oc * oc).sum() - r * r)
+        root = np.sqrt(np.maximum(disc, 0.0))
+        near = -b - root
+        t = np.where((disc > 0) & (near > 0), np.minimum(t, near), t)
+    return t
+
+
+def room_poses(num_views, step=0.15):
+    """`num_views` camera poses inside the room as (eye [3] fp64, c2w [3,3] fp64 in the convention of `look_at`, vertical fov): the default camera, then moved and
+    turned a little, with other fields of view."""
+    base = default_camera()
+    poses = []
+    for i in range(num_views):
+        eye = base["origin"].astype(np.float64) + np.array([step * (i % 8), -step * 2 / 3 * (i % 8), step / 3 * (i % 8) - 0.05 * (i // 8)])
+        poses.append((eye, look_at(eye, (1.2 - 0.2 * (i % 8), 0.5 + 0.1 * (i % 8), -0.9 + 0.03 * (i // 8))), 0.6911 + 0.07 * (i % 4)))
+    return poses
+
+
+def dataset_pose(eye, c2w):
+    """(R, T) of the reference's CameraInfo for a `look_at` pose: c2w = -R with column 0 negated again, eye = -R @ T."""
+    R = np.concatenate([c2w[:, :1], -c2w[:, 1:]], axis=1)
+    return R, -R.T @ eye
+
+
+def room_camera_infos(num_views, width, height):
+    """`num_views` views of the room (`room_poses`) with the fields of the reference's CameraInfo that prepare_initial_ply.py reads - R [3,3] and T [3] (fp64),
+    FovY, depth_image [H,W,1] fp32 (analytic: `room_depth`), diffuse_image [H,W,3] fp32 (the checker of `make_scene` at the hit point plus a smooth term) -
+    as SimpleNamespace objects. Pure numpy."""
+    from types import SimpleNamespace
+
+    infos = []
+    for eye, c2w, fov in room_poses(num_views):
+        R, T = dataset_pose(eye, c2w)
+        view = math.tan(fov * 0.5)
+        x = (width / height) * view * (2.0 * ((np.arange(width) + 0.5) / width) - 1.0)
+        y = view * (1.0 - 2.0 * ((np.arange(height) + 0.5) / height))
+        cam = np.stack([np.broadcast_to(x[None, :], (height, width)), np.broadcast_to(y[:, None], (height, width)), -np.ones((height, width))], -1)
+        dirs = cam @ c2w.T
+        dirs /= np.linalg.norm(dirs, axis=-1, keepdims=True)
+        depth = room_depth(eye, dirs)
+        hit = eye + dirs * depth[..., None]
+        checker = (np.floor(hit[..., 0] * 2.0 + 1e-6) + np.floor(hit[..., 1] * 2.0 + 1e-6) + np.floor(hit[..., 2] * 2.0 + 1e-6)).astype(np.int64) & 1
+        colour = (np.where(checker[..., None] == 1, 0.8, 0.2) * np.array([1.0, 0.9, 0.8]) + 0.1 * (dirs * 0.5 + 0.5)).astype(np.float32)
+        infos.append(SimpleNamespace(R=R, T=T, FovY=fov, depth_image=depth.astype(np.float32)[..., None], diffuse_image=np.ascontiguousarray(colour)))
+    return infos

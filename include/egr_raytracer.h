@@ -577,6 +577,64 @@ int egr_eval_metrics(int device, uint32_t num_views, uint32_t height, uint32_t w
                      void *hip_stream);
 const char *egr_eval_last_error(void);
 
+/* ---- The dense-init cloud (additive symbols of library version 0.8, egr_version() is unchanged): what prepare_initial_ply.py:52-104 does on the CPU with every
+ * pixel of every view in memory - unproject by the depth image, snap to a voxel of 1 / voxel_scale, average the diffuse colours per voxel, keep the voxels
+ * seen by at least min_count pixels - as a streamed scatter-reduce into a hash table the caller owns (csrc/initcloud.hip). Context-free like egr_prune_*.
+ *
+ * The table is three device buffers: keys int64 [cap] (-1 = empty), acc int64 [cap][4] (count and three colour sums), status int64 [EGR_VOXEL_STATUS_WORDS].
+ * cap is a power of two in EGR_VOXEL_MIN_CAPACITY..EGR_VOXEL_MAX_CAPACITY. The caller initialises it: keys to -1 (all bits set), acc and status to 0.
+ *   key      (x + 2^20) << 42 | (y + 2^20) << 21 | (z + 2^20) for the signed voxel coordinate (x, y, z): non-negative, and its integer order is the
+ *            lexicographic order of the signed triples, the order of torch.unique(dim=0).
+ *   sums     FIXED POINT: every colour component is quantised once, q = llrint((double)c * 2^32), and added as an int64. Integer addition is associative:
+ *            the content of the table depends on the SET of pixels alone - not on the order of the views, the chunking, the capacity, growth or timing. No
+ *            float atomics. The mean is (float)((double)sum / ((double)count * 2^32)). The sums stay inside int64 while count * colour_max < 2^31.
+ *   status   [0] occupied slots, [1] pixels added, [2] pixels dropped, [3] pixels (rehash: of records) that found no slot, and written by egr_voxel_extract:
+ *            [4] the largest count of the table, [5] the number of rows that extraction selected. [6], [7] are reserved.
+ *
+ * egr_voxel_accumulate: V views of H x W pixels in one launch. Per view, computed by the caller in fp64: c2w [V][9] row-major = -R with column 0 negated
+ * again, origin [V][3] = -R T, view_size [V] = tan(FovY / 2) - there is no trigonometry on the device. Per pixel (y, x), in fp64 with every operation rounded
+ * on its own (utils/depth_utils.py:28-63): u = (x + 0.5) / W, v = (y + 0.5) / H, cam = ((W / H) view_size (2u - 1), view_size (1 - 2v), -1),
+ * dir = cam c2w^T / |cam c2w^T|, pos = origin + dir * depth, coord = int32(rint(pos * voxel_scale)) - round half to even, as torch.round. depth is fp32
+ * [V][H][W]. The colour is fp32 [V][H][W][3] as it is (`colour`), or uint8 [V][H][W][3] (`colour_u8`) looked up in the caller's 256-entry fp32
+ * `colour_table` (untonemap(i / 255), prepare_initial_ply.py:72-73): exactly one of the two. positions_out (fp64 [V][H][W][3], NULL in production) receives pos.
+ * A pixel is DROPPED and counted in status[2] when its depth, position or colour is not finite, a coordinate is outside [-2^20, 2^20) voxels, or a colour
+ * component exceeds colour_max in magnitude (the reference would cast an undefined integer or average a NaN). Pixels of depth 0 are kept, as upstream.
+ * Pixels that share a voxel within a workgroup's 16 x 16 tile are combined in LDS first; the global table then sees one 64-bit compare-and-swap on the key and
+ * four 64-bit integer adds per distinct voxel of the tile. Probing is open addressing from a 64-bit mix of the key, BOUNDED by cap: a pixel that finds no slot
+ * is counted in status[3] and otherwise ignored - the kernel never writes outside the table and never spins, whatever the caller does. A caller that keeps
+ * occupied + pixels of the call <= cap / 2 never sees one. One launch, asynchronous on the stream.
+ *
+ * egr_voxel_rehash: inserts every occupied slot of the table (src_keys, src_acc, src_cap) into the table (keys, acc, cap) through the same claim-and-add;
+ * adds the slots it claims to status[0] (the caller zeroes status[0] first when it reuses the old status). Out of place. One launch, asynchronous.
+ *
+ * egr_voxel_extract: the slots with count >= min_count are compacted into (key, slot) pairs (wave-aggregated append), sorted by key with
+ * rocprim::radix_sort_pairs - the slot order depends on timing, the sorted order on the inputs alone - and written in one pass as n rows:
+ *   coords int32 [n][3], points fp32 [n][3] = (float)coord / (float)voxel_scale (an IEEE fp32 division, as coords.float() / voxel_scale upstream),
+ *   colors fp32 [n][3], counts int32 [n] (saturated at 2^31 - 1).
+ * The outputs have room for max_rows rows (<= cap; the occupied slots are always enough). SYNCHRONISES the stream once, to read n and the largest count:
+ * host_rows_and_largest[0] = n, [1] = the largest count (host memory). n > max_rows is an error and writes no row. The table is not modified.
+ * workspace: egr_voxel_extract_workspace_bytes(device, max_rows) bytes of device memory, 16-byte aligned, owned by the caller: EGR_VOXEL_PAIR_BYTES(max_rows)
+ * for the pairs plus what the sort asks for (the query makes HIP calls; it returns 0 on failure).
+ *
+ * The three validate BEFORE any HIP call (non-zero, egr_voxel_last_error() says why, nothing was touched): a NULL or misaligned table, a required pointer
+ * that is NULL, cap not a power of two or out of range, V, H or W == 0, both or neither of colour and colour_u8, colour_u8 without its table, voxel_scale
+ * <= 0 or not finite, colour_max outside (0, 2^30], max_rows == 0 or > cap, a short workspace, an output that overlaps an input or another output. */
+#define EGR_VOXEL_STATUS_WORDS 8
+#define EGR_VOXEL_MIN_CAPACITY 1024ull
+#define EGR_VOXEL_MAX_CAPACITY (1ull << 31)
+#define EGR_VOXEL_COORD_HALF_RANGE (1 << 20) /* coordinates are in [-2^20, 2^20) voxels: +-2621 m at the default voxel_scale of 400 */
+#define EGR_VOXEL_PAIR_BYTES(max_rows) ((((size_t)(max_rows) * 24) + 15) & ~(size_t)15) /* two (int64 key, uint32 slot) arrays: unsorted and sorted */
+int egr_voxel_accumulate(int device, int64_t *keys, int64_t *acc, int64_t *status, uint64_t cap, uint32_t num_views, uint32_t height, uint32_t width,
+                         const double *c2w, const double *origin, const double *view_size, const float *depth, const float *colour, const uint8_t *colour_u8,
+                         const float *colour_table, double voxel_scale, double colour_max, double *positions_out, void *hip_stream);
+int egr_voxel_rehash(int device, int64_t *keys, int64_t *acc, int64_t *status, uint64_t cap, const int64_t *src_keys, const int64_t *src_acc, uint64_t src_cap,
+                     void *hip_stream);
+size_t egr_voxel_extract_workspace_bytes(int device, uint64_t max_rows);
+int egr_voxel_extract(int device, const int64_t *keys, const int64_t *acc, int64_t *status, uint64_t cap, uint32_t min_count, double voxel_scale,
+                      uint64_t max_rows, int32_t *coords, float *points, float *colors, int32_t *counts, uint64_t *host_rows_and_largest, void *workspace,
+                      size_t workspace_bytes, void *hip_stream);
+const char *egr_voxel_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif
