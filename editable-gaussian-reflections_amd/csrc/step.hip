@@ -9,7 +9,7 @@
 // - as ONE launch: blockIdx.y = parameter group, one thread per element (fully coalesced streams, ~0.6 KB per gaussian).
 // The arithmetic follows torch.optim.Adam's default (non-capturable, non-amsgrad, no weight decay) single-tensor path step
 // for step: lerp, mul+addcmul, sqrt / bias_correction2_sqrt + eps, addcdiv with step_size = lr / bias_correction1 (the two
-// bias corrections are evaluated on the host in double like torch does).
+// bias corrections are evaluated on the host in double like torch does). A NaN parameter stays NaN through the clamp in every group, as through Tensor.clamp_.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -43,7 +43,7 @@ __global__ void __launch_bounds__(256) k_fused_step(StepArgs a) {
             p = p - a.step_size[blockIdx.y] * (m / denom); // addcdiv_(exp_avg, denom, value = -step_size)
             G.exp_avg[i] = m, G.exp_avg_sq[i] = v;
         }
-        p = fminf(fmaxf(p, G.clamp_min), G.clamp_max);
+        p = p != p ? p : fminf(fmaxf(p, G.clamp_min), G.clamp_max); // Tensor.clamp_ keeps NaN; fmaxf / fminf alone would return the bound
         G.param[i] = p;
         if (G.rt_param) G.rt_param[i] = p; // export
         if (G.grad) G.grad[i] = 0.0f;

@@ -401,7 +401,8 @@ typedef struct egr_param_group {
     uint32_t step;      /* this group's own 1-based Adam step count; 0: use the `step` argument             */
 } egr_param_group;
 /* `step` is Adam's 1-based step count of THIS update (torch keeps one per parameter tensor: a group whose state was re-created
- * - gaussian_model.py replace_tensor_to_optimizer - passes its own count in egr_param_group.step). Asynchronous on the stream. Returns 0 on success. */
+ * - gaussian_model.py replace_tensor_to_optimizer - passes its own count in egr_param_group.step). Asynchronous on the stream. Returns 0 on success.
+ * A parameter that is or becomes NaN stays NaN in every group: the clamp propagates it like torch's clamp_ (it is neither clamp_min nor -INFINITY afterwards). */
 int egr_fused_adam_step(int device, const egr_param_group *groups, int num_groups, uint32_t n, uint32_t step, double beta1, double beta2,
                         double eps, void *hip_stream);
 const char *egr_fused_step_last_error(void);
