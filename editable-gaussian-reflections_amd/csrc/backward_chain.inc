@@ -26,7 +26,6 @@
     for (int s = lane; s < EGR_GT_STRIDE * EGR_GT_SLOTS; s += EGR_WAVE) gt_vals[s] = 0.0f;
     __syncthreads(); // the kernel's only workgroup barrier (a team's waves run independently from here on)
     const float exp_power = *v.cfg.exp_power;
-    const float eps_scale_grad = *v.cfg.eps_scale_grad;
     const int num_bounces = min(*v.cfg.num_bounces, EGR_MAX_BOUNCES);
     const float view_size = BATCH ? 0.0f : tanf(*v.cam.vertical_fov_radians / 2.0f); // (primary_direction; a batch reads its view's record)
     uint32_t cur_q = blockIdx.x & 7u;
@@ -71,6 +70,6 @@
     if constexpr (TEAM > 1) {
         // no tiles left: this wave takes batches of bounce hits its team mates have queued until all of them are through
         if (lane == 0) atomicAdd(&bteam.done, 1u);
-        records += bwd_team_help<TEAM>(v, exp_power, eps_scale_grad, bteam, gt_vals_all, stage, wv, lane);
+        records += bwd_team_help<TEAM>(v, exp_power, bteam, gt_vals_all, stage, wv, lane);
     }
     if (lane == 0 && records) atomicAdd(v.control + CW_BUCKET_RECORDS, records);

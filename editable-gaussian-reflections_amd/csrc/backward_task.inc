@@ -79,17 +79,17 @@
             T_minus_Ttot = S.ld(SF(step, S_T)) - S.ld(SF(step, S_TTOT));
         }
 
-        // ---- the geometry half of B2 for one PRIMARY hit (trace.hip: hit_geometry_fn): opacity, mean and the six components of Q from the record
+        // ---- the geometry half of B2 for one hit (trace.hip: hit_geometry_fn): opacity, mean and the six components of Q from the record
         // position, the ray, the live (.., opacity, sigma) quarter and dL/dalpha. Independent of the other hits of the ray - the sequential half
         // (suffix sums -> dL/dalpha) is the caller's. (A bounce hit: bounce_batch.)
-        auto hit_geometry = [&](uint32_t pos, const float4 &a2, const f3 &ro, const f3 &rd, float dL_dalpha, auto &gx) { hit_geometry_fn<true>(v, exp_power, eps_scale_grad, pos, a2, ro, rd, dL_dalpha, gx); };
+        auto hit_geometry = [&](uint32_t pos, const float4 &a2, const f3 &ro, const f3 &rd, float dL_dalpha, auto &gx) { hit_geometry_fn(v, exp_power, pos, a2, ro, rd, dL_dalpha, gx); };
 
         // ---- B2 of a BOUNCE step in two passes per chunk of four hit rows. A row of the arena holds the it-th hit of every ray, and rays
         // end at different depths: with one lane per RAY a row costs the full per-hit arithmetic however few rays still have a hit (58 %
         // of the lanes on the bounce steps of the trained-like cloud; half of that again with 8x4-pixel tasks). Only the suffix sums that
         // give dL/dalpha run along the ray; the geometry gradient of a hit (nine tenths of the arithmetic) needs dL/dalpha and nothing
         // else from its neighbours. Pass 1 (lane = ray) walks the chunk's rows newest first and queues (ray, row, dL/dalpha) per hit in
-        // LDS; pass 2 (lane = HIT, 64 at a time whatever ray they belong to) does the geometry and sends the 15 components as wide adds.
+        // LDS; pass 2 (lane = HIT, 64 at a time whatever ray they belong to) does the geometry and sends the 14 components as one wide add.
         if constexpr (!PRIMARY) {
             table_dirty = true;
             bdl[lane] = dL_rgb.x, bdl[EGR_WAVE + lane] = dL_rgb.y, bdl[2 * EGR_WAVE + lane] = dL_rgb.z;
@@ -153,12 +153,12 @@
                             tk = uniform_u32(tk);
                             const uint32_t bi = tk & 0x3FFu;
                             if (bi >= nbatch) break;
-                            records += bounce_batch(v, exp_power, eps_scale_grad, bitems, bdl, bray, bi * (uint32_t)EGR_WAVE, nitems, stage, lane);
+                            records += bounce_batch(v, exp_power, bitems, bdl, bray, bi * (uint32_t)EGR_WAVE, nitems, stage, lane);
                             if (lane == 0) atomicAdd(&bteam.finished[wv], 1u);
                         }
                         while (uniform_u32(lds_peek(&bteam.finished[wv])) < nbatch) __builtin_amdgcn_s_sleep(1); // batches team mates still work on
                     } else {
-                        for (uint32_t bi = 0; bi < nbatch; bi++) records += bounce_batch(v, exp_power, eps_scale_grad, bitems, bdl, bray, bi * (uint32_t)EGR_WAVE, nitems, stage, lane);
+                        for (uint32_t bi = 0; bi < nbatch; bi++) records += bounce_batch(v, exp_power, bitems, bdl, bray, bi * (uint32_t)EGR_WAVE, nitems, stage, lane);
                     }
                     EGR_BWD_SYNC(); // the queue is reused by the next chunk
                 }
@@ -245,21 +245,20 @@
                     EGR_STATS(bt1 = __builtin_amdgcn_s_memtime();)
                     // primary hits go through the wave's LDS table (trace.hip: primary_presum here, primary_table_add below, outside this divergent
                     // block: a full table is emptied by the whole wave). (Bounce tiles are incoherent - an LDS table removed only 25 % of the
-                    // contributions at 15 ds_add_f32 per hit: bounce_batch sends a hit's 15 components straight to the gradient row as one record.)
+                    // contributions at 15 ds_add_f32 per hit: bounce_batch sends a hit's 14 components straight to the gradient row as one record.)
                     dpos = pos;
                     want = primary_presum(pos, gx, lane);
                 }
                 direct = primary_table_add(v, want, dpos, gx, gt_keys, gt_vals, gt_claim, stage, lane, records);
                 EGR_STATS(const unsigned long long bt2 = __builtin_amdgcn_s_memtime(); bt_math += bt1 - bt0; bt_table += bt2 - bt1;)
                 if (__ballot(direct) != 0ull) {
-                    float lo[15];
+                    float lo[EGR_REC0_COMPS], hi[EGR_REC1_COMPS]; // one record per segment of the row, like a flushed slot
 #pragma unroll
-                    for (int c = 0; c < 15; c++) lo[c] = gx[c];
-                    wide_add_wave<REC_PRIMARY_A>(v, direct, dpos, lo, stage);
-                    float hi[15];
+                    for (int c = 0; c < EGR_REC0_COMPS; c++) lo[c] = gx[c];
 #pragma unroll
-                    for (int c = 0; c < 15; c++) hi[c] = (15 + c < EGR_GT_COMPS) ? gx[(15 + c < EGR_GT_COMPS) ? 15 + c : 0] : 0.0f;
-                    wide_add_wave<REC_PRIMARY_Q>(v, direct, dpos, hi, stage);
+                    for (int c = 0; c < EGR_REC1_COMPS; c++) hi[c] = gx[EGR_REC0_COMPS + c];
+                    wide_add_wave<EGR_REC0_CELL>(v, direct, dpos, lo, stage);
+                    wide_add_wave<EGR_REC1_CELL>(v, direct, dpos, hi, stage);
                     records += 2u * (uint32_t)__popcll(__ballot(direct));
                 }
                 EGR_STATS(bt_wide += __builtin_amdgcn_s_memtime() - bt2;)

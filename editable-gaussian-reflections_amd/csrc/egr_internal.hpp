@@ -39,13 +39,14 @@ inline void egr_hip_check(hipError_t e, const char *what) {
 // ---- per-Gaussian records (internal layout in HBM) -----------------------------------------------------
 // inst_w : float4[4N]   64-B test record: rows of W = M^-1 (world->object; snapshot at update/rebuild) + live
 //                       quarter (f0.z, roughness, opacity, sigma) written per launch: one candidate test = one 64-B sector
-// inst_m : float4[4N]   64-B backward record: rows 0-2 = (row of M (object->world; snapshot), exp(scale_a)), row 3 = raw quaternion; read per BOUNCE
-//                       hit and once per gaussian by k_grad_gather (the scale / rotation chain of the primary hits' sum);
+// inst_m : float4[4N]   64-B backward record: rows 0-2 = (row of M (object->world; snapshot), exp(scale_a)), row 3 = raw quaternion; read once per hit
+//                       gaussian by k_grad_gather (the scale / rotation chain of the hits' summed Q), by no hit;
 //                       exp(scale) and the quaternion are LIVE: k_live rewrites them in every grad launch (backward_pass.cu:68-70
 //                       reads them from the parameter tensors), so between an update and the next grad launch the record mixes
 //                       snapshot M rows with the scale / rotation of the last grad launch
-// grad_rows: float[32N] gradient accumulation, one 128-B line per gaussian, zero between launches: 22 gradient components + the six
-//                       components of the primary hits' summed local matrix Q, which k_grad_gather turns into scale / rotation gradients (trace.hip GC_*)
+// grad_rows: float[32N] gradient accumulation, one 128-B line per gaussian, zero between launches, laid out by 64-B segment: cells 0-13 = opacity,
+//                       mean, rgb, weight and the six components of the hits' summed local matrix Q, which k_grad_gather turns into scale / rotation
+//                       gradients; cells 16-22 = normal, f0, roughness (trace.hip GC_*)
 // bsph   : float4[N]    bounding sphere of the ellipsoid (centre xyz, squared radius): 16 B, snapshot like W
 // app    : float4[2N]   live per-launch record: (relu rgb, n.x) (n.y, n.z, f0.x, f0.y)       32 B
 // wnodes : uint4[8*Nw]     8-wide BVH, one 128-B line per node; child slot (16 B):
@@ -81,7 +82,7 @@ struct DeviceView { // everything a kernel needs, passed by value
     const uint32_t *out_of_frame; // != 0: some box carries the -inf / +inf sentinel cells (see qslab_hit)
     float4 *inst_w;             // [n][4] test record: rows 0-2 = W (snapshot), row 3 = live quarter (k_live writes it per launch)
     float4 *inst_m;             // [n][4] backward record: rows 0-2 = (M row (snapshot), exp(scale_a) (live)), row 3 = raw quaternion (live)
-    float *grad_rows;           // [n][32] gradient accumulation rows in record order (one 128-B line per gaussian; 28 floats used: trace.hip GC_*)
+    float *grad_rows;           // [n][32] gradient accumulation rows in record order (one 128-B line per gaussian; 21 floats used: trace.hip GC_*)
     float4 *app;                // [n][2] live appearance (k_live writes it per launch)
     const float4 *bsph;         // [n] bounding sphere of the gaussian's ellipsoid (centre, squared radius; snapshot): the per-ray pre-test of primary tiles
     // per-launch scratch

@@ -720,36 +720,37 @@ template <bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM
 #define EGR_GT_COMPS 21
 #define EGR_GT_STRIDE 21 // floats per table slot ([slot][component], odd stride: lanes on different slots fall on different LDS banks)
 #define EGR_GT_EMPTY 0xFFFFFFFFu
-// cell order of a gradient row (DeviceView::grad_rows; 28 of its 32 floats used) and, cells 0-14, of a BOUNCE hit's wide-add record. A bounce hit adds its
-// finished d_scale / d_rot to GC_SCALE / GC_ROT; a PRIMARY hit leaves those cells alone and adds the six components of its symmetric local matrix Q
-// (hit_geometry_fn) to GC_Q - k_grad_gather applies the scale / rotation chain to their sum, once per gaussian.
-enum : int { GC_OPA = 0, GC_SCALE = 1, GC_MEAN = 4, GC_ROT = 7, GC_RGB = 11, GC_WEIGHT = 14, GC_NORMAL = 15, GC_F0 = 18, GC_ROUGH = 21, GC_Q = 22 };
-// component order of a PRIMARY hit: the LDS table and the two records a slot (or a hit without a slot) leaves as - A = components 0-14, B = Q (15-20: xx xy xz yy yz zz)
-enum : int { PC_OPA = 0, PC_MEAN = 1, PC_RGB = 4, PC_WEIGHT = 7, PC_NORMAL = 8, PC_F0 = 11, PC_ROUGH = 14, PC_Q = 15 };
-// which cells of the gradient row the 15 values of a record go to
-enum : int { REC_BOUNCE = 0, REC_PRIMARY_A = 1, REC_PRIMARY_Q = 2 };
+// cell order of a gradient row (DeviceView::grad_rows; 21 of its 32 floats used), laid out by 64-B SEGMENT: the L2 retires atomic requests per 64-B segment,
+// so every record falls into one. Segment 0 (cells 0-13) is what EVERY hit adds to - opacity, mean, rgb, weight and the six components of its symmetric local
+// matrix Q (hit_geometry_fn) - and is the whole record of a BOUNCE hit; segment 1 (cells 16-22) holds what only a primary hit has. No hit writes a scale or
+// rotation gradient: k_grad_gather applies the scale / rotation chain to the summed Q, once per gaussian.
+enum : int { GC_OPA = 0, GC_MEAN = 1, GC_RGB = 4, GC_WEIGHT = 7, GC_Q = 8, GC_NORMAL = 16, GC_F0 = 19, GC_ROUGH = 22 };
+// component order of a PRIMARY hit (the LDS table): components 0-13 are segment 0 cell for cell (Q: xx xy xz yy yz zz), components 14-20 go to segment 1
+enum : int { PC_OPA = 0, PC_MEAN = 1, PC_RGB = 4, PC_WEIGHT = 7, PC_Q = 8, PC_NORMAL = 14, PC_F0 = 17, PC_ROUGH = 20 };
+// the two records: (first row cell, components). A bounce hit is one REC0; a flushed table slot or a primary hit without a slot is one REC0 and one REC1.
+#define EGR_REC0_CELL 0
+#define EGR_REC0_COMPS 14
+#define EGR_REC1_CELL 16
+#define EGR_REC1_COMPS 7
+static_assert(EGR_REC0_COMPS + EGR_REC1_COMPS == EGR_GT_COMPS && PC_NORMAL == EGR_REC0_COMPS && GC_NORMAL == EGR_REC1_CELL, "the table's components are the two records, in order");
 #define EGR_ROW_STRIDE 32 // floats per gradient row: one 128-B line per gaussian
 #define EGR_BWD_SYNC() wave_sync() // the backward chain's waves run independently (like the forward's): phases that exchange data through LDS within ONE wave need no more than program order
 
-// SIXTEEN LANES PER RECORD add the 15 values of every lane with `ok` to the cells of its gaussian's gradient row that REC names - one 64-B atomic request per record, nothing returned, so the requests drain behind the wave's arithmetic
-// (a lane adding its own 15 values issues 15 x 64 scattered 4-B requests per instruction row; the earlier record paths -
+// SIXTEEN LANES PER RECORD add the N values of every lane with `ok` to the cells CELL .. CELL + N - 1 of its gaussian's gradient row - one 64-B atomic request per record, nothing returned, so the requests drain behind the wave's arithmetic
+// (a lane adding its own N values issues N x 64 scattered 4-B requests per instruction row; the earlier record paths -
 // per-block buckets + counting-sort reduce, per-wave record logs + an apply kernel - are measured in DESIGN.md 4 and gone).
 // Wave-uniform call; `stage` = 64 x 4 float4.
-template <int REC> EGR_DI void wide_add_wave(const DeviceView &v, bool ok, uint32_t pos, const float (&r)[15], float4 *stage) {
+template <int CELL, int N> EGR_DI void wide_add_wave(const DeviceView &v, bool ok, uint32_t pos, const float (&r)[N], float4 *stage) {
+    static_assert(N >= 1 && N <= 15, "a record is its row index and up to 15 values: 16 lanes");
+    static_assert(CELL >= 0 && CELL / 16 == (CELL + N - 1) / 16 && CELL + N <= EGR_ROW_STRIDE, "a record's cells lie in ONE 64-B segment of the row");
     const int lane = threadIdx.x & (EGR_WAVE - 1);
-    uint32_t cell = 0u; // the row cell of this lane's component (lane & 15) - 1
-    if constexpr (REC == REC_PRIMARY_A) { // record A is not contiguous in the row: the lane picks its cell from the compile-time map (fifteen selects, once per call)
-        constexpr int cells[15] = {GC_OPA, GC_MEAN, GC_MEAN + 1, GC_MEAN + 2, GC_RGB, GC_RGB + 1, GC_RGB + 2, GC_WEIGHT, GC_NORMAL, GC_NORMAL + 1, GC_NORMAL + 2, GC_F0, GC_F0 + 1, GC_F0 + 2, GC_ROUGH};
-#pragma unroll
-        for (int i = 0; i < 15; i++) cell = (lane & 15) == i + 1 ? (uint32_t)cells[i] : cell;
-    } else {
-        cell = (REC == REC_PRIMARY_Q ? (uint32_t)GC_Q : 0u) + (uint32_t)((lane & 15) - 1); // contiguous
-    }
+    const uint32_t cell = (uint32_t)CELL + (uint32_t)((lane & 15) - 1); // the row cell of this lane's component (lane & 15) - 1
     if (ok) {
-        stage[4 * lane + 0] = make_float4(u2f(pos), r[0], r[1], r[2]);
-        stage[4 * lane + 1] = make_float4(r[3], r[4], r[5], r[6]);
-        stage[4 * lane + 2] = make_float4(r[7], r[8], r[9], r[10]);
-        stage[4 * lane + 3] = make_float4(r[11], r[12], r[13], r[14]);
+        auto rv = [&](int i) { return i < N ? r[i < N ? i : 0] : 0.0f; };
+        stage[4 * lane + 0] = make_float4(u2f(pos), rv(0), rv(1), rv(2));
+        if (N > 3) stage[4 * lane + 1] = make_float4(rv(3), rv(4), rv(5), rv(6));
+        if (N > 7) stage[4 * lane + 2] = make_float4(rv(7), rv(8), rv(9), rv(10));
+        if (N > 11) stage[4 * lane + 3] = make_float4(rv(11), rv(12), rv(13), rv(14));
     }
     const unsigned long long okm = __ballot(ok);
     EGR_BWD_SYNC();
@@ -760,12 +761,12 @@ template <int REC> EGR_DI void wide_add_wave(const DeviceView &v, bool ok, uint3
         if (((okm >> (4 * pass)) & 0xFull) == 0ull) continue; // wave-uniform: none of these four records exists
         const float x = sf[16 * src + c];
         const uint32_t p = f2u(sf[16 * src]);
-        if (((okm >> src) & 1ull) && c != 0 && (REC != REC_PRIMARY_Q || c <= 6) && x != 0.0f) atomicAdd(v.grad_rows + (size_t)p * EGR_ROW_STRIDE + cell, x);
+        if (((okm >> src) & 1ull) && c != 0 && c <= N && x != 0.0f) atomicAdd(v.grad_rows + (size_t)p * EGR_ROW_STRIDE + cell, x); // (c > N: a stale stage word)
     }
     EGR_BWD_SYNC();
 }
 
-// Flush of the primary step's LDS table: every used slot leaves as two 16-lane records (components 0-14 and the six of Q).
+// Flush of the primary step's LDS table: every used slot leaves as two 16-lane records, one per segment of its row (components 0-13 and 14-20).
 EGR_DI uint32_t grad_table_flush(const DeviceView &v, uint32_t *gt_keys, float *gt_vals, float4 *stage, int lane) {
     uint32_t sent = 0u; // records (two per used slot)
     EGR_BWD_SYNC();
@@ -775,23 +776,20 @@ EGR_DI uint32_t grad_table_flush(const DeviceView &v, uint32_t *gt_keys, float *
         const uint32_t pos = in_table ? gt_keys[s] : EGR_GT_EMPTY;
         const bool valid = pos != EGR_GT_EMPTY;
         if (in_table) gt_keys[s] = EGR_GT_EMPTY;
-        float lo[15], hi[15];
+        float lo[EGR_REC0_COMPS], hi[EGR_REC1_COMPS];
 #pragma unroll
-        for (int c = 0; c < 15; c++) {
+        for (int c = 0; c < EGR_REC0_COMPS; c++) {
             lo[c] = valid ? gt_vals[s * EGR_GT_STRIDE + c] : 0.0f;
             if (valid) gt_vals[s * EGR_GT_STRIDE + c] = 0.0f; // (an unused slot holds zeros already)
         }
 #pragma unroll
-        for (int c = 0; c < 15; c++) {
-            hi[c] = 0.0f;
-            if (15 + c < EGR_GT_COMPS) {
-                hi[c] = valid ? gt_vals[s * EGR_GT_STRIDE + 15 + c] : 0.0f;
-                if (valid) gt_vals[s * EGR_GT_STRIDE + 15 + c] = 0.0f;
-            }
+        for (int c = 0; c < EGR_REC1_COMPS; c++) {
+            hi[c] = valid ? gt_vals[s * EGR_GT_STRIDE + EGR_REC0_COMPS + c] : 0.0f;
+            if (valid) gt_vals[s * EGR_GT_STRIDE + EGR_REC0_COMPS + c] = 0.0f;
         }
         if (__ballot(valid) == 0ull) continue;
-        wide_add_wave<REC_PRIMARY_A>(v, valid, pos, lo, stage);
-        wide_add_wave<REC_PRIMARY_Q>(v, valid, pos, hi, stage);
+        wide_add_wave<EGR_REC0_CELL>(v, valid, pos, lo, stage);
+        wide_add_wave<EGR_REC1_CELL>(v, valid, pos, hi, stage);
         sent += 2u * (uint32_t)__popcll(__ballot(valid));
     }
     EGR_BWD_SYNC();
@@ -886,75 +884,54 @@ EGR_DI bool primary_table_add(const DeviceView &v, const bool want, const uint32
 
 // ---- the scale / rotation chain (backward_pass.cu:170-205, activations.cu:66-73): d_scale and d_rot from L = (dl2w_0, dl2w_1, dl2w_2), the gradient with
 // respect to the rows of the object->world matrix, and the gaussian's backward record (rows of M with exp(scale) in .w, raw quaternion). LINEAR in L with
-// coefficients that belong to the gaussian alone: a bounce hit applies it to its own dl2w (bounce_batch, T = float), for the primary hits of a launch
-// k_grad_gather applies it to the sum (rebuilt from the summed Q of the gradient row, T = double). The one copy of the formula.
-// Why double there: d_rot is what the projection along q leaves of dL/dq, a small difference of large terms. Per hit the rounding errors of that
+// coefficients that belong to the gaussian alone: k_grad_gather applies it once per gaussian to the sum over all hits of a launch, primary and bounce
+// (rebuilt from the summed Q of the gradient row). The one copy of the formula.
+// Why double: d_rot is what the projection along q leaves of dL/dq, a small difference of large terms. Per hit the rounding errors of that
 // difference average out over the hits of a gaussian; applied ONCE to the sum in fp32 the error of the one evaluation stays (measured: up to 2.8 x the
 // fp32 reference's distance from the fp64 one, tests/test_hip_gradient_terms.py). One evaluation per gaussian is cheap enough to do in fp64.
-template <class T> EGR_DI T chain_rcp(T b) {
-    if constexpr (sizeof(T) == sizeof(float)) return egr_rcp_refined(b);
-    else return T(1) / b;
-}
-template <class T> EGR_DI T chain_div(T a, T b, T r) { // a / b, r = chain_rcp(b)
-    if constexpr (sizeof(T) == sizeof(float)) return egr_div_rn(a, b, r);
-    else return a / b;
-}
-template <class T> EGR_DI T chain_sqrt(T x) {
-    if constexpr (sizeof(T) == sizeof(float)) return egr_sqrt_rn(x);
-    else return sqrt(x);
-}
-template <class T> struct ChainVec { T x, y, z; }; // (f3 is float only)
-template <class T> EGR_DI void scale_rot_chain(const float4 &M0, const float4 &M1, const float4 &M2, const float4 &qu, const float sigma, const float eps, const ChainVec<T> &dl2w0,
-                                               const ChainVec<T> &dl2w1, const ChainVec<T> &dl2w2, T (&d_scale)[3], T (&d_rot)[4]) {
+struct ChainVec { double x, y, z; }; // (f3 is float only)
+EGR_DI void scale_rot_chain(const float4 &M0, const float4 &M1, const float4 &M2, const float4 &qu, const float sigma, const float eps, const ChainVec &dl2w0, const ChainVec &dl2w1,
+                            const ChainVec &dl2w2, double (&d_scale)[3], double (&d_rot)[4]) {
+    using T = double;
     const T scaling_factor = sigma, eps_scale_grad = eps;
-    const ChainVec<T> scaling = {T(M0.w), T(M1.w), T(M2.w)}; // exp(scale), stored by k_instances
-    const ChainVec<T> den = {scaling.x * scaling_factor + eps_scale_grad, scaling.y * scaling_factor + eps_scale_grad, scaling.z * scaling_factor + eps_scale_grad};
-    // (nine quotients over three denominators, further down four over |q| and two reciprocals: each denominator's reciprocal is refined once and every
-    // quotient corrected from it - egr_div_rn, the results of `/` - instead of seventeen full expansions of a division)
-    const ChainVec<T> rden = {chain_rcp(den.x), chain_rcp(den.y), chain_rcp(den.z)};
-    auto div3 = [&](const float4 &m) { return ChainVec<T>{chain_div(T(m.x), den.x, rden.x), chain_div(T(m.y), den.y, rden.y), chain_div(T(m.z), den.z, rden.z)}; };
-    const ChainVec<T> rot_0 = div3(M0), rot_1 = div3(M1), rot_2 = div3(M2); // :178-180
+    const ChainVec scaling = {T(M0.w), T(M1.w), T(M2.w)}; // exp(scale), stored by k_instances
+    const ChainVec den = {scaling.x * scaling_factor + eps_scale_grad, scaling.y * scaling_factor + eps_scale_grad, scaling.z * scaling_factor + eps_scale_grad};
+    auto div3 = [&](const float4 &m) { return ChainVec{T(m.x) / den.x, T(m.y) / den.y, T(m.z) / den.z}; };
+    const ChainVec rot_0 = div3(M0), rot_1 = div3(M1), rot_2 = div3(M2); // :178-180
     d_scale[0] = (dl2w0.x * rot_0.x + dl2w1.x * rot_1.x + dl2w2.x * rot_2.x) * scaling.x; // :181-182
     d_scale[1] = (dl2w0.y * rot_0.y + dl2w1.y * rot_1.y + dl2w2.y * rot_2.y) * scaling.y;
     d_scale[2] = (dl2w0.z * rot_0.z + dl2w1.z * rot_1.z + dl2w2.z * rot_2.z) * scaling.z;
-    auto mul3 = [](const ChainVec<T> &a, const ChainVec<T> &b) { return ChainVec<T>{a.x * b.x, a.y * b.y, a.z * b.z}; };
-    const ChainVec<T> dr0 = mul3(dl2w0, scaling), dr1 = mul3(dl2w1, scaling), dr2 = mul3(dl2w2, scaling); // :185-187
+    auto mul3 = [](const ChainVec &a, const ChainVec &b) { return ChainVec{a.x * b.x, a.y * b.y, a.z * b.z}; };
+    const ChainVec dr0 = mul3(dl2w0, scaling), dr1 = mul3(dl2w1, scaling), dr2 = mul3(dl2w2, scaling); // :185-187
     const T qr = qu.x, qx = qu.y, qy = qu.z, qz = qu.w;
-    const T qn = chain_sqrt(qr * qr + qx * qx + qy * qy + qz * qz);
-    const T rqn = chain_rcp(qn);
-    const T r = chain_div(qr, qn, rqn), x = chain_div(qx, qn, rqn), y = chain_div(qy, qn, rqn), z = chain_div(qz, qn, rqn); // activations.cu:66-69
+    const T qn = sqrt(qr * qr + qx * qx + qy * qy + qz * qz);
+    const T r = qr / qn, x = qx / qn, y = qy / qn, z = qz / qn; // activations.cu:66-69
     const T dL_dr = T(2) * x * (dr2.y - dr1.z) + T(2) * y * (dr0.z - dr2.x) + T(2) * z * (dr1.x - dr0.y); // :194-205
     const T dL_dx = T(-4) * x * (dr1.y + dr2.z) + T(2) * y * (dr0.y + dr1.x) + T(2) * z * (dr0.z + dr2.x) + T(2) * r * (dr2.y - dr1.z);
     const T dL_dy = T(2) * x * (dr0.y + dr1.x) - T(4) * y * (dr0.x + dr2.z) + T(2) * z * (dr1.z + dr2.y) + T(2) * r * (dr0.z - dr2.x);
     const T dL_dz = T(2) * x * (dr0.z + dr2.x) + T(2) * y * (dr1.z + dr2.y) - T(4) * z * (dr0.x + dr1.y) + T(2) * r * (dr1.x - dr0.y);
     const T dd = dL_dr * qr + dL_dx * qx + dL_dy * qy + dL_dz * qz; // activations.cu:71-73
     const T qn3 = qn * qn * qn;
-    const T inv3 = chain_div(T(1), qn3, chain_rcp(qn3)), inv1 = chain_div(T(1), qn, rqn);
+    const T inv3 = T(1) / qn3, inv1 = T(1) / qn;
     d_rot[0] = dd * -qr * inv3 + dL_dr * inv1, d_rot[1] = dd * -qx * inv3 + dL_dx * inv1;
     d_rot[2] = dd * -qy * inv3 + dL_dy * inv1, d_rot[3] = dd * -qz * inv3 + dL_dz * inv1;
 }
 
-// ---- the geometry half of B2 for one hit (backward_pass.cu:151-205) from the record position, the ray, the live (.., opacity, sigma) quarter and
+// ---- the geometry half of B2 for one hit (backward_pass.cu:151-167) from the record position, the ray, the live (.., opacity, sigma) quarter and
 // dL/dalpha. Independent of the other hits of the ray - the sequential half (suffix sums -> dL/dalpha) is the caller's.
-// Here the two kinds of hit part:
-//  PRIMARY_HIT  stops after d_mean and returns opacity, mean and six numbers (PC_* order): the scale / rotation chain depends on the gaussian alone and
-//               is linear in dl2w, so it is applied once per gaussian to the launch's sum (k_grad_gather) - no fetch of the backward record (inst_m),
-//               no denominators, quotients or quaternion arithmetic in the hit row. What is summed is not dl2w itself but the LOCAL matrix
-//               Q = (-dL_dx_local * sigma) (x) local_hit, with dl2w_i = sum_k W_k,i * Q_k (W: the gaussian's world->object rows): dL_dx_local is a
-//               multiple of local_hit, so Q is symmetric - six components instead of nine - and a rounding error of the SUM is symmetric too.
-//               That matters: the rotation gradient is what is left of dl2w when its symmetric part cancels (nothing, for an isotropic gaussian),
-//               and a sum of the nine dl2w components carries an unsymmetric error of eps x sum |dl2w| into that difference (measured on a
-//               near-isotropic cloud, HIP's distance from the fp64 reference over the fp32 reference's, per loss term: 1.24-2.8 with dl2w summed
-//               and the chain in fp32; with Q and the chain in fp64 - scale_rot_chain - 0.33-0.95, as with the per-hit chain).
-//  bounce hit   runs the chain itself and returns the finished components 0 .. 10 (opacity, scale, mean, rotation; GC_* order): its 15 components are ONE
-//               64-B record; with L there would be 17, i.e. a second atomic record per bounce hit, and the record rate is the nearest ceiling of the
-//               bounce-heavy (trained-like) backward chain.
-template <bool PRIMARY_HIT, class GX> EGR_DI void hit_geometry_fn(const DeviceView &v, const float exp_power, const float eps_scale_grad, uint32_t pos, const float4 &a2, const f3 &ro, const f3 &rd, float dL_dalpha, GX &gx) {
+// Every hit, primary or bounce, stops after d_mean and returns opacity, mean and six numbers (PC_* order = GC_* order: segment 0 of the row): the scale /
+// rotation chain (:170-205) depends on the gaussian alone and is linear in dl2w, so it is applied once per gaussian to the launch's sum (k_grad_gather) -
+// no fetch of the backward record (inst_m), no denominators, quotients or quaternion arithmetic per hit. What is summed is not dl2w itself but the LOCAL
+// matrix Q = (-dL_dx_local * sigma) (x) local_hit, with dl2w_i = sum_k W_k,i * Q_k (W: the gaussian's world->object rows): dL_dx_local is a multiple of
+// local_hit, so Q is symmetric - six components instead of nine - and a rounding error of the SUM is symmetric too. That matters: the rotation gradient is
+// what is left of dl2w when its symmetric part cancels (nothing, for an isotropic gaussian), and a sum of the nine dl2w components carries an unsymmetric
+// error of eps x sum |dl2w| into that difference (measured on a near-isotropic cloud, HIP's distance from the fp64 reference over the fp32 reference's, per
+// loss term: 1.24-2.8 with dl2w summed and the chain in fp32; with Q and the chain in fp64 - scale_rot_chain - 0.33-0.95, as with the per-hit chain).
+// With Q a bounce hit is 14 values (geometry 8 + 6, rgb 3, weight): still ONE 64-B record, because Q sits in segment 0 of the row.
+template <class GX> EGR_DI void hit_geometry_fn(const DeviceView &v, const float exp_power, uint32_t pos, const float4 &a2, const f3 &ro, const f3 &rd, float dL_dalpha, GX &gx) {
     const float opacity = a2.z, scaling_factor = a2.w;
     // recompute the local hit exactly as the forward did
     const float4 W0 = v.inst_w[4 * pos], W1 = v.inst_w[4 * pos + 1], W2 = v.inst_w[4 * pos + 2];
-    float4 M0, M1, M2, qu;
-    if constexpr (!PRIMARY_HIT) M0 = v.inst_m[4 * pos], M1 = v.inst_m[4 * pos + 1], M2 = v.inst_m[4 * pos + 2], qu = v.inst_m[4 * pos + 3]; // (requested with W: left where they are used, the compiler issues them ~ 500 instructions later and the row waits a second time)
     f3 lo, ld, dhat, u;
     float t_unused;
     bool behind_unused, outside_unused;
@@ -971,45 +948,36 @@ template <bool PRIMARY_HIT, class GX> EGR_DI void hit_geometry_fn(const DeviceVi
     const f3 dL_dx_world = mk3(dot(mk3(W0.x, W1.x, W2.x), dL_dx_local), dot(mk3(W0.y, W1.y, W2.y), dL_dx_local),
                                dot(mk3(W0.z, W1.z, W2.z), dL_dx_local)) * scaling_factor; // :161-167
     const f3 d_mean = -dL_dx_world;
-    if constexpr (PRIMARY_HIT) {
-        gx[PC_OPA] = d_opacity, gx[PC_MEAN] = d_mean.x, gx[PC_MEAN + 1] = d_mean.y, gx[PC_MEAN + 2] = d_mean.z;
-        const f3 ql = -dL_dx_local * scaling_factor;
-        gx[PC_Q] = ql.x * local_hit.x, gx[PC_Q + 1] = ql.x * local_hit.y, gx[PC_Q + 2] = ql.x * local_hit.z;
-        gx[PC_Q + 3] = ql.y * local_hit.y, gx[PC_Q + 4] = ql.y * local_hit.z, gx[PC_Q + 5] = ql.z * local_hit.z;
-    } else {
-        const f3 dl2w0 = -dL_dx_world.x * local_hit, dl2w1 = -dL_dx_world.y * local_hit, dl2w2 = -dL_dx_world.z * local_hit;
-        float d_scale[3], d_rot[4];
-        scale_rot_chain<float>(M0, M1, M2, qu, scaling_factor, eps_scale_grad, {dl2w0.x, dl2w0.y, dl2w0.z}, {dl2w1.x, dl2w1.y, dl2w1.z}, {dl2w2.x, dl2w2.y, dl2w2.z}, d_scale, d_rot);
-        gx[GC_OPA] = d_opacity, gx[GC_SCALE] = d_scale[0], gx[GC_SCALE + 1] = d_scale[1], gx[GC_SCALE + 2] = d_scale[2];
-        gx[GC_MEAN] = d_mean.x, gx[GC_MEAN + 1] = d_mean.y, gx[GC_MEAN + 2] = d_mean.z;
-        gx[GC_ROT] = d_rot[0], gx[GC_ROT + 1] = d_rot[1], gx[GC_ROT + 2] = d_rot[2], gx[GC_ROT + 3] = d_rot[3];
-    }
+    gx[PC_OPA] = d_opacity, gx[PC_MEAN] = d_mean.x, gx[PC_MEAN + 1] = d_mean.y, gx[PC_MEAN + 2] = d_mean.z;
+    const f3 ql = -dL_dx_local * scaling_factor;
+    gx[PC_Q] = ql.x * local_hit.x, gx[PC_Q + 1] = ql.x * local_hit.y, gx[PC_Q + 2] = ql.x * local_hit.z;
+    gx[PC_Q + 3] = ql.y * local_hit.y, gx[PC_Q + 4] = ql.y * local_hit.z, gx[PC_Q + 5] = ql.z * local_hit.z;
 }
 
 // One batch of 64 hits of a bounce step's queue (backward_task.inc: pass 2), lane = hit: the geometry gradient from the hit's record index, the
-// ray and dL/dalpha, the radiance part from the ray's dL/drgb, all 15 components out as one record. Queue, rays and radiance gradients are the
-// LDS of the wave that OWNS the tile; `stage` is the executing wave's. Returns the records sent.
-EGR_DI uint32_t bounce_batch(const DeviceView &v, const float exp_power, const float eps_scale_grad, const uint4 *bitems, const float *bdl, const float *bray, uint32_t i0, uint32_t nitems,
-                             float4 *stage, int lane) {
+// ray and dL/dalpha, the radiance part from the ray's dL/drgb, all 14 components (segment 0 of the row) out as one record. Queue, rays and radiance
+// gradients are the LDS of the wave that OWNS the tile; `stage` is the executing wave's. Returns the records sent.
+EGR_DI uint32_t bounce_batch(const DeviceView &v, const float exp_power, const uint4 *bitems, const float *bdl, const float *bray, uint32_t i0, uint32_t nitems, float4 *stage, int lane) {
+    static_assert(PC_OPA == GC_OPA && PC_MEAN == GC_MEAN && PC_RGB == GC_RGB && PC_WEIGHT == GC_WEIGHT && PC_Q == GC_Q && GC_Q + 6 == EGR_REC0_COMPS, "components 0-13 of a hit are segment 0 of the row");
     const bool valid = i0 + (uint32_t)lane < nitems;
     uint32_t dpos = 0;
-    float gx[15];
+    float gx[EGR_REC0_COMPS];
 #pragma unroll
-    for (int c = 0; c < 15; c++) gx[c] = 0.0f;
+    for (int c = 0; c < EGR_REC0_COMPS; c++) gx[c] = 0.0f;
     if (valid) {
-        // (everything a hit needs beyond its gaussian's records travels in the queue or sits in LDS: the fetches of this pass - live quarter,
-        // W, M - are ONE round trip; it used to re-read the arena row first and the ray from the state)
+        // (everything a hit needs beyond its gaussian's test record travels in the queue or sits in LDS: the fetches of this pass - live quarter
+        // and W, one 64-B record - are ONE round trip; it used to re-read the arena row first and the ray from the state)
         const uint4 item = bitems[i0 + (uint32_t)lane];
         const uint32_t ray = item.x, pos = item.z;
         const float weight = u2f(item.w);
         const float4 a2 = v.inst_w[4 * pos + 3];
         const f3 iro = mk3(bray[ray], bray[EGR_WAVE + ray], bray[2 * EGR_WAVE + ray]), ird = mk3(bray[3 * EGR_WAVE + ray], bray[4 * EGR_WAVE + ray], bray[5 * EGR_WAVE + ray]);
-        hit_geometry_fn<false>(v, exp_power, eps_scale_grad, pos, a2, iro, ird, u2f(item.y), gx);
+        hit_geometry_fn(v, exp_power, pos, a2, iro, ird, u2f(item.y), gx);
         gx[GC_RGB] = bdl[ray] * weight, gx[GC_RGB + 1] = bdl[EGR_WAVE + ray] * weight, gx[GC_RGB + 2] = bdl[2 * EGR_WAVE + ray] * weight;
         gx[GC_WEIGHT] = weight;
         dpos = pos;
     }
-    wide_add_wave<REC_BOUNCE>(v, valid, dpos, gx, stage);
+    wide_add_wave<EGR_REC0_CELL>(v, valid, dpos, gx, stage);
     return (uint32_t)__popcll(__ballot(valid));
 }
 
@@ -1024,7 +992,7 @@ template <int TEAM> struct BwdTeamShared {
 };
 
 // The backward half of the fused per-tile chain (see k_forward_chain): a wave takes a tile's backward through all its steps - the
-// primary step (21 gradient components per hit through the LDS table), then the bounce steps, last bounce first (15 components per
+// primary step (21 gradient components per hit through the LDS table), then the bounce steps, last bounce first (14 components per
 // hit, straight out as wide adds; in the team build their batches can be taken by team mates). Per-step code: backward_task.inc.
 #ifndef EGR_BWD_WAVES
 #define EGR_BWD_WAVES 3
@@ -1076,7 +1044,7 @@ __global__ void __launch_bounds__(256) k_order_backward(DeviceView v) {
 }
 
 // A team mate without tiles: take batches of the chunks its team mates have open (backward_task.inc: the ticket) until all waves are through.
-template <int TEAM> EGR_DI uint32_t bwd_team_help(const DeviceView &v, const float exp_power, const float eps_scale_grad, BwdTeamShared<TEAM> &bteam, float (*gt_vals_all)[EGR_GT_STRIDE * EGR_GT_SLOTS],
+template <int TEAM> EGR_DI uint32_t bwd_team_help(const DeviceView &v, const float exp_power, BwdTeamShared<TEAM> &bteam, float (*gt_vals_all)[EGR_GT_STRIDE * EGR_GT_SLOTS],
                                                   float4 *stage, const int wv, const int lane) {
     uint32_t records = 0u;
     while (uniform_u32(lds_peek(&bteam.done)) < (uint32_t)TEAM) {
@@ -1093,7 +1061,7 @@ template <int TEAM> EGR_DI uint32_t bwd_team_help(const DeviceView &v, const flo
             // the owner does not touch its queue, rays or radiance gradients before `finished` says that every batch of the chunk is done
             const uint32_t nitems = uniform_u32(lds_peek(&bteam.nitems[w]));
             const uint4 *bitems = reinterpret_cast<const uint4 *>(gt_vals_all[w]);
-            records += bounce_batch(v, exp_power, eps_scale_grad, bitems, gt_vals_all[w] + 16 * EGR_WAVE, gt_vals_all[w] + 19 * EGR_WAVE, bi * (uint32_t)EGR_WAVE, nitems, stage, lane);
+            records += bounce_batch(v, exp_power, bitems, gt_vals_all[w] + 16 * EGR_WAVE, gt_vals_all[w] + 19 * EGR_WAVE, bi * (uint32_t)EGR_WAVE, nitems, stage, lane);
             if (lane == 0) atomicAdd(&bteam.finished[w], 1u);
             any = true;
         }
@@ -1116,10 +1084,10 @@ template <int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribu
 // caller's gradient tensors - coalesced on the tensor side - and empties the row for the next launch.
 // OVERWRITE (egr_set_grad_overwrite: the tensors are a per-launch buffer that is all-reduced over the ranks): the launch's sums are
 // STORED, rows without a contribution store zeros - the caller neither clears the buffer nor pays the read half of a "+=".
-// A row holds finished values (bounce hits) and, in its GC_Q cells, the summed local matrix Q of the launch's PRIMARY hits (hit_geometry_fn): dl2w = W^T Q
-// and the scale / rotation chain (scale_rot_chain) are applied to that sum here, once, with the records the hits read - nothing rewrites them between the
-// chains and this kernel.
-// No cheap scatter kernel any more: the fp64 chain (three reciprocals, seventeen quotients and a square root in double per hit gaussian) takes it from 38 to
+// A row holds sums that are final (opacity, mean, rgb, weight, normal, f0, roughness) and, in its GC_Q cells, the summed local matrix Q of ALL the launch's
+// hits (hit_geometry_fn): dl2w = W^T Q and the scale / rotation chain (scale_rot_chain) are applied to that sum here, once, with the records the hits
+// read - nothing rewrites them between the chains and this kernel. Scale and rotation gradients exist only here, as locals.
+// No cheap scatter kernel any more: the fp64 chain (seventeen quotients and a square root in double per hit gaussian) takes it from 38 to
 // 98 VGPRs and from eight to four waves per SIMD; measured +0.015 ms on 0.095 ms at 1M gaussians (it still streams rows, records and nine tensors).
 template <bool OVERWRITE> __global__ void __launch_bounds__(256) k_grad_gather(DeviceView v) {
     const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
@@ -1141,18 +1109,19 @@ template <bool OVERWRITE> __global__ void __launch_bounds__(256) k_grad_gather(D
     }
 #pragma unroll
     for (int c = 0; c < 6; c++) any_l |= f2u(x[GC_Q + c]) << 1;
+    float d_scale[3] = {0.f, 0.f, 0.f}, d_rot[4] = {0.f, 0.f, 0.f, 0.f}; // (a row without Q has none)
     if (any_l != 0) {
         const float4 M0 = v.inst_m[4 * pos], M1 = v.inst_m[4 * pos + 1], M2 = v.inst_m[4 * pos + 2], qu = v.inst_m[4 * pos + 3];
         const float4 W0 = v.inst_w[4 * pos], W1 = v.inst_w[4 * pos + 1], W2 = v.inst_w[4 * pos + 2];
         const float scaling_factor = v.inst_w[4 * pos + 3].w;
         const double q00 = x[GC_Q], q01 = x[GC_Q + 1], q02 = x[GC_Q + 2], q11 = x[GC_Q + 3], q12 = x[GC_Q + 4], q22 = x[GC_Q + 5];
-        auto dl2w_of = [&](double w0, double w1, double w2) { return ChainVec<double>{w0 * q00 + w1 * q01 + w2 * q02, w0 * q01 + w1 * q11 + w2 * q12, w0 * q02 + w1 * q12 + w2 * q22}; }; // dl2w_i = sum_k W_k,i Q_k
-        double d_scale[3], d_rot[4];
-        scale_rot_chain<double>(M0, M1, M2, qu, scaling_factor, *v.cfg.eps_scale_grad, dl2w_of(W0.x, W1.x, W2.x), dl2w_of(W0.y, W1.y, W2.y), dl2w_of(W0.z, W1.z, W2.z), d_scale, d_rot);
+        auto dl2w_of = [&](double w0, double w1, double w2) { return ChainVec{w0 * q00 + w1 * q01 + w2 * q02, w0 * q01 + w1 * q11 + w2 * q12, w0 * q02 + w1 * q12 + w2 * q22}; }; // dl2w_i = sum_k W_k,i Q_k
+        double ds[3], dr[4];
+        scale_rot_chain(M0, M1, M2, qu, scaling_factor, *v.cfg.eps_scale_grad, dl2w_of(W0.x, W1.x, W2.x), dl2w_of(W0.y, W1.y, W2.y), dl2w_of(W0.z, W1.z, W2.z), ds, dr);
 #pragma unroll
-        for (int a = 0; a < 3; a++) x[GC_SCALE + a] = (float)((double)x[GC_SCALE + a] + d_scale[a]);
+        for (int a = 0; a < 3; a++) d_scale[a] = (float)ds[a];
 #pragma unroll
-        for (int a = 0; a < 4; a++) x[GC_ROT + a] = (float)((double)x[GC_ROT + a] + d_rot[a]);
+        for (int a = 0; a < 4; a++) d_rot[a] = (float)dr[a];
     }
     const egr_gaussians &g = v.g;
     auto put = [](float *p, float val) {
@@ -1162,11 +1131,11 @@ template <bool OVERWRITE> __global__ void __launch_bounds__(256) k_grad_gather(D
     put(g.dL_dopacity + gid, x[GC_OPA]);
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-        put(g.dL_dscale + 3 * gid + a, x[GC_SCALE + a]), put(g.dL_dmean + 3 * gid + a, x[GC_MEAN + a]), put(g.dL_drgb + 3 * gid + a, x[GC_RGB + a]);
+        put(g.dL_dscale + 3 * gid + a, d_scale[a]), put(g.dL_dmean + 3 * gid + a, x[GC_MEAN + a]), put(g.dL_drgb + 3 * gid + a, x[GC_RGB + a]);
         put(g.dL_dnormal + 3 * gid + a, x[GC_NORMAL + a]), put(g.dL_df0 + 3 * gid + a, x[GC_F0 + a]);
     }
 #pragma unroll
-    for (int a = 0; a < 4; a++) put(g.dL_drotation + 4 * gid + a, x[GC_ROT + a]);
+    for (int a = 0; a < 4; a++) put(g.dL_drotation + 4 * gid + a, d_rot[a]);
     put(g.dL_droughness + gid, x[GC_ROUGH]);
     put(g.total_weight + gid, x[GC_WEIGHT]);
 }
