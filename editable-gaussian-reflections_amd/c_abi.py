@@ -86,6 +86,28 @@ def eval_metrics(num_views, height, width, final, rgb, target_final, target_diff
         raise RuntimeError(L.egr_eval_last_error().decode())
 
 
+EGR_SSIM_TILE = 32
+
+
+def ssim_workspace_bytes(num_views, height, width):
+    """EGR_SSIM_WORKSPACE_BYTES(V, H, W) of the header: one partial of 18 fp64 sums per EGR_SSIM_TILE x EGR_SSIM_TILE tile and view."""
+    return num_views * ((height + EGR_SSIM_TILE - 1) // EGR_SSIM_TILE) * ((width + EGR_SSIM_TILE - 1) // EGR_SSIM_TILE) * (18 * 8)
+
+
+def eval_ssim(num_views, height, width, final, rgb, target_final, target_diffuse, target_specular, ssim_sum, ssim, workspace, device=0, stream=0):
+    """egr_eval_ssim on integer device addresses (include/egr_raytracer.h has the shapes; None = NULL). `workspace`: ssim_workspace_bytes() bytes, 8-byte aligned."""
+    L = lib()
+    if L.egr_eval_ssim(device, num_views, height, width, final, rgb, target_final, target_diffuse, target_specular, ssim_sum, ssim, workspace, C.c_void_p(stream)) != 0:
+        raise RuntimeError(L.egr_eval_last_error().decode())
+
+
+def ssim_images(num_views, height, width, pred, gt, ssim_sum, ssim, workspace, device=0, stream=0):
+    """egr_ssim_images on integer device addresses: pred, gt [V][3][H][W] display images. `workspace`: ssim_workspace_bytes() bytes, 8-byte aligned."""
+    L = lib()
+    if L.egr_ssim_images(device, num_views, height, width, pred, gt, ssim_sum, ssim, workspace, C.c_void_p(stream)) != 0:
+        raise RuntimeError(L.egr_eval_last_error().decode())
+
+
 # the dense-init cloud (csrc/initcloud.hip): a hash table of voxels in three caller-owned device buffers
 EGR_VOXEL_STATUS_WORDS = 8
 EGR_VOXEL_MIN_CAPACITY, EGR_VOXEL_MAX_CAPACITY = 1024, 1 << 31
@@ -197,6 +219,9 @@ def lib(path=None):
         L.egr_eval_metrics.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P, P, P, P, P, P, P]
         L.egr_eval_last_error.argtypes = []
         L.egr_eval_last_error.restype = C.c_char_p
+        # fused SSIM (csrc/ssim.hip): device, V, H, W, final, rgb, target_final, target_diffuse, target_specular, ssim_sum, ssim, workspace, stream
+        L.egr_eval_ssim.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P, P, P, P, P, P]
+        L.egr_ssim_images.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P, P, P]  # device, V, H, W, pred, gt, ssim_sum, ssim, workspace, stream
         # the dense-init cloud (csrc/initcloud.hip). accumulate: device, keys, acc, status, cap, V, H, W, c2w, origin, view_size, depth, colour, colour_u8, colour_table,
         # voxel_scale, colour_max, positions_out, stream
         L.egr_voxel_accumulate.argtypes = [C.c_int, P, P, P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P, P, P, P, C.c_double, C.c_double, P, P]

@@ -18,6 +18,7 @@
 #include <string>
 
 #include "../../include/egr_raytracer.h"
+#include "egr_eval_shared.hpp"
 
 namespace {
 
@@ -42,27 +43,7 @@ struct F3 {
     float x, y, z;
 };
 
-// D(x) = clamp(tonemap(x), 0, 1), operation by operation as torch evaluates it in fp32 (every product and sum rounded on its own: no fused multiply-add).
-// NaN propagates: a negative quotient gives NaN from the power, +-huge inputs give inf / inf, and the clamp is written with comparisons, which keep a NaN
-// (fminf / fmaxf would drop it).
-__device__ __forceinline__ float tone_display(float x) {
-#pragma clang fp contract(off)
-    if (x != x) x = 0.0f;                                         // nan_to_num: NaN -> 0
-    else if (x == INFINITY) x = 999999999.9f;                     //             +inf -> posinf
-    else if (x == -INFINITY) x = -3.402823466e+38f;               //             -inf -> the most negative float (then inf / inf = NaN below)
-    const float num = x * (6.2f * x + 0.5f);
-    const float den = x * (6.2f * x + 1.7f) + 0.06f;
-    float y = powf(__fdiv_rn(num, den), 1.3f);
-    y = y < 0.0f ? 0.0f : y;
-    y = y > 1.0f ? 1.0f : y;
-    return y;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-    return v; // lane 0 holds the sum (a fixed tree: the same order on every run)
-}
+// D(x) = clamp(tonemap(x), 0, 1) and the wave's fixed summation tree: egr_eval_shared.hpp (csrc/ssim.hip uses the same two)
 
 __global__ void __launch_bounds__(EVAL_THREADS) k_eval_partial(EvalArgs a) {
     __shared__ double s_wave[EVAL_THREADS / 64][EVAL_SUMS];
@@ -148,10 +129,7 @@ __global__ void __launch_bounds__(EVAL_THREADS) k_eval_finish(EvalArgs a) {
 
 thread_local std::string g_eval_error;
 
-int fail(const std::string &what) {
-    g_eval_error = "libegr_hip: egr_eval_metrics: " + what;
-    return 1;
-}
+int fail(const std::string &what) { return egr_eval_fail("egr_eval_metrics", what); }
 
 bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
@@ -159,6 +137,11 @@ bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
 }
 
 } // namespace
+
+int egr_eval_fail(const char *function, const std::string &what) {
+    g_eval_error = std::string("libegr_hip: ") + function + ": " + what;
+    return 1;
+}
 
 extern "C" const char *egr_eval_last_error(void) { return g_eval_error.c_str(); }
 

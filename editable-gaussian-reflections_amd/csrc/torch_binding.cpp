@@ -890,6 +890,52 @@ static std::tuple<Tensor, Tensor, Tensor> eval_metrics(const Tensor &final, cons
     return {sse, psnr, display};
 }
 
+// Fused SSIM (egr_eval_ssim, csrc/ssim.hip) on the tensors of eval_metrics, with its checks. Returns (ssim_sum fp64 [V,3,3,2]: the sums of the SSIM map per pass and
+// channel over all pixels and over the interior, ssim fp64 [V,3,2]: the two means per pass; a skipped pass reads NaN) on the device, two launches on the current
+// stream, no host synchronisation.
+static std::tuple<Tensor, Tensor> eval_ssim(const Tensor &final, const c10::optional<Tensor> &rgb, const c10::optional<Tensor> &target_final,
+                                            const c10::optional<Tensor> &target_diffuse, const c10::optional<Tensor> &target_specular) {
+    TORCH_CHECK(final.is_cuda() && final.scalar_type() == torch::kFloat32 && final.is_contiguous() && final.dim() == 4 && final.size(3) == 3, "eval_ssim: final must be a contiguous fp32 [V,H,W,3] GPU tensor");
+    const int64_t V = final.size(0), H = final.size(1), W = final.size(2);
+    TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && H <= 0x7FFFFFFF && W <= 0x7FFFFFFF, "eval_ssim: at least one view and one pixel are required");
+    const auto dev = final.device();
+    const c10::DeviceGuard guard(dev); // the outputs, the workspace and current_stream() belong to final's device, which need not be the current one
+    auto ptr = [&](const c10::optional<Tensor> &t, std::vector<int64_t> want, const char *what) -> const float * {
+        if (!t.has_value() || !t->defined()) return nullptr;
+        TORCH_CHECK(t->is_cuda() && t->device() == dev && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->sizes() == torch::IntArrayRef(want), "eval_ssim: ", what,
+                    " must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " on final's device, got ", t->sizes());
+        return t->data_ptr<float>();
+    };
+    const float *prgb = ptr(rgb, {V, EGR_NUM_STEPS, H, W, 3}, "rgb");
+    const float *tf = ptr(target_final, {V, 3, H, W}, "target_final"), *td = ptr(target_diffuse, {V, 3, H, W}, "target_diffuse"), *ts = ptr(target_specular, {V, 3, H, W}, "target_specular");
+    const auto f64 = torch::dtype(torch::kFloat64).device(dev);
+    Tensor sum = torch::empty({V, 3, 3, 2}, f64), mean = torch::empty({V, 3, 2}, f64);
+    Tensor workspace = torch::empty({(int64_t)(EGR_SSIM_WORKSPACE_BYTES(V, H, W) / 8)}, f64); // (freed stream-ordered by the caching allocator)
+    const int rc = egr_eval_ssim(dev.index(), (uint32_t)V, (uint32_t)H, (uint32_t)W, final.data_ptr<float>(), prgb, tf, td, ts, sum.data_ptr<double>(), mean.data_ptr<double>(),
+                                 workspace.data_ptr(), current_stream());
+    TORCH_CHECK(rc == 0, egr_eval_last_error());
+    return {sum, mean};
+}
+
+// The same kernel on display images the caller already has (egr_ssim_images): pred, gt contiguous fp32 [V,3,H,W] on one GPU, used as they are. Returns
+// (ssim_sum fp64 [V,3,2], ssim fp64 [V,2]) on the device.
+static std::tuple<Tensor, Tensor> ssim_images(const Tensor &pred, const Tensor &gt) {
+    TORCH_CHECK(pred.is_cuda() && pred.scalar_type() == torch::kFloat32 && pred.is_contiguous() && pred.dim() == 4 && pred.size(1) == 3, "ssim_images: pred must be a contiguous fp32 [V,3,H,W] GPU tensor");
+    TORCH_CHECK(gt.is_cuda() && gt.device() == pred.device() && gt.scalar_type() == torch::kFloat32 && gt.is_contiguous() && gt.sizes() == pred.sizes(),
+                "ssim_images: gt must be a contiguous fp32 tensor ", pred.sizes(), " on pred's device, got ", gt.sizes());
+    const int64_t V = pred.size(0), H = pred.size(2), W = pred.size(3);
+    TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && H <= 0x7FFFFFFF && W <= 0x7FFFFFFF, "ssim_images: at least one view and one pixel are required");
+    const auto dev = pred.device();
+    const c10::DeviceGuard guard(dev);
+    const auto f64 = torch::dtype(torch::kFloat64).device(dev);
+    Tensor sum = torch::empty({V, 3, 2}, f64), mean = torch::empty({V, 2}, f64);
+    Tensor workspace = torch::empty({(int64_t)(EGR_SSIM_WORKSPACE_BYTES(V, H, W) / 8)}, f64);
+    const int rc = egr_ssim_images(dev.index(), (uint32_t)V, (uint32_t)H, (uint32_t)W, pred.data_ptr<float>(), gt.data_ptr<float>(), sum.data_ptr<double>(), mean.data_ptr<double>(),
+                                   workspace.data_ptr(), current_stream());
+    TORCH_CHECK(rc == 0, egr_eval_last_error());
+    return {sum, mean};
+}
+
 // The dense-init cloud (egr_voxel_*, csrc/initcloud.hip). The table is three caller-owned GPU tensors: keys int64 [cap] (filled with -1), acc int64 [cap,4] and
 // status int64 [8] (zeroed). voxel_accumulate adds V views in one launch: c2w fp64 [V,3,3], origin fp64 [V,3], view_size fp64 [V] (the caller's host fp64 camera
 // set-up, uploaded), depth fp32 [V,H,W], colour fp32 or uint8 [V,H,W,3] (uint8 with the 256-entry fp32 table), positions_out fp64 [V,H,W,3] or None.
@@ -988,6 +1034,8 @@ TORCH_LIBRARY(egr, m) {
     m.def("eval_metrics(Tensor final, Tensor? rgb, Tensor? target_final, Tensor? target_diffuse, Tensor? target_specular, bool want_display=False) -> "
           "(Tensor sse, Tensor psnr, Tensor display)",
           &eval_metrics);
+    m.def("eval_ssim(Tensor final, Tensor? rgb, Tensor? target_final, Tensor? target_diffuse, Tensor? target_specular) -> (Tensor ssim_sum, Tensor ssim)", &eval_ssim);
+    m.def("ssim_images(Tensor pred, Tensor gt) -> (Tensor ssim_sum, Tensor ssim)", &ssim_images);
     m.def("voxel_accumulate(Tensor keys, Tensor acc, Tensor status, Tensor c2w, Tensor origin, Tensor view_size, Tensor depth, Tensor colour, Tensor? colour_table, "
           "float voxel_scale, float colour_max, Tensor? positions_out=None) -> ()",
           &voxel_accumulate);

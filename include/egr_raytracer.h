@@ -578,6 +578,43 @@ int egr_eval_metrics(int device, uint32_t num_views, uint32_t height, uint32_t w
                      void *hip_stream);
 const char *egr_eval_last_error(void);
 
+/* ---- Fused SSIM (additive symbols of library version 0.8, egr_version() is unchanged): the structural similarity of utils/loss_utils.py:39-70 (ssim) for the
+ * same three passes of V views in TWO launches (csrc/ssim.hip), in fp64. Context-free; errors are reported through egr_eval_last_error().
+ *
+ * Definition. p and g are display images: D(pred) and D(gt) with the D of egr_eval_metrics - the same device function, bit for bit - for egr_eval_ssim, and the
+ * caller's images as they are for egr_ssim_images.
+ *   window    w[k] = e[k] / sum(e), e[k] = exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0..10: computed and normalised on the host in fp64, applied separably (rows, then
+ *             columns).
+ *   padding   zero, "same" (loss_utils.py:51-60): a tap outside the image contributes nothing and is never read.
+ *   moments   per pixel and channel, in fp64: mu1 = W*p, mu2 = W*g, s1 = W*(p p) - mu1^2, s2 = W*(g g) - mu2^2, s12 = W*(p g) - mu1 mu2.
+ *   map       ((2 mu1 mu2 + C1) (2 s12 + C2)) / ((mu1^2 + mu2^2 + C1) (s1 + s2 + C2)), C1 = 1e-4, C2 = 9e-4. NaN propagates by plain arithmetic: the display
+ *             clamp keeps a NaN, so a NaN pixel poisons its 11 x 11 neighbourhood and the means, as upstream.
+ *   [0] full      the mean of the map over all 3 H W values: the reference's ssim(pred[None], gt[None]).
+ *   [1] interior  the mean over the 3 (H - 10) (W - 10) values whose window lies wholly inside the image; NaN when H < 11 or W < 11. This is the region that
+ *                 torchmetrics' StructuralSimilarityIndexMeasure averages (reflect pad, then crop the pad off); agreement with torchmetrics itself is UNPINNED
+ *                 (it is not available where this library is tested).
+ * Deviations from loss_utils.ssim, deliberate: the arithmetic is fp64 throughout (upstream: fp32, whose variance terms - a cancellation divided by C2 - are noise
+ * in the fourth digit on flat regions), and the window is exactly separable and sums to 1 (upstream's 2-D window is an fp32 outer product of fp32 weights whose
+ * sum is off by about 1e-8, which alone moves the result by 2.6e-6 on flat regions).
+ * Outputs (device, fp64), both flavours from the same map:
+ *   egr_eval_ssim     ssim_sum [V][3 passes][3 channels][2]: the sums of the map over all pixels and over the interior; ssim [V][3 passes][2]: the two means over
+ *                     the three channels. A pass whose target is NULL (or that lacks rgb) is skipped and reports NaN, as in egr_eval_metrics.
+ *   egr_ssim_images   pred, gt [V][3][H][W] channel-major fp32, one pass: ssim_sum [V][3 channels][2], ssim [V][2].
+ * k_ssim_partial (grid: EGR_SSIM_BLOCKS x V workgroups of 256 threads) owns one EGR_SSIM_TILE^2 output tile: the tile and a 5-pixel halo of both sides in LDS,
+ * the row pass and the column pass of the five moments in fp64, two sums per pass and channel reduced over the wave and the workgroup, one partial (18 fp64 sums)
+ * per tile in `workspace`; k_ssim_finish (one workgroup per view) adds the partials in a fixed order. No float atomics, no workgroup waits for another: the
+ * result depends on the inputs alone and is the same bit for bit on every run.
+ * workspace: EGR_SSIM_WORKSPACE_BYTES(V, H, W) bytes of device memory, 8-byte aligned, owned by the caller, free for reuse once the stream has passed the call.
+ * Refused BEFORE any HIP call (non-zero, egr_eval_last_error() says why): V == 0 (or > 65535), H or W == 0, a NULL final / pred / gt / ssim_sum / ssim /
+ * workspace, a misaligned workspace, a diffuse or specular target without rgb, an output that overlaps an input or another output. Asynchronous on the stream. */
+#define EGR_SSIM_TILE 32u /* output pixels per tile edge of k_ssim_partial: one partial (18 fp64 sums) of workspace per tile */
+#define EGR_SSIM_BLOCKS(H, W) ((((size_t)(H) + EGR_SSIM_TILE - 1) / EGR_SSIM_TILE) * (((size_t)(W) + EGR_SSIM_TILE - 1) / EGR_SSIM_TILE))
+#define EGR_SSIM_WORKSPACE_BYTES(V, H, W) ((size_t)(V) * EGR_SSIM_BLOCKS(H, W) * (18 * 8))
+int egr_eval_ssim(int device, uint32_t num_views, uint32_t height, uint32_t width, const float *final, const float *rgb, const float *target_final,
+                  const float *target_diffuse, const float *target_specular, double *ssim_sum, double *ssim, void *workspace, void *hip_stream);
+int egr_ssim_images(int device, uint32_t num_views, uint32_t height, uint32_t width, const float *pred, const float *gt, double *ssim_sum, double *ssim,
+                    void *workspace, void *hip_stream);
+
 /* ---- The dense-init cloud (additive symbols of library version 0.8, egr_version() is unchanged): what prepare_initial_ply.py:52-104 does on the CPU with every
  * pixel of every view in memory - unproject by the depth image, snap to a voxel of 1 / voxel_scale, average the diffuse colours per voxel, keep the voxels
  * seen by at least min_count pixels - as a streamed scatter-reduce into a hash table the caller owns (csrc/initcloud.hip). Context-free like egr_prune_*.
