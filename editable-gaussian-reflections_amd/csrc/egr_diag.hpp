@@ -35,7 +35,7 @@
 // The diagnostic control words [DG_BEGIN, DG_END) of ControlWord (egr_internal.hpp); EGR_DIAG_TABLE below says what each holds. k_prologue zeroes the whole range in
 // every launch of EVERY build and seeds DG_STEP_EXIT; everything else is written by EGR_TRAVERSAL_STATS builds only.
 enum DiagSlot : int {
-    DG_BEGIN = 32, // per step class, 64-bit: primary at the slot, bounce DG_CLASS_STRIDE words on (56 .. 79); the backward's five words are added through one pointer (backward_task.inc)
+    DG_BEGIN = 32, // per step class, 64-bit: primary at the slot, bounce DG_CLASS_STRIDE words on (56 .. 79); the backward's five words are added through one pointer (backward_chain.hpp: primary_hits)
     DG_VISITS = 32, DG_LEAF_HITS = 34, DG_WALK_ITERS = 36, DG_EVAL_ROUNDS = 38, DG_TRAVERSAL_CYC = 40, DG_COMPOSITE_CYC = 42, DG_LEAF_EVAL_CYC = 44, DG_BWD_MATH_CYC = 46 /* x 5 */, DG_CLASS_STRIDE = 24,
     DG_EPILOGUE_CYC = 80, DG_CHAIN_CYC = 82, DG_FILTER_CYC = 84, DG_FILTER_LEAVES = 86, DG_COMP_SCAN_CYC = 88 /* x 5, one pointer again (forward_task.inc) */, // once per launch, 64-bit
     DG_LIST_HIST = 98 /* x 7 */, DG_TEAM_OFFERS = 124, DG_TEAM_HELPED = 125, DG_TEAM_HELP_ITERS = 126, DG_TEAM_TALL = 127, // once per launch, 32-bit

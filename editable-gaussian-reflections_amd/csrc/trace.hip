@@ -6,7 +6,7 @@
 //     (ragged per-ray work: 1..1000s of candidates); waves never wait on each other (no workgroup barrier after the first instruction);
 //   * a tile runs through ALL its steps in one go (k_forward_chain: trace, step epilogue, trace, ...; k_backward_chain), so
 //     a launch pays the tail of its heaviest tile once per chain, not once per step. The per-step source lives in
-//     forward_task.inc / backward_task.inc / egr_epilogue.hpp. Per-ray state lives in a task-linear SoA buffer (fully coalesced);
+//     forward_task.inc / backward_chain.hpp (backward_step) / egr_epilogue.hpp. Per-ray state lives in a task-linear SoA buffer (fully coalesced);
 //   * the 8-wide BVH (128-B line-sized nodes, 16-bit child boxes) is walked by PRIMARY tiles as one FRUSTUM (all 64 rays leave the camera
 //     origin: one interval test per child slot for the whole tile, eight nodes per iteration; the leaves found are evaluated one after
 //     the other, records through the scalar cache, every lane for its own ray) and by BOUNCE tiles as PAIRS (one wave-wide LIFO of
@@ -108,6 +108,47 @@ EGR_DI f3 primary_direction(const DeviceView &v, int ix, int iy, bool jitter, ui
     const float *w = w2c; // rows of w2c (= columns of c2w)
     f3 w0 = mk3(w[0], w[1], w[2]), w1 = mk3(w[3], w[4], w[5]), w2 = mk3(w[6], w[7], w[8]);
     return normalize(w0 * x + w1 * y - w2);
+}
+
+// One task of a chain kernel (the backward chain decodes it here; the forward chain's loop, forward_chain.inc, spells the same out). BATCH (the frames of egr_render_views, the views of egr_train_views): the task index is
+// ((macro-tile group) * batch_frames + frame) << task_shift | sub-task - the frames of one macro tile are adjacent, so the samples of a tile run
+// close in time on one XCD (the queue chunks are contiguous task ranges). The tile's pixels come from the base task `tb`, its ray state and its
+// rows of the per-task tables from the full index `tq`.
+struct ChainTask {
+    uint32_t tq;       // full task index: ray state, per-task tables
+    uint32_t tb;       // base task: the tile's pixels (== tq outside a batch)
+    uint32_t bframe;   // (BATCH) batch frame index of this task
+    const float *bcam; // (BATCH) its view's camera record
+    bool last_frame;   // (stats / random_seeds are "last launch wins" stores: a batch's last frame only)
+};
+template <bool BATCH> EGR_DI ChainTask decode_task(const DeviceView &v, const uint32_t tq) {
+    ChainTask t{tq, tq, 0u, nullptr, true};
+    if constexpr (BATCH) {
+        t.tb = batch_base_task(v, tq);
+        t.bframe = v.batch_frame0 + (tq >> v.task_shift) % v.batch_frames;
+        t.bcam = v.batch_cams + (size_t)(t.bframe / v.batch_spv) * EGR_BATCH_CAM_FLOATS;
+        t.last_frame = t.bframe == v.batch_last_frame;
+    }
+    return t;
+}
+// The primary ray of pixel `tg` of a task: origin, direction and the seed after the jitter draws. The backward regenerates it from the seed
+// instead of reading a stored copy (backward_chain.hpp: output_gradients); forward_task.inc R1 is the same sequence. `view_size`: see primary_direction (a batch reads its view's record).
+struct PrimaryRay {
+    f3 ro, rd;
+    uint32_t seed;
+};
+template <bool BATCH> EGR_DI PrimaryRay primary_ray(const DeviceView &v, const TaskGeom &tg, const ChainTask &t, const float view_size) {
+    PrimaryRay r;
+    if constexpr (BATCH) { // frame f of a batch: the f-th of the sequential launches would see total_num_calls + f + 1 (its prologue adds 1)
+        r.seed = tea4(tg.pixel_id, (uint32_t)*v.meta.total_num_calls + t.bframe + 1u);
+        r.ro = mk3(t.bcam[0], t.bcam[1], t.bcam[2]);
+        r.rd = primary_direction(v, tg.px, tg.py, *v.cfg.jitter_primary_rays != 0, r.seed, t.bcam[12], t.bcam + 3);
+    } else {
+        r.seed = tea4(tg.pixel_id, (uint32_t)*v.meta.total_num_calls); // shaders.cu:88
+        r.ro = mk3(v.cam.origin[0], v.cam.origin[1], v.cam.origin[2]);
+        r.rd = primary_direction(v, tg.px, tg.py, *v.cfg.jitter_primary_rays != 0, r.seed, view_size, v.cam.rotation_w2c);
+    }
+    return r;
 }
 
 // The geometry of one (ray, gaussian) pair - object-space ray, closest-approach point, the two rejections that only need those
@@ -954,7 +995,7 @@ template <class GX> EGR_DI void hit_geometry_fn(const DeviceView &v, const float
     gx[PC_Q + 3] = ql.y * local_hit.y, gx[PC_Q + 4] = ql.y * local_hit.z, gx[PC_Q + 5] = ql.z * local_hit.z;
 }
 
-// One batch of 64 hits of a bounce step's queue (backward_task.inc: pass 2), lane = hit: the geometry gradient from the hit's record index, the
+// One batch of 64 hits of a bounce step's queue (backward_chain.hpp: bounce_hits, pass 2), lane = hit: the geometry gradient from the hit's record index, the
 // ray and dL/dalpha, the radiance part from the ray's dL/drgb, all 14 components (segment 0 of the row) out as one record. Queue, rays and radiance
 // gradients are the LDS of the wave that OWNS the tile; `stage` is the executing wave's. Returns the records sent.
 EGR_DI uint32_t bounce_batch(const DeviceView &v, const float exp_power, const uint4 *bitems, const float *bdl, const float *bray, uint32_t i0, uint32_t nitems, float4 *stage, int lane) {
@@ -993,7 +1034,7 @@ template <int TEAM> struct BwdTeamShared {
 
 // The backward half of the fused per-tile chain (see k_forward_chain): a wave takes a tile's backward through all its steps - the
 // primary step (21 gradient components per hit through the LDS table), then the bounce steps, last bounce first (14 components per
-// hit, straight out as wide adds; in the team build their batches can be taken by team mates). Per-step code: backward_task.inc.
+// hit, straight out as wide adds; in the team build their batches can be taken by team mates). Per-step code: backward_chain.hpp (backward_step).
 #ifndef EGR_BWD_WAVES
 #define EGR_BWD_WAVES 3
 #endif
@@ -1043,7 +1084,7 @@ __global__ void __launch_bounds__(256) k_order_backward(DeviceView v) {
     }
 }
 
-// A team mate without tiles: take batches of the chunks its team mates have open (backward_task.inc: the ticket) until all waves are through.
+// A team mate without tiles: take batches of the chunks its team mates have open (backward_chain.hpp: bounce_hits, the ticket) until all waves are through.
 template <int TEAM> EGR_DI uint32_t bwd_team_help(const DeviceView &v, const float exp_power, BwdTeamShared<TEAM> &bteam, float (*gt_vals_all)[EGR_GT_STRIDE * EGR_GT_SLOTS],
                                                   float4 *stage, const int wv, const int lane) {
     uint32_t records = 0u;
@@ -1070,14 +1111,13 @@ template <int TEAM> EGR_DI uint32_t bwd_team_help(const DeviceView &v, const flo
     return records;
 }
 
+#include "backward_chain.hpp"
 template <int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribute__((amdgpu_waves_per_eu(EGR_BWD_WAVES, EGR_BWD_WAVES))) k_backward_chain(DeviceView v) {
-    constexpr bool BATCH = false;
-#include "backward_chain.inc"
+    backward_chain<TEAM, false>(v);
 }
 // The same chain for the views of a multi-view training launch (egr_train_views). Its own kernel, so that the launches of egr_raytrace keep theirs.
 template <int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribute__((amdgpu_waves_per_eu(EGR_BWD_WAVES, EGR_BWD_WAVES))) k_backward_batch(DeviceView v) {
-    constexpr bool BATCH = true;
-#include "backward_chain.inc"
+    backward_chain<TEAM, true>(v);
 }
 
 // Last backward kernel: one thread per gaussian id adds its gradient row (a 128-B line at its record position) to the

@@ -313,7 +313,7 @@ def test_backward_parity(ren, orc, syn, bounces, team_help):
 @BOTH_HELP_MODES
 def test_backward_parity_long_bounce_chains(ren, orc, syn, team_help):
     """Bounce rays through a translucent cloud composite 20+ hits: their backward chains span several arena blocks per bounce step, which
-    the two-pass bounce backward (suffix sums per ray, geometry per hit; backward_task.inc) walks in chunks of four rows. Surfaces are made
+    the two-pass bounce backward (suffix sums per ray, geometry per hit; backward_chain.hpp: bounce_hits) walks in chunks of four rows. Surfaces are made
     specular enough for the bounces to happen at all (a dense-init cloud's accumulated normal is too short for most rays)."""
     from hip_common import generic_targets, grads_vs_oracle_listing_flipped_pixels
 
