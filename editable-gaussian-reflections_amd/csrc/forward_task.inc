@@ -578,7 +578,9 @@
                 atomicAdd(d, tc_scan), atomicAdd(d + 1, tc_alloc), atomicAdd(d + 2, tc_av), atomicAdd(d + 3, tc_p1), atomicAdd(d + 4, tc_app);
             })
             if (GRADS) {
-                // arena exhausted: forward results stay exact, backward skips this task (status flag is raised)
+                // arena exhausted: forward results stay exact, the backward skips THIS STEP of this task, all of it (no chain head, no hits; the status flag is
+                // raised): the gradients of an overflowing launch are those of its recorded (task, step)s (tests/test_hip_overflow.py). Either store alone makes
+                // the backward skip; the hit count is also what egr_debug_get_step_hits reports.
                 if (lane == 0) v.task_last_block[chain_head] = recording ? last_block : 0xFFFFFFFFu;
                 if (tg.inside) S.st(SF(step, S_NHITS), u2f(recording ? nhits : 0u));
             }

@@ -109,7 +109,8 @@ typedef struct egr_counters {
     uint64_t device_bytes;               /* device memory this context holds right now (scratch, arena, ray state, tree, records);
                                           * the caller's tensors (parameters, gradients, framebuffer) are not included          */
     uint32_t arena_blocks_used, arena_blocks_cap; /* composited-hit arena (backward capacity): 9-KB blocks the last grad launch took (waves take them in runs of 8:
-                                                   * up to 7 per resident wave are taken and not written) / holds */
+                                                   * up to 7 per resident wave are taken and not written; the count runs on past the capacity when the arena
+                                                   * overflows: used > cap then) / holds */
     uint32_t ext_blocks_used, ext_blocks_cap;     /* candidate-list extension blocks (forward capacity) the last launch took / holds         */
     uint64_t accepted[EGR_NUM_STEPS];    /* accepted candidates per step = entries the reference inserts into its forward list
                                           * (shaders.cu:74; its counter runs on over the three steps, so their SUM must stay below
@@ -117,8 +118,11 @@ typedef struct egr_counters {
 } egr_counters;
 
 #define EGR_STATUS_OK 0u
-#define EGR_STATUS_CANDIDATE_OVERFLOW 1u /* a ray met more candidates than the forward capacity allows (dropped) */
-#define EGR_STATUS_HIT_ARENA_OVERFLOW 2u /* composited-hit arena (backward capacity) exhausted; gradients partial */
+/* Both overflows are defined states (nothing is written out of bounds, the next launch starts clean; tests/test_hip_overflow.py): */
+#define EGR_STATUS_CANDIDATE_OVERFLOW 1u /* a ray met more candidates than the forward capacity allows: the candidates that found neither room in the ray's
+                                          * own run nor an extension block are dropped from its list; rays whose list fits their own run are bit-exact */
+#define EGR_STATUS_HIT_ARENA_OVERFLOW 2u /* composited-hit arena (backward capacity) exhausted: an 8x8 tile's bounce step that needed a block and got none is
+                                          * not recorded at all; the forward results stay exact, the gradients are exactly those of the recorded (tile, step)s */
 
 /* Raytracer::Raytracer(width, height, num_gaussians, ppll_forward_size, ppll_backward_size) (raytracer.cpp:45-79).
  * The two sizes are entry counts of the reference's per-pixel linked lists (36 B per entry,
