@@ -187,6 +187,9 @@ def lib(path=None):
             getattr(L, name).argtypes = [P, P]
         L.egr_raytrace.argtypes = [P, C.c_int, P]
         L.egr_update_bvh_ex.argtypes = [P, C.c_uint, P]
+        L.egr_update_bvh_from.argtypes = [P, C.POINTER(egr_gaussians), C.c_uint, P]  # ctx, src (its eight parameter pointers), flags, stream
+        L.egr_raytrace_import.argtypes = [P, C.POINTER(egr_gaussians), P]  # ctx, dst (its eight dL_d* pointers), stream
+        L.egr_debug_get_backward_records.argtypes = [P, P, P]  # ctx, host out [n][4][4] floats, stream
         L.egr_set_partition.argtypes = [P, C.c_int, C.c_int]
         L.egr_set_exact_stats.argtypes = [P, C.c_int]
         L.egr_set_grad_overwrite.argtypes = [P, C.c_int]
@@ -202,6 +205,7 @@ def lib(path=None):
         L.egr_render_views.argtypes = [P, C.POINTER(egr_view_batch), P]
         L.egr_set_batch_frames.argtypes = [P, C.c_int]
         L.egr_train_views.argtypes = [P, C.POINTER(egr_train_batch), P]
+        L.egr_train_views_import.argtypes = [P, C.POINTER(egr_train_batch), C.POINTER(egr_gaussians), P]
         L.egr_get_counters.argtypes = [P, C.POINTER(egr_counters), P]
         L.egr_get_counters_ex.argtypes = [P, P, C.c_size_t, P]
         # fused prune (csrc/prune.hip): device, n, total_weight, divisor, min_weight, points, cam_centers, cam_znear, num_cams, remove_mask, src_index, count, workspace, stream
@@ -275,8 +279,20 @@ class RawRaytracer:
         else:
             self._check(self.L.egr_update_bvh(self.ctx, self.stream))
 
+    def update_bvh_from(self, pointers, fuse_live=False):
+        """egr_update_bvh_from: export and refit in one pass. `pointers`: dict with the integer device addresses of the caller's eight parameter
+        arrays (GAUSSIAN_PARAMS); the bound arrays then hold their values."""
+        src = egr_gaussians(count=self.g.count, **{k: pointers[k] for k in GAUSSIAN_PARAMS})
+        self._check(self.L.egr_update_bvh_from(self.ctx, C.byref(src), 1 if fuse_live else 0, self.stream))
+
     def raytrace(self, grads_enabled):  # :81-94
         self._check(self.L.egr_raytrace(self.ctx, 1 if grads_enabled else 0, self.stream))
+
+    def raytrace_import(self, pointers):
+        """egr_raytrace_import: a grad launch whose gather also adds the bound gradient arrays to the caller's. `pointers`: dict with the integer
+        device addresses of the caller's eight gradient arrays (GAUSSIAN_GRADS without total_weight)."""
+        dst = egr_gaussians(count=self.g.count, **{k: pointers[k] for k in GAUSSIAN_GRADS[:8]})
+        self._check(self.L.egr_raytrace_import(self.ctx, C.byref(dst), self.stream))
 
     def render_views(self, num_views, samples_per_view, rotation_c2w_dataset, camera_center, vertical_fov_radians, znear=0.01, zfar=999.9, **outputs):
         """egr_render_views: the camera arrays and `outputs` (final= required; rgb=, depth=, normal=, f0=, roughness= optional) are integer

@@ -213,6 +213,33 @@ int egr_update_bvh_ex(egr_context *c, unsigned flags, void *stream) {
 }
 int egr_update_bvh(egr_context *c, void *stream) { return egr_update_bvh_ex(c, 0u, stream); }
 
+int egr_update_bvh_from(egr_context *c, const egr_gaussians *src, unsigned flags, void *stream) {
+    if (!c) return 1;
+    c->live_fresh = false;
+    // ---- validation: before any HIP call
+    // (an empty cloud has nothing to read: its tensors have no storage, and their pointers may be NULL)
+    if (!src || (c->g.count != 0 && (!src->scale || !src->rotation || !src->mean || !src->opacity || !src->rgb || !src->normal || !src->roughness || !src->f0))) {
+        c->last_error = "libegr_hip: egr_update_bvh_from: src and its eight parameter pointers must be non-NULL";
+        return 1;
+    }
+    if (reinterpret_cast<uintptr_t>(src->rotation) & 15u) {
+        c->last_error = "libegr_hip: egr_update_bvh_from: src->rotation must be 16-byte aligned";
+        return 1;
+    }
+    if (flags & ~(unsigned)EGR_UPDATE_FUSE_LIVE) {
+        c->last_error = "libegr_hip: egr_update_bvh_from: unknown flag";
+        return 1;
+    }
+    if (require_ready(c, true)) return 1;
+    const EgrParamSource from{src->scale, src->rotation, src->mean, src->opacity, src->rgb, src->normal, src->roughness, src->f0};
+    return guarded(c, [&] {
+        hipStream_t s = (hipStream_t)stream;
+        if (c->timing) EGR_HIP(hipEventRecord(c->ev_ub0, s));
+        egr_bvh_refit(c, s, (flags & EGR_UPDATE_FUSE_LIVE) != 0, &from);
+        if (c->timing) EGR_HIP(hipEventRecord(c->ev_ub1, s)), c->have_ub = true;
+    });
+}
+
 int egr_raytrace(egr_context *c, int grads_enabled, void *stream) {
     if (!c) return 1;
     // The live records of an egr_update_bvh_ex(EGR_UPDATE_FUSE_LIVE) are honoured by the raytrace that is the NEXT call on this context
@@ -222,6 +249,34 @@ int egr_raytrace(egr_context *c, int grads_enabled, void *stream) {
     const bool live_fresh = c->live_fresh;
     c->live_fresh = false;
     return traced(c, stream, [&](hipStream_t s) { egr_trace_launch(c, grads_enabled != 0, live_fresh, s); });
+}
+
+// The caller's gradient tensors of an importing grad launch, validated before any HIP call: all eight non-NULL, none the holder's own (the sum would be
+// added to itself), and no per-launch buffer (its launches store, and a partition reduces between gather and import).
+static int import_target(egr_context *c, const char *who, const egr_gaussians *dst, EgrGradImport &imp) {
+    auto refuse = [&](const char *what) {
+        c->last_error = std::string("libegr_hip: ") + who + ": " + what;
+        return 1;
+    };
+    const bool empty = c->g.count == 0; // (nothing to add to: the pointers are not read and may be NULL)
+    if (!dst || (!empty && (!dst->dL_drgb || !dst->dL_dnormal || !dst->dL_df0 || !dst->dL_droughness || !dst->dL_dopacity || !dst->dL_dscale || !dst->dL_dmean || !dst->dL_drotation)))
+        return refuse("dst and its eight dL_d* pointers must be non-NULL");
+    if (c->grad_overwrite) return refuse("the context writes a per-launch gradient buffer (egr_set_grad_overwrite): import after the reduction instead");
+    const egr_gaussians &h = c->g;
+    if (!empty && (dst->dL_drgb == h.dL_drgb || dst->dL_dnormal == h.dL_dnormal || dst->dL_df0 == h.dL_df0 || dst->dL_droughness == h.dL_droughness || dst->dL_dopacity == h.dL_dopacity ||
+        dst->dL_dscale == h.dL_dscale || dst->dL_dmean == h.dL_dmean || dst->dL_drotation == h.dL_drotation))
+        return refuse("dst must not be the bound gradient tensors themselves");
+    imp = EgrGradImport{dst->dL_drgb, dst->dL_dnormal, dst->dL_df0, dst->dL_droughness, dst->dL_dopacity, dst->dL_dscale, dst->dL_dmean, dst->dL_drotation};
+    return 0;
+}
+
+int egr_raytrace_import(egr_context *c, const egr_gaussians *dst, void *stream) {
+    if (!c) return 1;
+    const bool live_fresh = c->live_fresh; // (consumed as by egr_raytrace)
+    c->live_fresh = false;
+    EgrGradImport imp{};
+    if (import_target(c, "egr_raytrace_import", dst, imp)) return 1;
+    return traced(c, stream, [&](hipStream_t s) { egr_trace_launch(c, true, live_fresh, s, &imp); });
 }
 
 int egr_render_views(egr_context *c, const egr_view_batch *b, void *stream) {
@@ -239,10 +294,14 @@ int egr_render_views(egr_context *c, const egr_view_batch *b, void *stream) {
     return traced(c, stream, [&](hipStream_t s) { egr_render_views_launch(c, b, live_fresh, s); });
 }
 
-int egr_train_views(egr_context *c, const egr_train_batch *b, void *stream) {
+int egr_train_views(egr_context *c, const egr_train_batch *b, void *stream) { return egr_train_views_import(c, b, nullptr, stream); }
+
+int egr_train_views_import(egr_context *c, const egr_train_batch *b, const egr_gaussians *dst, void *stream) {
     if (!c) return 1;
     const bool live_fresh = c->live_fresh; // (consumed as by egr_raytrace)
     c->live_fresh = false;
+    EgrGradImport imp{};
+    if (dst && import_target(c, "egr_train_views_import", dst, imp)) return 1;
     if (!b || b->num_views == 0 || !b->rotation_c2w_dataset || !b->camera_center || !b->vertical_fov_radians) {
         c->last_error = "libegr_hip: egr_train_views: num_views must be >= 1 and the three camera arrays non-NULL";
         return 1;
@@ -251,7 +310,7 @@ int egr_train_views(egr_context *c, const egr_train_batch *b, void *stream) {
         c->last_error = "libegr_hip: egr_train_views: num_views must stay below 2^31";
         return 1;
     }
-    return traced(c, stream, [&](hipStream_t s) { egr_train_views_launch(c, b, live_fresh, s); });
+    return traced(c, stream, [&](hipStream_t s) { egr_train_views_launch(c, b, live_fresh, s, dst ? &imp : nullptr); });
 }
 
 int egr_set_batch_frames(egr_context *c, int frames) {
@@ -375,12 +434,13 @@ int egr_debug_get_instances(egr_context *c, float *M, float *W, float *aabb, voi
         std::vector<uint32_t> pos(n);
         std::vector<float> tmp(n * 16);
         EGR_HIP(hipMemcpy(pos.data(), c->pos_of_gid, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        auto unpermute = [&](const float4 *src, float *dst, size_t stride) { // records live at sorted positions; report them per gaussian id
+        auto unpermute = [&](const float4 *src, float *dst, size_t stride) { // test records live at sorted positions; report them per gaussian id
             EGR_HIP(hipMemcpy(tmp.data(), src, n * stride * sizeof(float), hipMemcpyDeviceToHost));
             for (size_t i = 0; i < n; i++) memcpy(dst + 12 * i, tmp.data() + stride * (size_t)pos[i], 12 * sizeof(float));
         };
-        if (M) { // backward records hold (M row, exp(scale)); the reported 3x4 transform carries the mean in column 3
-            unpermute(c->inst_m, M, 16);
+        if (M) { // backward records (kept by id) hold (M row, exp(scale)); the reported 3x4 transform carries the mean in column 3
+            EGR_HIP(hipMemcpy(tmp.data(), c->inst_m, n * 16 * sizeof(float), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n; i++) memcpy(M + 12 * i, tmp.data() + 16 * i, 12 * sizeof(float));
             std::vector<float> mean(3 * n);
             EGR_HIP(hipMemcpy(mean.data(), c->g.mean, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
             for (size_t i = 0; i < n; i++)
@@ -388,6 +448,14 @@ int egr_debug_get_instances(egr_context *c, float *M, float *W, float *aabb, voi
         }
         if (W) unpermute(c->inst_w, W, 16);
         if (aabb) EGR_HIP(hipMemcpy(aabb, c->aabb, n * 6 * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
+int egr_debug_get_backward_records(egr_context *c, float *host_out, void *stream) {
+    if (!c || !host_out) return 1;
+    return guarded(c, [&] {
+        EGR_HIP(hipStreamSynchronize((hipStream_t)stream));
+        if (c->n_built) EGR_HIP(hipMemcpy(host_out, c->inst_m, (size_t)c->n_built * 16 * sizeof(float), hipMemcpyDeviceToHost)); // (kept by id: no permutation)
     });
 }
 

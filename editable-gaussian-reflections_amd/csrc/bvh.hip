@@ -36,25 +36,55 @@ inline int nblk(uint64_t n, int bs = BS) { return (int)((n + bs - 1) / bs); }
 // mask (bvh_wrapper.cu:55): sigma > 0 && any(size > 0); masked-out instances get an empty box (lo > hi) and a W
 // record that can never pass the cube test (they keep their leaf slot, so a walk may still look at them).
 // ---------------------------------------------------------------------------------------------------------
-// Records are stored at the gaussian's MORTON-SORTED position (pos_of_gid), i.e. in leaf order: rays that are close
+// The test record, the appearance and the sphere are stored at the gaussian's MORTON-SORTED position (pos_of_gid), i.e. in leaf order: rays that are close
 // in space then read neighbouring 48-B records (same / adjacent cache lines) instead of lines scattered over the
 // whole array - the scene's own order is arbitrary (the reference never sorts its clouds).
 // `live` (egr_update_bvh_ex with EGR_UPDATE_FUSE_LIVE): also write what k_live (trace.hip) writes at every launch - the activated appearance
 // and the (f0.z, roughness, opacity, sigma) quarter of the test record - so that the raytrace that follows immediately skips that pass
 // over the cloud (the records' lines are being written here anyway).
-__global__ void __launch_bounds__(BS) k_instances(uint32_t n, egr_gaussians g, egr_config cfg, const uint32_t *__restrict__ pos_of_gid,
+// The backward record inst_m is the exception: it is stored by gaussian ID. No hit reads it - its writers (here, k_live) and its one reader
+// (k_grad_gather) all run one thread per id, so its stores and loads are coalesced and nothing has to be permuted.
+// `src` (egr_update_bvh_from): the parameters are read from the CALLER's tensors and stored to the bound (holder) tensors `g` on the way - what the
+// caller's eight copies would leave there, bit for bit - so the export costs no pass of its own. A tensor whose source IS the holder's is not stored.
+__global__ void __launch_bounds__(BS) k_instances(uint32_t n, egr_gaussians g, EgrParamSource src, egr_config cfg, const uint32_t *__restrict__ pos_of_gid,
                                                   float4 *__restrict__ inst_w, float4 *__restrict__ inst_m, float *__restrict__ aabb, int cube,
                                                   float4 *__restrict__ app, int live, float4 *__restrict__ bsph) {
     uint32_t i = blockIdx.x * BS + threadIdx.x;
     if (i >= n) return;
     const uint32_t slot = pos_of_gid ? pos_of_gid[i] : i;
     const float alpha_threshold = *cfg.alpha_threshold, exp_power = *cfg.exp_power, gsf = *cfg.global_scale_factor;
-    float opacity = sigmoid_act(g.opacity[i]);
+    const float raw_opacity = src.opacity[i];
+    const float raw_scale[3] = {src.scale[3 * i], src.scale[3 * i + 1], src.scale[3 * i + 2]};
+    // (the appearance is read by a pass that writes the live records or exports; a plain refit of the holder's own tensors leaves it alone, as ever)
+    const bool need_app = live || src.rgb != g.rgb || src.normal != g.normal || src.f0 != g.f0 || src.roughness != g.roughness;
+    float raw_roughness = 0.f, raw_rgb[3] = {0.f, 0.f, 0.f}, raw_normal[3] = {0.f, 0.f, 0.f}, raw_f0[3] = {0.f, 0.f, 0.f};
+    if (need_app) {
+        raw_roughness = src.roughness[i];
+#pragma unroll
+        for (int a = 0; a < 3; a++) raw_rgb[a] = src.rgb[3 * i + a], raw_normal[a] = src.normal[3 * i + a], raw_f0[a] = src.f0[3 * i + a];
+    }
+    const float4 q4 = reinterpret_cast<const float4 *>(src.rotation)[i];
+    float m[3] = {src.mean[3 * i], src.mean[3 * i + 1], src.mean[3 * i + 2]};
+    { // the export: wave-uniform branches, the values are in registers anyway
+        auto out = [](const float *holder) { return const_cast<float *>(holder); };
+        if (src.opacity != g.opacity) out(g.opacity)[i] = raw_opacity;
+        if (src.roughness != g.roughness) out(g.roughness)[i] = raw_roughness;
+        if (src.rotation != g.rotation) reinterpret_cast<float4 *>(out(g.rotation))[i] = q4;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            if (src.scale != g.scale) out(g.scale)[3 * i + a] = raw_scale[a];
+            if (src.mean != g.mean) out(g.mean)[3 * i + a] = m[a];
+            if (src.rgb != g.rgb) out(g.rgb)[3 * i + a] = raw_rgb[a];
+            if (src.normal != g.normal) out(g.normal)[3 * i + a] = raw_normal[a];
+            if (src.f0 != g.f0) out(g.f0)[3 * i + a] = raw_f0[a];
+        }
+    }
+    float opacity = sigmoid_act(raw_opacity);
     float sf = compute_scaling_factor(opacity, alpha_threshold, exp_power);
-    f3 sizes = mk3(expf(g.scale[3 * i]), expf(g.scale[3 * i + 1]), expf(g.scale[3 * i + 2]));
+    const float act_scale[3] = {expf(raw_scale[0]), expf(raw_scale[1]), expf(raw_scale[2])}; // (once: the sizes and the record's .w hold the same value)
+    f3 sizes = mk3(act_scale[0], act_scale[1], act_scale[2]);
     sizes = (sizes * sf) * gsf; // bvh_wrapper.cu:49-53
     bool visible = sf > 0.0f && (sizes.x > 0.0f || sizes.y > 0.0f || sizes.z > 0.0f);
-    const float4 q4 = reinterpret_cast<const float4 *>(g.rotation)[i];
     float r = q4.x, x = q4.y, y = q4.z, z = q4.w;
     float norm = sqrtf(r * r + x * x + y * y + z * z); // bvh_wrapper.cu:18-22
     r /= norm, x /= norm, y /= norm, z /= norm;
@@ -62,7 +92,6 @@ __global__ void __launch_bounds__(BS) k_instances(uint32_t n, egr_gaussians g, e
                      {2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x)},
                      {2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y)}};
     float s[3] = {sizes.x, sizes.y, sizes.z};
-    float m[3] = {g.mean[3 * i], g.mean[3 * i + 1], g.mean[3 * i + 2]};
     float inv[3] = {1.0f / s[0], 1.0f / s[1], 1.0f / s[2]};
     float lo[3], hi[3];
     float4 Wr[3];
@@ -70,7 +99,7 @@ __global__ void __launch_bounds__(BS) k_instances(uint32_t n, egr_gaussians g, e
 #pragma unroll
     for (int a = 0; a < 3; a++) {
         float M0 = s[0] * R[a][0], M1 = s[1] * R[a][1], M2 = s[2] * R[a][2];
-        inst_m[4 * slot + a] = make_float4(M0, M1, M2, expf(g.scale[3 * i + a])); // .w: activated scale (backward_pass.cu:170)
+        inst_m[4 * (size_t)i + a] = make_float4(M0, M1, M2, act_scale[a]); // by id; .w: activated scale (backward_pass.cu:170)
         float W0 = R[0][a] * inv[a], W1 = R[1][a] * inv[a], W2 = R[2][a] * inv[a];
         Wr[a] = make_float4(W0, W1, W2, -(W0 * m[0] + W1 * m[1] + W2 * m[2]));
         finite = finite && isfinite(W0 + W1 + W2 + Wr[a].w);
@@ -83,7 +112,7 @@ __global__ void __launch_bounds__(BS) k_instances(uint32_t n, egr_gaussians g, e
         hi[a] = m[a] + ext;
         finite = finite && (lo[a] <= hi[a]) && isfinite(lo[a]) && isfinite(hi[a]);
     }
-    inst_m[4 * slot + 3] = q4; // raw quaternion for the normalisation backward (activations.cu:66-73)
+    inst_m[4 * (size_t)i + 3] = q4; // raw quaternion for the normalisation backward (activations.cu:66-73)
     const bool usable = visible && finite; // NaN / inf parameters can never be hit
 #pragma unroll
     for (int a = 0; a < 3; a++) {
@@ -101,9 +130,9 @@ __global__ void __launch_bounds__(BS) k_instances(uint32_t n, egr_gaussians g, e
         bsph[slot] = usable && isfinite(rad) ? make_float4(m[0], m[1], m[2], rad * rad) : make_float4(0.f, 0.f, 0.f, -3.0e38f);
     }
     if (live) { // the same expressions as k_live (utils/helpers.cu:10-33)
-        app[2 * (size_t)slot] = make_float4(relu_act(g.rgb[3 * i]), relu_act(g.rgb[3 * i + 1]), relu_act(g.rgb[3 * i + 2]), g.normal[3 * i]);
-        app[2 * (size_t)slot + 1] = make_float4(g.normal[3 * i + 1], g.normal[3 * i + 2], clip01_act(g.f0[3 * i]), clip01_act(g.f0[3 * i + 1]));
-        inst_w[4 * (size_t)slot + 3] = make_float4(clip01_act(g.f0[3 * i + 2]), clip01_act(g.roughness[i]), opacity, sf);
+        app[2 * (size_t)slot] = make_float4(relu_act(raw_rgb[0]), relu_act(raw_rgb[1]), relu_act(raw_rgb[2]), raw_normal[0]);
+        app[2 * (size_t)slot + 1] = make_float4(raw_normal[1], raw_normal[2], clip01_act(raw_f0[0]), clip01_act(raw_f0[1]));
+        inst_w[4 * (size_t)slot + 3] = make_float4(clip01_act(raw_f0[2]), clip01_act(raw_roughness), opacity, sf);
     }
 }
 
@@ -486,7 +515,7 @@ void egr_bvh_rebuild(egr_context *c, hipStream_t s) {
         c->bvh_valid = true;
         return;
     }
-    hipLaunchKernelGGL(k_instances, dim3(nblk(n)), dim3(BS), 0, s, n, c->g, c->cfg, (const uint32_t *)nullptr, c->inst_w, c->inst_m, c->aabb, c->exact_stats ? 1 : 0, c->app, 0, c->bsph); // boxes for the frame
+    hipLaunchKernelGGL(k_instances, dim3(nblk(n)), dim3(BS), 0, s, n, c->g, egr_param_source_of(c->g), c->cfg, (const uint32_t *)nullptr, c->inst_w, c->inst_m, c->aabb, c->exact_stats ? 1 : 0, c->app, 0, c->bsph); // boxes for the frame
     uint32_t *bounds = c->scratch_u32, *counters = c->scratch_u32 + 16;
     hipLaunchKernelGGL(k_bounds_init, dim3(1), dim3(64), 0, s, bounds);
     hipLaunchKernelGGL(k_bounds, dim3(nblk(n)), dim3(BS), 0, s, n, c->aabb, bounds);
@@ -509,7 +538,7 @@ void egr_bvh_rebuild(egr_context *c, hipStream_t s) {
     size_t bytes = c->sort_tmp_bytes;
     EGR_HIP(rocprim::radix_sort_pairs(c->sort_tmp, bytes, c->keys_in, c->keys_out, c->vals_in, c->vals_out, (size_t)n, 0, 63, s));
     hipLaunchKernelGGL(k_inverse_perm, dim3(nblk(n)), dim3(BS), 0, s, n, c->vals_out, c->pos_of_gid);
-    hipLaunchKernelGGL(k_instances, dim3(nblk(n)), dim3(BS), 0, s, n, c->g, c->cfg, (const uint32_t *)c->pos_of_gid, c->inst_w, c->inst_m, c->aabb, c->exact_stats ? 1 : 0, c->app, 0, c->bsph); // records in leaf order
+    hipLaunchKernelGGL(k_instances, dim3(nblk(n)), dim3(BS), 0, s, n, c->g, egr_param_source_of(c->g), c->cfg, (const uint32_t *)c->pos_of_gid, c->inst_w, c->inst_m, c->aabb, c->exact_stats ? 1 : 0, c->app, 0, c->bsph); // records in leaf order
     if (n == 1) { // a single leaf under a one-child root
         uint4 root[EGR_WIDTH];
         for (int k = 0; k < EGR_WIDTH; k++) root[k] = make_uint4(0xFFFFFFFFu, 0x0000FFFFu, 0u, k == 0 ? (EGR_LEAF_FLAG | 0u) : EGR_EMPTY_SLOT);
@@ -552,12 +581,12 @@ void egr_bvh_rebuild(egr_context *c, hipStream_t s) {
     c->bvh_valid = true;
 }
 
-void egr_bvh_refit(egr_context *c, hipStream_t s, bool fuse_live) {
+void egr_bvh_refit(egr_context *c, hipStream_t s, bool fuse_live, const EgrParamSource *src) {
     const uint32_t n = c->g.count;
     if (!c->bvh_valid || n != c->n_built) throw EgrCheck{hipErrorInvalidValue, "update_bvh: tree was built for a different gaussian count; call rebuild_bvh"};
     c->boxes_are_cubes = c->exact_stats;
     if (n == 0) return;
-    hipLaunchKernelGGL(k_instances, dim3(nblk(n)), dim3(BS), 0, s, n, c->g, c->cfg, (const uint32_t *)c->pos_of_gid, c->inst_w, c->inst_m, c->aabb, c->exact_stats ? 1 : 0,
+    hipLaunchKernelGGL(k_instances, dim3(nblk(n)), dim3(BS), 0, s, n, c->g, src ? *src : egr_param_source_of(c->g), c->cfg, (const uint32_t *)c->pos_of_gid, c->inst_w, c->inst_m, c->aabb, c->exact_stats ? 1 : 0,
                        c->app, fuse_live ? 1 : 0, c->bsph);
     c->live_fresh = fuse_live;
     refit_boxes(c, s);

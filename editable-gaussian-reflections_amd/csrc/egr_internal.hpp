@@ -40,7 +40,8 @@ inline void egr_hip_check(hipError_t e, const char *what) {
 // inst_w : float4[4N]   64-B test record: rows of W = M^-1 (world->object; snapshot at update/rebuild) + live
 //                       quarter (f0.z, roughness, opacity, sigma) written per launch: one candidate test = one 64-B sector
 // inst_m : float4[4N]   64-B backward record: rows 0-2 = (row of M (object->world; snapshot), exp(scale_a)), row 3 = raw quaternion; read once per hit
-//                       gaussian by k_grad_gather (the scale / rotation chain of the hits' summed Q), by no hit;
+//                       gaussian by k_grad_gather (the scale / rotation chain of the hits' summed Q), by no hit - so it is indexed by gaussian ID:
+//                       its writers (k_instances, k_live) and its reader run one thread per id, all three coalesced;
 //                       exp(scale) and the quaternion are LIVE: k_live rewrites them in every grad launch (backward_pass.cu:68-70
 //                       reads them from the parameter tensors), so between an update and the next grad launch the record mixes
 //                       snapshot M rows with the scale / rotation of the last grad launch
@@ -51,8 +52,19 @@ inline void egr_hip_check(hipError_t e, const char *what) {
 // app    : float4[2N]   live per-launch record: (relu rgb, n.x) (n.y, n.z, f0.x, f0.y)       32 B
 // wnodes : uint4[8*Nw]     8-wide BVH, one 128-B line per node; child slot (16 B):
 //          x = lo.x | lo.y<<16, y = lo.z | hi.x<<16, z = hi.y | hi.z<<16 (16-bit cells of the build frame), w = link
-// inst_w / inst_m / app / grad_rows are indexed by SORTED POSITION (Morton / leaf order);
+// inst_w / app / bsph / grad_rows are indexed by SORTED POSITION (Morton / leaf order): hits read or add to them; inst_m by gaussian id;
 // gid_of_pos / pos_of_gid map between sorted positions and the caller's gaussian ids
+
+// The eight parameter tensors a refit reads (egr_update_bvh_from: the caller's own; otherwise the bound holder's).
+struct EgrParamSource {
+    const float *scale, *rotation, *mean, *opacity, *rgb, *normal, *roughness, *f0;
+};
+inline EgrParamSource egr_param_source_of(const egr_gaussians &g) { return EgrParamSource{g.scale, g.rotation, g.mean, g.opacity, g.rgb, g.normal, g.roughness, g.f0}; }
+// The caller's eight gradient tensors a grad launch adds to on its way out (egr_raytrace_import). A kernel argument of k_grad_gather alone - not part of
+// DeviceView, which the chain kernels take by value.
+struct EgrGradImport {
+    float *dL_drgb, *dL_dnormal, *dL_df0, *dL_droughness, *dL_dopacity, *dL_dscale, *dL_dmean, *dL_drotation;
+};
 
 struct BvhFrame { // quantisation frame of one build: cell = (x - o) * s + 2
     float ox, oy, oz, sx, sy, sz;
@@ -81,7 +93,7 @@ struct DeviceView { // everything a kernel needs, passed by value
     BvhFrame frame;
     const uint32_t *out_of_frame; // != 0: some box carries the -inf / +inf sentinel cells (see qslab_hit)
     float4 *inst_w;             // [n][4] test record: rows 0-2 = W (snapshot), row 3 = live quarter (k_live writes it per launch)
-    float4 *inst_m;             // [n][4] backward record: rows 0-2 = (M row (snapshot), exp(scale_a) (live)), row 3 = raw quaternion (live)
+    float4 *inst_m;             // [n][4] backward record BY GAUSSIAN ID: rows 0-2 = (M row (snapshot), exp(scale_a) (live)), row 3 = raw quaternion (live)
     float *grad_rows;           // [n][32] gradient accumulation rows in record order (one 128-B line per gaussian; 21 floats used: trace.hip GC_*)
     float4 *app;                // [n][2] live appearance (k_live writes it per launch)
     const float4 *bsph;         // [n] bounding sphere of the gaussian's ellipsoid (centre, squared radius; snapshot): the per-ray pre-test of primary tiles
@@ -261,14 +273,14 @@ template <class T> void egr_dev_free(egr_context *c, T *&p) {
 void egr_bvh_free(egr_context *c);
 void egr_bvh_reserve(egr_context *c, uint32_t n);
 void egr_bvh_rebuild(egr_context *c, hipStream_t s);
-void egr_bvh_refit(egr_context *c, hipStream_t s, bool fuse_live = false);
+void egr_bvh_refit(egr_context *c, hipStream_t s, bool fuse_live = false, const EgrParamSource *src = nullptr); // src: read the parameters there and store them to the holder on the way
 int egr_bvh_check(egr_context *c, hipStream_t s, std::string &msg);
 // trace.hip
 void egr_trace_alloc(egr_context *c);
 void egr_trace_free(egr_context *c);
-void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s);
+void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s, const EgrGradImport *import_into = nullptr); // import_into (grad launches): the gather also adds the holder's gradients to these
 void egr_render_views_launch(egr_context *c, const egr_view_batch *b, bool live_fresh, hipStream_t s);
-void egr_train_views_launch(egr_context *c, const egr_train_batch *b, bool live_fresh, hipStream_t s);
+void egr_train_views_launch(egr_context *c, const egr_train_batch *b, bool live_fresh, hipStream_t s, const EgrGradImport *import_into = nullptr);
 uint32_t egr_num_tasks_for_rank(const egr_context *c);
 void egr_build_task_order(egr_context *c);
 DeviceView egr_make_view(const egr_context *c);

@@ -382,14 +382,54 @@ struct Raytracer : torch::CustomClassHolder {
         if (ctx) egr_destroy(ctx);
     }
 
-    void raytrace() { // raytracer.cpp:81-94
-        check(egr_raytrace(ctx, torch::autograd::GradMode::is_enabled() ? 1 : 0, current_stream()), "raytrace");
+    // The caller's eight tensors of a fused export / import, in the export order of gaussian_raytracer.py:41-50 (scale, rotation, mean, opacity, rgb, normal,
+    // roughness, f0): each a contiguous fp32 tensor on the tracer's device with the shape of the holder's. Checked before anything is launched.
+    void check_like_holder(const char *who, const std::vector<Tensor> &t) {
+        const Tensor *like[8] = {&gaussian_data->scale, &gaussian_data->rotation, &gaussian_data->mean, &gaussian_data->opacity, &gaussian_data->rgb, &gaussian_data->normal,
+                                 &gaussian_data->roughness, &gaussian_data->f0};
+        static const char *const names[8] = {"scale", "rotation", "mean", "opacity", "rgb", "normal", "roughness", "f0"};
+        TORCH_CHECK(t.size() == 8, who, ": eight tensors expected (scale, rotation, mean, opacity, rgb, normal, roughness, f0), got ", t.size());
+        for (int k = 0; k < 8; k++)
+            TORCH_CHECK(t[k].defined() && t[k].device() == like[k]->device() && t[k].scalar_type() == torch::kFloat32 && t[k].is_contiguous() && t[k].sizes() == like[k]->sizes(), who,
+                        ": '", names[k], "' must be a contiguous fp32 tensor ", like[k]->sizes(), " on the tracer's device");
+    }
+    // import_into (addition; grad mode only): the caller's eight gradient tensors, in the order of update_bvh_from's parameters. The launch's gather adds what it
+    // leaves in the holder's gradients to them - `t.grad += holder.grad` for the eight, bit for bit, without the extra pass (egr_raytrace_import).
+    void raytrace(c10::optional<std::vector<Tensor>> import_into) { // raytracer.cpp:81-94
+        const bool grads = torch::autograd::GradMode::is_enabled();
+        if (!import_into.has_value()) {
+            check(egr_raytrace(ctx, grads ? 1 : 0, current_stream()), "raytrace");
+            return;
+        }
+        TORCH_CHECK(grads, "raytrace: import_into needs grad mode (a no-grad launch has no gradients to import)");
+        const egr_gaussians dst = import_target("raytrace", *import_into);
+        check(egr_raytrace_import(ctx, &dst, current_stream()), "raytrace");
+    }
+    egr_gaussians import_target(const char *who, const std::vector<Tensor> &t) {
+        check_like_holder(who, t);
+        egr_gaussians dst{};
+        dst.count = (uint32_t)gaussian_data->count;
+        dst.dL_dscale = ptr<float>(t[0]), dst.dL_drotation = ptr<float>(t[1]), dst.dL_dmean = ptr<float>(t[2]), dst.dL_dopacity = ptr<float>(t[3]);
+        dst.dL_drgb = ptr<float>(t[4]), dst.dL_dnormal = ptr<float>(t[5]), dst.dL_droughness = ptr<float>(t[6]), dst.dL_df0 = ptr<float>(t[7]);
+        return dst;
     }
     void denoise() { check(egr_denoise(ctx, current_stream()), "denoise"); }
     void reset_accumulators() { framebuffer_data->reset_accumulators(); }
     // fuse_live (addition; default = the reference's update_bvh()): the pass also writes the live per-gaussian records and the NEXT raytrace()
     // skips its own pass over the cloud - for callers that run update_bvh() and raytrace() back to back (egr_update_bvh_ex)
     void update_bvh(bool fuse_live) { check(egr_update_bvh_ex(ctx, fuse_live ? EGR_UPDATE_FUSE_LIVE : 0u, current_stream()), "update_bvh"); }
+    // export + update_bvh(fuse_live) in one pass over the cloud (egr_update_bvh_from): the eight tensors hold the caller's current parameter values; the
+    // holder's tensors then hold them too, as after the eight copy_ calls of gaussian_raytracer.py:41-50
+    void update_bvh_from(Tensor scale, Tensor rotation, Tensor mean, Tensor opacity, Tensor rgb, Tensor normal, Tensor roughness, Tensor f0, bool fuse_live) {
+        const std::vector<Tensor> t{scale, rotation, mean, opacity, rgb, normal, roughness, f0};
+        check_like_holder("update_bvh_from", t);
+        TORCH_CHECK((reinterpret_cast<uintptr_t>(rotation.data_ptr()) & 15u) == 0, "update_bvh_from: 'rotation' must be 16-byte aligned");
+        egr_gaussians src{};
+        src.count = (uint32_t)gaussian_data->count;
+        src.scale = ptr<float>(scale), src.rotation = ptr<float>(rotation), src.mean = ptr<float>(mean), src.opacity = ptr<float>(opacity);
+        src.rgb = ptr<float>(rgb), src.normal = ptr<float>(normal), src.roughness = ptr<float>(roughness), src.f0 = ptr<float>(f0);
+        check(egr_update_bvh_from(ctx, &src, fuse_live ? EGR_UPDATE_FUSE_LIVE : 0u, current_stream()), "update_bvh_from");
+    }
     void rebuild_bvh() { check(egr_rebuild_bvh(ctx, current_stream()), "rebuild_bvh"); }
     void resize(int64_t n) { // raytracer.cpp:112-120
         gaussian_data->resize(n);
@@ -504,6 +544,12 @@ struct Raytracer : torch::CustomClassHolder {
     // the gradient tensors (or the per-launch buffer: one grad launch for the whole batch) as V sequential raytrace() calls with grad mode on would.
     void train_views(Tensor R, Tensor centers, Tensor fovy, double znear, double zfar, c10::optional<Tensor> diffuse, c10::optional<Tensor> specular,
                      c10::optional<Tensor> depth, c10::optional<Tensor> normal, c10::optional<Tensor> roughness, c10::optional<Tensor> f0) {
+        train_views_import(R, centers, fovy, znear, zfar, diffuse, specular, depth, normal, roughness, f0, c10::nullopt);
+    }
+    // ... with raytrace()'s import_into: the batch's one gather also adds to the caller's eight gradient tensors (egr_train_views_import)
+    void train_views_import(Tensor R, Tensor centers, Tensor fovy, double znear, double zfar, c10::optional<Tensor> diffuse, c10::optional<Tensor> specular,
+                            c10::optional<Tensor> depth, c10::optional<Tensor> normal, c10::optional<Tensor> roughness, c10::optional<Tensor> f0,
+                            c10::optional<std::vector<Tensor>> import_into) {
         const auto [r, cc, fv, V] = batch_cameras("train_views", R, centers, fovy);
         const auto dev = framebuffer_data->output_rgb.device();
         egr_train_batch b{};
@@ -520,7 +566,12 @@ struct Raytracer : torch::CustomClassHolder {
                         "' must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " (channel-major) on the tracer's device, got ", t.sizes(), " ", t.scalar_type(), " on ", t.device());
             *slot[k] = t.data_ptr<float>();
         }
-        check(egr_train_views(ctx, &b, current_stream()), "train_views");
+        if (import_into.has_value()) {
+            const egr_gaussians dst = import_target("train_views", *import_into);
+            check(egr_train_views_import(ctx, &b, &dst, current_stream()), "train_views");
+        } else {
+            check(egr_train_views(ctx, &b, current_stream()), "train_views");
+        }
     }
     // batched denoise (egr_denoise_views): final [V,H,W,3] and its guide normal - render_views' [V,3,H,W,3] buffer (step 0 is the guide) or a packed [V,H,W,3] -
     // as contiguous fp32 tensors on the tracer's device. Returns a new [V,H,W,3] tensor; each view is bit-equal to denoise() on a framebuffer that holds the same
@@ -587,6 +638,14 @@ struct Raytracer : torch::CustomClassHolder {
         check(egr_debug_get_instances(ctx, M.data_ptr<float>(), W.data_ptr<float>(), A.data_ptr<float>(), current_stream()), "debug_instances");
         return {M, W, A};
     }
+    Tensor debug_backward_records() { // [n,4,4] float32 on the host, by gaussian id (egr_debug_get_backward_records)
+        float frame[6];
+        uint32_t info[4] = {0u, 0u, 0u, 0u}; // (info[3]: the count the tree was built for - the rows the library copies, whatever the holder was resized to since)
+        check(egr_debug_get_bvh_state(ctx, frame, info, current_stream()), "debug_backward_records");
+        Tensor t = torch::zeros({(int64_t)info[3], 4, 4}, torch::kFloat32);
+        check(egr_debug_get_backward_records(ctx, t.data_ptr<float>(), current_stream()), "debug_backward_records");
+        return t;
+    }
     std::tuple<Tensor, Tensor> debug_bvh_state() { // (float32[6]: the build frame's origin xyz and cells per world unit xyz; int64[4]: out_of_frame flag, wide nodes, depth, n built) on the host
         Tensor f = torch::zeros({6}, torch::kFloat32), i = torch::zeros({4}, torch::kInt64);
         uint32_t info[4] = {0u, 0u, 0u, 0u};
@@ -599,10 +658,11 @@ struct Raytracer : torch::CustomClassHolder {
         using Self = c10::intrusive_ptr<Raytracer>;
         m.class_<Raytracer>("Raytracer")
             .def(torch::init<int64_t, int64_t, int64_t, int64_t, int64_t>())
-            .def("raytrace", &Raytracer::raytrace)
+            .def("raytrace", &Raytracer::raytrace, "", {torch::arg("import_into") = c10::IValue()})
             .def("denoise", &Raytracer::denoise)
             .def("reset_accumulators", &Raytracer::reset_accumulators)
             .def("update_bvh", &Raytracer::update_bvh, "", {torch::arg("fuse_live") = false})
+            .def("update_bvh_from", &Raytracer::update_bvh_from)
             .def("rebuild_bvh", &Raytracer::rebuild_bvh)
             .def("resize", &Raytracer::resize)
             .def("get_camera", [](const Self &self) { return self->camera_data; })
@@ -655,6 +715,7 @@ struct Raytracer : torch::CustomClassHolder {
             .def("render_views", &Raytracer::render_views)
             .def("render_views_into", &Raytracer::render_views_into)
             .def("train_views", &Raytracer::train_views)
+            .def("train_views_import", &Raytracer::train_views_import)
             .def("denoise_views", &Raytracer::denoise_views)
             .def("set_batch_frames", &Raytracer::set_batch_frames)
             .def("set_exact_stats", &Raytracer::set_exact_stats)
@@ -671,6 +732,7 @@ struct Raytracer : torch::CustomClassHolder {
             .def("check_bvh", &Raytracer::check_bvh)
             .def("last_error", &Raytracer::last_error)
             .def("debug_instances", &Raytracer::debug_instances)
+            .def("debug_backward_records", &Raytracer::debug_backward_records)
             .def("debug_bvh_state", &Raytracer::debug_bvh_state)
             .def("debug_step_hits", &Raytracer::debug_step_hits)
             .def("debug_hit_sequence_hash", &Raytracer::debug_hit_sequence_hash);

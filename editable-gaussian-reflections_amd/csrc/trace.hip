@@ -710,7 +710,7 @@ __global__ void __launch_bounds__(256) k_live(DeviceView v, int grads) {
     // the 4th quarter of the 64-B test record (rows of W are the first three): what a candidate test needs besides W
     v.inst_w[4 * pos + 3] = make_float4(clip01_act(g.f0[3 * i + 2]), clip01_act(g.roughness[i]), o, sigma);
     if (grads) {
-        float4 *im = v.inst_m + 4 * pos;
+        float4 *im = v.inst_m + 4 * (size_t)i; // (the backward record is kept by id: egr_internal.hpp)
         im[0].w = expf(g.scale[3 * i]), im[1].w = expf(g.scale[3 * i + 1]), im[2].w = expf(g.scale[3 * i + 2]);
         im[3] = reinterpret_cast<const float4 *>(g.rotation)[i];
     }
@@ -1129,9 +1129,7 @@ template <int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribu
 // read - nothing rewrites them between the chains and this kernel. Scale and rotation gradients exist only here, as locals.
 // No cheap scatter kernel any more: the fp64 chain (seventeen quotients and a square root in double per hit gaussian) takes it from 38 to
 // 98 VGPRs and from eight to four waves per SIMD; measured +0.015 ms on 0.095 ms at 1M gaussians (it still streams rows, records and nine tensors).
-template <bool OVERWRITE> __global__ void __launch_bounds__(256) k_grad_gather(DeviceView v) {
-    const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
-    if (gid >= v.n) return;
+template <bool OVERWRITE> EGR_DI void grad_gather_row(const DeviceView &v, const uint32_t gid) {
     const size_t pos = v.pos_of_gid[gid];
     float4 *row = reinterpret_cast<float4 *>(v.grad_rows + pos * EGR_ROW_STRIDE);
     float x[EGR_ROW_STRIDE];
@@ -1151,7 +1149,8 @@ template <bool OVERWRITE> __global__ void __launch_bounds__(256) k_grad_gather(D
     for (int c = 0; c < 6; c++) any_l |= f2u(x[GC_Q + c]) << 1;
     float d_scale[3] = {0.f, 0.f, 0.f}, d_rot[4] = {0.f, 0.f, 0.f, 0.f}; // (a row without Q has none)
     if (any_l != 0) {
-        const float4 M0 = v.inst_m[4 * pos], M1 = v.inst_m[4 * pos + 1], M2 = v.inst_m[4 * pos + 2], qu = v.inst_m[4 * pos + 3];
+        const float4 *im = v.inst_m + 4 * (size_t)gid; // (the backward record is kept by id: coalesced)
+        const float4 M0 = im[0], M1 = im[1], M2 = im[2], qu = im[3];
         const float4 W0 = v.inst_w[4 * pos], W1 = v.inst_w[4 * pos + 1], W2 = v.inst_w[4 * pos + 2];
         const float scaling_factor = v.inst_w[4 * pos + 3].w;
         const double q00 = x[GC_Q], q01 = x[GC_Q + 1], q02 = x[GC_Q + 2], q11 = x[GC_Q + 3], q12 = x[GC_Q + 4], q22 = x[GC_Q + 5];
@@ -1178,6 +1177,44 @@ template <bool OVERWRITE> __global__ void __launch_bounds__(256) k_grad_gather(D
     for (int a = 0; a < 4; a++) put(g.dL_drotation + 4 * gid + a, d_rot[a]);
     put(g.dL_droughness + gid, x[GC_ROUGH]);
     put(g.total_weight + gid, x[GC_WEIGHT]);
+}
+// The import of one tensor for the 256 gaussians of a workgroup: `width` floats each, a contiguous run of both tensors - to += from, element by element, as
+// float4s where the run is whole and both tensors are 16-byte aligned (a holder tensor starts 3n, 6n, ... floats into the flat gradient buffer).
+EGR_DI void import_block_tensor(float *__restrict__ to, const float *from, const uint32_t block, const uint32_t n, const uint32_t width) {
+    const size_t beg = (size_t)block * 256u * width, end = min(beg + (size_t)256u * width, (size_t)n * width);
+    if (end - beg == (size_t)256u * width && ((reinterpret_cast<uintptr_t>(to) | reinterpret_cast<uintptr_t>(from)) & 15u) == 0) {
+        float4 *to4 = reinterpret_cast<float4 *>(to + beg);
+        const float4 *from4 = reinterpret_cast<const float4 *>(from + beg);
+        for (uint32_t q = threadIdx.x; q < 64u * width; q += 256u) {
+            float4 a = to4[q];
+            const float4 b = from4[q];
+            a.x += b.x, a.y += b.y, a.z += b.z, a.w += b.w;
+            to4[q] = a;
+        }
+    } else {
+        for (size_t j = beg + threadIdx.x; j < end; j += 256u) to[j] += from[j];
+    }
+}
+// IMPORT (egr_raytrace_import; never with OVERWRITE): what this kernel leaves in the holder's gradient tensors - the accumulated value, also of a row without a
+// contribution - is added to the caller's tensors `imp`: what a multi-tensor `caller.grad += holder.grad` after the launch computes, bit for bit. The
+// workgroup's 256 gaussians are a contiguous run of every tensor, so once its threads have stored their sums (the barrier) the workgroup adds the runs as
+// whole lines, like the multi-tensor kernel - but the holder's values are the ones it has just written: they come from the cache, and nothing is launched
+// or read a second time. total_weight is not imported.
+template <bool OVERWRITE, bool IMPORT> __global__ void __launch_bounds__(256) k_grad_gather(DeviceView v, EgrGradImport imp) {
+    static_assert(!(OVERWRITE && IMPORT), "an importing launch adds");
+    const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
+    if constexpr (!IMPORT) {
+        if (gid >= v.n) return;
+        grad_gather_row<OVERWRITE>(v, gid);
+    } else {
+        if (gid < v.n) grad_gather_row<false>(v, gid);
+        __syncthreads(); // (workgroup scope: the stores above are visible to the loads below)
+        const egr_gaussians &g = v.g;
+        import_block_tensor(imp.dL_drgb, g.dL_drgb, blockIdx.x, v.n, 3), import_block_tensor(imp.dL_dnormal, g.dL_dnormal, blockIdx.x, v.n, 3);
+        import_block_tensor(imp.dL_df0, g.dL_df0, blockIdx.x, v.n, 3), import_block_tensor(imp.dL_droughness, g.dL_droughness, blockIdx.x, v.n, 1);
+        import_block_tensor(imp.dL_dopacity, g.dL_dopacity, blockIdx.x, v.n, 1), import_block_tensor(imp.dL_dscale, g.dL_dscale, blockIdx.x, v.n, 3);
+        import_block_tensor(imp.dL_dmean, g.dL_dmean, blockIdx.x, v.n, 3), import_block_tensor(imp.dL_drotation, g.dL_drotation, blockIdx.x, v.n, 4);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1442,11 +1479,14 @@ __global__ void k_copy3(const float *__restrict__ src, float *__restrict__ dst, 
 
 // The chain kernels of the code object in the order it has always held them - the order of their first use, which this table now is (the compiler
 // reports under profiles/ and the profiling tools list the kernels in it; where a launch names them has no say in it any more).
-[[maybe_unused]] void (*const chain_kernel_order[])(DeviceView) = {
-    k_forward_chain<true, false, 1>, k_forward_chain<true, false, EGR_TEAM>, k_backward_chain<1>, k_forward_chain<true, true, EGR_TEAM>, k_forward_chain<false, true, EGR_TEAM>, k_forward_chain<false, false, EGR_TEAM>,
-    k_forward_chain<true, true, 1>, k_forward_chain<false, true, 1>, k_forward_chain<false, false, 1>, k_backward_chain<EGR_BWD_TEAM>, k_grad_gather<true>, k_grad_gather<false>,
-    k_forward_batch<true, EGR_TEAM>, k_forward_batch<false, EGR_TEAM>, k_forward_batch<true, 1>, k_forward_batch<false, 1>, k_forward_batch_grads<true, EGR_TEAM>, k_forward_batch_grads<false, EGR_TEAM>,
-    k_forward_batch_grads<true, 1>, k_forward_batch_grads<false, 1>, k_backward_batch<EGR_BWD_TEAM>, k_backward_batch<1>};
+[[maybe_unused]] const void *const chain_kernel_order[] = {
+#define K(...) reinterpret_cast<const void *>(&__VA_ARGS__)
+    K(k_forward_chain<true, false, 1>), K(k_forward_chain<true, false, EGR_TEAM>), K(k_backward_chain<1>), K(k_forward_chain<true, true, EGR_TEAM>), K(k_forward_chain<false, true, EGR_TEAM>), K(k_forward_chain<false, false, EGR_TEAM>),
+    K(k_forward_chain<true, true, 1>), K(k_forward_chain<false, true, 1>), K(k_forward_chain<false, false, 1>), K(k_backward_chain<EGR_BWD_TEAM>), K(k_grad_gather<true, false>), K(k_grad_gather<false, false>),
+    K(k_forward_batch<true, EGR_TEAM>), K(k_forward_batch<false, EGR_TEAM>), K(k_forward_batch<true, 1>), K(k_forward_batch<false, 1>), K(k_forward_batch_grads<true, EGR_TEAM>), K(k_forward_batch_grads<false, EGR_TEAM>),
+    K(k_forward_batch_grads<true, 1>), K(k_forward_batch_grads<false, 1>), K(k_backward_batch<EGR_BWD_TEAM>), K(k_backward_batch<1>), K(k_grad_gather<false, true>)
+#undef K
+};
 
 } // namespace
 
@@ -1661,8 +1701,14 @@ void launch_begin(egr_context *c, const DeviceView &v, bool grads, bool live_fre
     } else {
         hipLaunchKernelGGL(k_prologue, dim3(1), dim3(64), 0, s, v, grads ? 1 : 0);
     }
-    EGR_HIP(hipMemsetAsync(c->stats.num_accumulated_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s)); // stats.h:25-28
-    EGR_HIP(hipMemsetAsync(c->stats.num_traversed_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
+    // stats.h:25-28. A launch whose tasks cover the whole image stores both counts of EVERY pixel at step 0 (forward_task.inc: `active` is `inside` there; a batch:
+    // in its last frame, which always runs), so clearing them first is a pass over 8 B per pixel for nothing. A rank of a partition and a masked launch leave
+    // pixels out, a rank without tasks all of them: those clear as ever.
+    const bool stores_every_pixel = c->world == 1 && c->pixel_mask == nullptr && v.num_tasks != 0;
+    if (!stores_every_pixel) {
+        EGR_HIP(hipMemsetAsync(c->stats.num_accumulated_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
+        EGR_HIP(hipMemsetAsync(c->stats.num_traversed_per_pixel, 0, sizeof(int32_t) * v.num_pixels, s));
+    }
     // (skipped when the egr_update_bvh_ex(EGR_UPDATE_FUSE_LIVE) just before this launch wrote the same records from the same parameters)
     if (v.n && !live_fresh) hipLaunchKernelGGL(k_live, dim3((v.n + 255) / 256), dim3(256), 0, s, v, grads ? 1 : 0);
     egr_stamp_end(c, s);
@@ -1720,13 +1766,15 @@ void launch_backward_chain(egr_context *c, const DeviceView &v, uint32_t tasks, 
 }
 
 // The last step of a grad launch: the gradient rows to the caller's tensors.
-void launch_grad_gather(egr_context *c, const DeviceView &v, hipStream_t s) {
-    if (!(v.n && (v.num_tasks || c->grad_overwrite))) return; // (a rank without tiles still owes its per-launch buffer a row of zeros)
+void launch_grad_gather(egr_context *c, const DeviceView &v, const EgrGradImport *imp, hipStream_t s) {
+    if (!(v.n && (v.num_tasks || c->grad_overwrite || imp))) return; // (a rank without tiles still owes its per-launch buffer a row of zeros, an importing caller what the holder has)
     egr_stamp_begin(c, "backward_grad_gather", s);
     // (per-launch buffer: the FIRST grad launch after the caller consumed the buffer stores, any further one before the next
     // egr_grad_delta_consumed adds - two launches before a fold never drop the first one's gradients)
-    if (v.grad_overwrite) hipLaunchKernelGGL(k_grad_gather<true>, dim3((v.n + 255u) / 256u), dim3(256), 0, s, v);
-    else hipLaunchKernelGGL(k_grad_gather<false>, dim3((v.n + 255u) / 256u), dim3(256), 0, s, v);
+    // (egr_raytrace_import refuses a context with a per-launch buffer: an importing launch always adds)
+    if (imp) hipLaunchKernelGGL((k_grad_gather<false, true>), dim3((v.n + 255u) / 256u), dim3(256), 0, s, v, *imp);
+    else if (v.grad_overwrite) hipLaunchKernelGGL((k_grad_gather<true, false>), dim3((v.n + 255u) / 256u), dim3(256), 0, s, v, EgrGradImport{});
+    else hipLaunchKernelGGL((k_grad_gather<false, false>), dim3((v.n + 255u) / 256u), dim3(256), 0, s, v, EgrGradImport{});
     egr_stamp_end(c, s);
     if (c->grad_overwrite) c->delta_pending = true;
 }
@@ -1748,7 +1796,7 @@ template <class T, void (*KERNEL)(DeviceView, T *)> void export_per_step(egr_con
 
 } // namespace
 
-void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s) {
+void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s, const EgrGradImport *import_into) {
     const DeviceView v = egr_make_view(c);
     launch_begin(c, v, grads, live_fresh, nullptr, s);
     if (v.num_tasks) {
@@ -1761,7 +1809,7 @@ void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s
             egr_stamp_end(c, s);
         }
     }
-    if (grads) launch_grad_gather(c, v, s);
+    if (grads) launch_grad_gather(c, v, import_into, s);
     hipLaunchKernelGGL(k_epilogue, dim3(1), dim3(64), 0, s, v, grads ? 1 : 0);
 }
 
@@ -1810,7 +1858,7 @@ void egr_render_views_launch(egr_context *c, const egr_view_batch *b, bool live_
 // records every frame's hits into the batch arena, k_order_backward over the same (tasks x frames), and the backward chain over them - all three with the
 // frame in the task index. Prologue, stats reset, k_live, k_grad_gather and the epilogue run once per call, so the chunks' gradients meet in the gradient
 // rows and leave them in ONE gather (the whole batch is one grad launch for the per-launch buffer).
-void egr_train_views_launch(egr_context *c, const egr_train_batch *b, bool live_fresh, hipStream_t s) {
+void egr_train_views_launch(egr_context *c, const egr_train_batch *b, bool live_fresh, hipStream_t s, const EgrGradImport *import_into) {
     const uint32_t V = b->num_views;
     const uint32_t B = std::min(V, std::max(1u, c->batch_frames));
     egr_batch_reserve(c, B, V);
@@ -1838,7 +1886,7 @@ void egr_train_views_launch(egr_context *c, const egr_train_batch *b, bool live_
         launch_forward_chain(c, v, v.num_tasks * v.batch_frames, ForwardKernel::batch_grads, s);
         launch_backward_chain(c, v, v.num_tasks * v.batch_frames, true, s);
     }
-    launch_grad_gather(c, v, s);
+    launch_grad_gather(c, v, import_into, s);
     hipLaunchKernelGGL(k_batch_epilogue, dim3(1), dim3(64), 0, s, v, V);
 }
 

@@ -145,6 +145,35 @@ class GaussianRaytracer:
                              [self.pc._get_scaling, self.pc._get_rotation, self.pc.get_xyz, self.pc._opacity, self.pc.get_diffuse, self.pc.get_normal,
                               self.pc.get_roughness, self.pc.get_f0])
 
+    @staticmethod
+    def _like_holder(tensors, holders, aligned=()):
+        """The native checks of update_bvh_from / raytrace(import_into=...): contiguous fp32 tensors on the holder's device with the holder's shapes."""
+        ok = lambda t, h: isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == h.device and t.shape == h.shape and t.is_contiguous()
+        return all(ok(t, h) for t, h in zip(tensors, holders)) and all(tensors[k].data_ptr() % 16 == 0 for k in aligned)
+
+    @torch.no_grad()
+    def _export_and_update_bvh(self):
+        """`_export_param_values()` + `update_bvh(True)`: one native pass that reads the model's tensors, leaves their values in the holder's and refits
+        (update_bvh_from). An editing model exports through its own launch, and tensors the native checks would refuse take the two calls."""
+        m = self.cuda_module
+        if not hasattr(self.pc, "export_edited"):
+            g = m.get_gaussians()
+            src = [self.pc._get_scaling, self.pc._get_rotation, self.pc.get_xyz, self.pc._opacity, self.pc.get_diffuse, self.pc.get_normal, self.pc.get_roughness, self.pc.get_f0]
+            if self._like_holder(src, [g.scale, g.rotation, g.mean, g.opacity, g.rgb, g.normal, g.roughness, g.f0], aligned=(1,)):
+                m.update_bvh_from(*src, True)
+                return
+        self._export_param_values()
+        m.update_bvh(True)
+
+    def _import_target(self):
+        """The model's eight .grad tensors when the grad launch itself can add to them (raytrace(import_into=...)), else None: the caller imports. A tracer
+        with a per-launch buffer (a partition) reduces between the launch and the import, so it never fuses."""
+        g = self.cuda_module.get_gaussians()
+        if not self.import_grads or g.grad_delta.numel() != 0:
+            return None
+        dst = [p.grad for p in (self.pc._scaling, self.pc._rotation, self.pc._xyz, self.pc._opacity, self.pc._diffuse, self.pc._normal, self.pc._roughness, self.pc._f0)]
+        return dst if self._like_holder(dst, [g.scale, g.rotation, g.mean, g.opacity, g.rgb, g.normal, g.roughness, g.f0]) else None
+
     @torch.no_grad()
     def _import_param_gradients(self):  # gaussian_raytracer.py:53-62
         g = self.cuda_module.get_gaussians()
@@ -207,24 +236,27 @@ class GaussianRaytracer:
     def __call__(self, viewpoint_camera, target=None, target_diffuse=None, target_specular=None, target_depth=None, target_normal=None,
                  target_roughness=None, target_f0=None, force_update_bvh=False, denoise=False, znear=0.01, zfar=999.9, eval_mode=None):
         assert eval_mode is None or eval_mode in self.EVAL_MODES, eval_mode
+        grads = torch.is_grad_enabled()
+        refit = grads or force_update_bvh  # (then the export below is part of the refit's pass)
         with torch.no_grad():
             R = torch.from_numpy(viewpoint_camera.R).cuda().float() if isinstance(viewpoint_camera.R, np.ndarray) else viewpoint_camera.R.cuda()
             # gaussian_raytracer.py:94-100 (R_c2w_blender = blender_rotation(R); znear / zfar / fov fill_; set_pose(camera_center, R_c2w_blender)) as ONE launch
             self.cuda_module.set_camera(R, viewpoint_camera.camera_center, float(viewpoint_camera.FoVy), float(os.getenv("ZNEAR", znear)), float(os.getenv("ZFAR", zfar)))
-            self._export_param_values()
+            if not refit:
+                self._export_param_values()
             framebuffer = self.cuda_module.get_framebuffer()
             # CHW -> HWC into framebuffer.target_*, zeros when absent (gaussian_raytracer.py:109-137: six copy_ / zero_ calls) - as ONE launch over the
             # pixels of this rank's own tiles (egr_set_targets_chw; the kernel waits for nothing: a temporary's memory is stream-ordered)
             self.cuda_module.set_targets_chw(target_diffuse, target_specular, target_depth, target_normal, target_roughness, target_f0)
-        grads = torch.is_grad_enabled()
-        if grads or force_update_bvh:
-            # raytrace() follows with the same parameter values: one pass over the cloud writes the snapshot AND the live records
-            self.cuda_module.update_bvh(True)
+        if refit:
+            # raytrace() follows with the same parameter values: one pass over the cloud exports them, writes the snapshot AND the live records
+            self._export_and_update_bvh()
         gathered = not grads and self._partitioned_eval(eval_mode)  # (a collective follows: every rank of the group makes this call - or pass eval_mode="full_image")
         if not grads and not gathered:
             self._set_full_image(True)
+        import_into = self._import_target() if grads else None  # (the launch's gather adds to the model's .grad itself)
         try:
-            self.cuda_module.raytrace()
+            self.cuda_module.raytrace(import_into)
         finally:  # a raytrace that raises (stale BVH, exact-stats gate) must not leave a training rank tracing the whole image
             if not grads and not gathered:
                 self._set_full_image(False)
@@ -234,7 +266,7 @@ class GaussianRaytracer:
             self.cuda_module.denoise()
         if grads:
             self.all_reduce_grads()
-            if self.import_grads:
+            if self.import_grads and import_into is None:
                 self._import_param_gradients()
         return {"render": framebuffer.output_rgb.clone()}
 
@@ -330,11 +362,11 @@ def train_views(cameras, raytracer: GaussianRaytracer, targets_available=True, z
                 continue
             zeros = torch.zeros((ch, H, W), dtype=torch.float32, device="cuda")
             targets.append(torch.stack([zeros if t is None else torch.as_tensor(t).to("cuda", torch.float32) for t in imgs]).contiguous())
-        raytracer._export_param_values()
-        m.update_bvh(True)  # the launch follows with the same parameter values (fused live records)
-        m.train_views(R, centers, fovy, float(os.getenv("ZNEAR", znear)), float(os.getenv("ZFAR", zfar)), *targets)
+        raytracer._export_and_update_bvh()  # the launch follows with the same parameter values (fused live records)
+        import_into = raytracer._import_target()
+        m.train_views_import(R, centers, fovy, float(os.getenv("ZNEAR", znear)), float(os.getenv("ZFAR", zfar)), *targets, import_into)
     raytracer.all_reduce_grads()
-    if raytracer.import_grads:
+    if raytracer.import_grads and import_into is None:
         raytracer._import_param_gradients()
 
 

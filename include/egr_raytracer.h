@@ -153,12 +153,25 @@ int egr_update_bvh(egr_context *ctx, void *hip_stream);
  * reads the live parameters again as usual. One pass of ~130 B per gaussian less per training iteration. */
 #define EGR_UPDATE_FUSE_LIVE 1u
 int egr_update_bvh_ex(egr_context *ctx, unsigned flags, void *hip_stream);
+/* Export and refit in one pass (an additive symbol of library version 0.8): egr_update_bvh_ex(flags) for a caller whose current parameter values are in tensors
+ * of its OWN. The pass over the cloud reads the eight parameter pointers of `src` (count rows of the bound gaussians, fp32, contiguous, device memory, rotation
+ * 16-byte aligned; nothing else of `src` is read), stores what it read to the bound parameter tensors - they then hold what eight copies from `src` would leave,
+ * bit for bit - and snapshots the transforms from the same values. A pointer of `src` that equals the bound one is not stored. `flags` as for egr_update_bvh_ex.
+ * With a count of 0 the pointers are not read and may be NULL. A NULL src or parameter pointer, a misaligned rotation and an unknown flag return non-zero with an egr_last_error message before anything is launched. */
+int egr_update_bvh_from(egr_context *ctx, const egr_gaussians *src, unsigned flags, void *hip_stream);
 
 /* Raytracer::raytrace (raytracer.cpp:81-94): metadata update, stats reset, one launch of the whole
  * forward (+ backward when grads_enabled) path = __raygen__rg (shaders.cu:77-173), then
  * accumulated_sample_count += 1 when accumulate_samples. grads_enabled is what
  * torch::autograd::GradMode::is_enabled() returned in the caller (metadata.h:29). Asynchronous. */
 int egr_raytrace(egr_context *ctx, int grads_enabled, void *hip_stream);
+/* Gather and import in one pass (an additive symbol of library version 0.8): egr_raytrace(grads_enabled = 1) for a caller that adds the bound gradient tensors
+ * to gradient tensors of its own after every launch. Only the eight dL_d* pointers of `dst` are read (count rows each, fp32, contiguous, device memory). The
+ * launch's last kernel leaves in the bound tensors what egr_raytrace leaves there and adds every value it leaves - the ACCUMULATED one, also of gaussians the
+ * launch did not hit - to dst's: the result of `dst.dL_dX += bound.dL_dX` for the eight tensors after the launch, bit for bit. total_weight is not imported.
+ * With a count of 0 the pointers are not read and may be NULL. Refused (non-zero, egr_last_error, nothing launched): a NULL dst or dL_d* pointer, a dL_d* pointer that is the bound one, and a context with
+ * egr_set_grad_overwrite on (a partition reduces its per-launch buffer before anything is imported). */
+int egr_raytrace_import(egr_context *ctx, const egr_gaussians *dst, void *hip_stream);
 
 /* Camera upload (replaces the caller's ten tiny tensor kernels of renderer/gaussian_raytracer.py:94-100, which stay valid): rotation_c2w_dataset =
  * the dataset's camera-to-world rotation `viewpoint_camera.R` (row-major 3x3 fp32), camera_center = `viewpoint_camera.camera_center` (3 fp32), both DEVICE
@@ -325,6 +338,8 @@ typedef struct egr_train_batch {
  * EGR_STATUS_HIT_ARENA_OVERFLOW, never silent) and 80 B per 8x8 tile and frame of per-task tables. Wrong arguments (V == 0, a NULL camera array), a stale
  * tree and the exact-stats gate return non-zero with an egr_last_error message and write nothing. */
 int egr_train_views(egr_context *ctx, const egr_train_batch *batch, void *hip_stream);
+/* The same with the import of egr_raytrace_import in the batch's one gather (dst as there; NULL: egr_train_views). */
+int egr_train_views_import(egr_context *ctx, const egr_train_batch *batch, const egr_gaussians *dst, void *hip_stream);
 
 /* Synchronises the stream and returns the work counters / status of the most recent egr_raytrace.
  * ABI: egr_counters only ever GROWS AT ITS END (version string of egr_version() bumps with it). egr_get_counters writes
@@ -345,6 +360,10 @@ int egr_last_kernel_ms(egr_context *ctx, float *ms, const char **names, int max_
 /* Copies the snapshot instance records for parity tests: M[N*12], W[N*12] (3x4 row-major), aabb[N*6]
  * (lo xyz, hi xyz; invisible instances have lo > hi). Host pointers; synchronises. */
 int egr_debug_get_instances(egr_context *ctx, float *M, float *W, float *aabb, void *hip_stream);
+/* Debug: the 64-B backward record of every gaussian, by gaussian id, on the host: out[n][4][4] = rows 0-2 (row of M as of the last update / rebuild, exp(scale_a)
+ * as of the last grad launch or update), row 3 the raw quaternion (likewise). n = the count the tree was last built for (egr_debug_get_bvh_state: info[3]).
+ * Synchronises the stream. */
+int egr_debug_get_backward_records(egr_context *ctx, float *out, void *hip_stream);
 /* Composited hits per pixel and bounce step of the last egr_raytrace with grads_enabled (what backward_pass.cu:38-45 calls
  * num_hits[step]; the reference keeps it in registers, stats.num_accumulated_per_pixel only shows the last step): host_out =
  * int32 [EGR_NUM_STEPS][H*W], host pointer; pixels outside this context's partition read 0. Parity tests use it to LIST the
