@@ -189,6 +189,7 @@ def lib(path=None):
         L.egr_update_bvh_ex.argtypes = [P, C.c_uint, P]
         L.egr_update_bvh_from.argtypes = [P, C.POINTER(egr_gaussians), C.c_uint, P]  # ctx, src (its eight parameter pointers), flags, stream
         L.egr_raytrace_import.argtypes = [P, C.POINTER(egr_gaussians), P]  # ctx, dst (its eight dL_d* pointers), stream
+        L.egr_raytrace_targets.argtypes = [P, C.c_int, C.POINTER(egr_gaussians), C.POINTER(P * 6), P]  # ctx, grads_enabled, dst or NULL, six target images or NULL, stream
         L.egr_debug_get_backward_records.argtypes = [P, P, P]  # ctx, host out [n][4][4] floats, stream
         L.egr_set_partition.argtypes = [P, C.c_int, C.c_int]
         L.egr_set_exact_stats.argtypes = [P, C.c_int]
@@ -293,6 +294,14 @@ class RawRaytracer:
         device addresses of the caller's eight gradient arrays (GAUSSIAN_GRADS without total_weight)."""
         dst = egr_gaussians(count=self.g.count, **{k: pointers[k] for k in GAUSSIAN_GRADS[:8]})
         self._check(self.L.egr_raytrace_import(self.ctx, C.byref(dst), self.stream))
+
+    def raytrace_targets(self, grads_enabled=True, import_into=None, targets=None):
+        """egr_raytrace_targets: a launch that reads its target images where the caller keeps them. `import_into`: as raytrace_import's `pointers`, or
+        None; `targets`: six integer device addresses of contiguous fp32 [C,H,W] images in the order of TRAIN_BATCH_TARGETS (None / 0 = absent = zeros), or None for the
+        framebuffer's target buffers. The images must stay valid and unmodified until the launch has completed."""
+        dst = None if import_into is None else C.byref(egr_gaussians(count=self.g.count, **{k: import_into[k] for k in GAUSSIAN_GRADS[:8]}))
+        planes = None if targets is None else C.byref((C.c_void_p * 6)(*[t or None for t in targets]))
+        self._check(self.L.egr_raytrace_targets(self.ctx, 1 if grads_enabled else 0, dst, planes, self.stream))
 
     def render_views(self, num_views, samples_per_view, rotation_c2w_dataset, camera_center, vertical_fov_radians, znear=0.01, zfar=999.9, **outputs):
         """egr_render_views: the camera arrays and `outputs` (final= required; rgb=, depth=, normal=, f0=, roughness= optional) are integer

@@ -279,6 +279,27 @@ int egr_raytrace_import(egr_context *c, const egr_gaussians *dst, void *stream) 
     return traced(c, stream, [&](hipStream_t s) { egr_trace_launch(c, true, live_fresh, s, &imp); });
 }
 
+// A launch with its optional extras: the import of egr_raytrace_import (dst) and the six target images read in place (targets). Both need a grad launch.
+int egr_raytrace_targets(egr_context *c, int grads_enabled, const egr_gaussians *dst, const float *const *targets, void *stream) {
+    if (!c) return 1;
+    const bool live_fresh = c->live_fresh; // (consumed as by egr_raytrace)
+    c->live_fresh = false;
+    if (!grads_enabled && targets) {
+        c->last_error = "libegr_hip: egr_raytrace_targets: targets need a grad launch (a no-grad launch reads no target)";
+        return 1;
+    }
+    if (!grads_enabled && dst) {
+        c->last_error = "libegr_hip: egr_raytrace_targets: dst needs a grad launch (a no-grad launch has no gradients to import)";
+        return 1;
+    }
+    EgrGradImport imp{};
+    if (dst && import_target(c, "egr_raytrace_targets", dst, imp)) return 1;
+    EgrTargetPlanes planes{};
+    if (targets)
+        for (int k = 0; k < 6; k++) planes.chw[k] = targets[k];
+    return traced(c, stream, [&](hipStream_t s) { egr_trace_launch(c, grads_enabled != 0, live_fresh, s, dst ? &imp : nullptr, targets ? &planes : nullptr); });
+}
+
 int egr_render_views(egr_context *c, const egr_view_batch *b, void *stream) {
     if (!c) return 1;
     const bool live_fresh = c->live_fresh; // (consumed as by egr_raytrace: the batch's first chunk may use the live records of a fused update)

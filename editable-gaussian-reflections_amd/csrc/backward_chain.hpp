@@ -68,13 +68,15 @@ EGR_DI RayGrads output_gradients(const DeviceView &v, const BwdWave<TEAM> &W, co
                 g.dL_f0 = mk3(third * sign1(o_f0.x - tgt(5, 3, 0)), third * sign1(o_f0.y - tgt(5, 3, 1)), third * sign1(o_f0.z - tgt(5, 3, 2))) * *v.cfg.loss_weight_f0;
                 g.dL_rough = sign1(o_rough - tgt(4, 1, 0)) * *v.cfg.loss_weight_roughness;
             } else {
-                const float *td = v.fb.target_diffuse + 3 * (size_t)pid, *tn = v.fb.target_normal + 3 * (size_t)pid,
-                            *tf = v.fb.target_f0 + 3 * (size_t)pid;
-                g.dL_rgb = mk3(third * sign1(o_rgb.x - td[0]), third * sign1(o_rgb.y - td[1]), third * sign1(o_rgb.z - td[2])) * *v.cfg.loss_weight_diffuse;
-                g.dL_depth = sign1(o_depth - v.fb.target_depth[pid]) * *v.cfg.loss_weight_depth;
-                g.dL_n = mk3(third * sign1(o_n.x - tn[0]), third * sign1(o_n.y - tn[1]), third * sign1(o_n.z - tn[2])) * *v.cfg.loss_weight_normal;
-                g.dL_f0 = mk3(third * sign1(o_f0.x - tf[0]), third * sign1(o_f0.y - tf[1]), third * sign1(o_f0.z - tf[2])) * *v.cfg.loss_weight_f0;
-                g.dL_rough = sign1(o_rough - v.fb.target_roughness[pid]) * *v.cfg.loss_weight_roughness;
+                // the framebuffer's pixel-major buffers, or the caller's channel-major images in place (NULL: zeros): one set of loads, two launch-uniform strides
+                const bool planes = v.target_planes != 0u;
+                const size_t cs = planes ? (size_t)v.num_pixels : (size_t)1;
+                auto tgt = [&](int b, uint32_t ch, uint32_t c) { const float *p = v.batch_targets[b]; return p ? p[(size_t)pid * (planes ? 1u : ch) + c * cs] : 0.0f; };
+                g.dL_rgb = mk3(third * sign1(o_rgb.x - tgt(0, 3, 0)), third * sign1(o_rgb.y - tgt(0, 3, 1)), third * sign1(o_rgb.z - tgt(0, 3, 2))) * *v.cfg.loss_weight_diffuse;
+                g.dL_depth = sign1(o_depth - tgt(2, 1, 0)) * *v.cfg.loss_weight_depth;
+                g.dL_n = mk3(third * sign1(o_n.x - tgt(3, 3, 0)), third * sign1(o_n.y - tgt(3, 3, 1)), third * sign1(o_n.z - tgt(3, 3, 2))) * *v.cfg.loss_weight_normal;
+                g.dL_f0 = mk3(third * sign1(o_f0.x - tgt(5, 3, 0)), third * sign1(o_f0.y - tgt(5, 3, 1)), third * sign1(o_f0.z - tgt(5, 3, 2))) * *v.cfg.loss_weight_f0;
+                g.dL_rough = sign1(o_rough - tgt(4, 1, 0)) * *v.cfg.loss_weight_roughness;
             }
             // the primary ray is regenerated from the seed instead of being stored (a batch: its view's camera record and the seed base of its frame)
             const PrimaryRay p = primary_ray<BATCH>(v, tg, task, W.view_size);
@@ -89,8 +91,9 @@ EGR_DI RayGrads output_gradients(const DeviceView &v, const BwdWave<TEAM> &W, co
                 const size_t P = v.num_pixels, q = (size_t)task.bframe * 3 * P + pid;
                 t_spec = p ? mk3(p[q], p[q + P], p[q + 2 * P]) : mk3(0, 0, 0);
             } else {
-                const float *ts = v.fb.target_specular + 3 * (size_t)pid;
-                t_spec = mk3(ts[0], ts[1], ts[2]);
+                const float *p = v.batch_targets[1]; // (pixel-major or planes, as the primary step's)
+                const size_t q = (size_t)pid * (v.target_planes ? 1u : 3u), cs = v.target_planes ? (size_t)v.num_pixels : (size_t)1;
+                t_spec = p ? mk3(p[q], p[q + cs], p[q + 2 * cs]) : mk3(0, 0, 0);
             }
             float down = powf(1.0f - S.ld(SF(step - 1, S_ROUGH)), EGR_ROUGHNESS_DOWNWEIGHT_GRAD_POWER); // :11-13
             g.dL_rgb = (mk3(third * sign1(spec.x - t_spec.x), third * sign1(spec.y - t_spec.y), third * sign1(spec.z - t_spec.z)) *

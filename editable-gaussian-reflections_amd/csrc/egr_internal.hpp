@@ -128,8 +128,16 @@ struct DeviceView { // everything a kernel needs, passed by value
     uint32_t batch_spv;        // samples per view
     const float *batch_cams;   // [views][EGR_BATCH_CAM_FLOATS] camera records (k_batch_cameras)
     // multi-view training (egr_train_views; k_forward_batch_grads, k_backward_batch): frame = view (batch_spv = 1). The per-view targets, channel-major
-    // [V][C][H][W] as egr_train_batch holds them (diffuse, specular, depth, normal, roughness, f0; NULL: zeros). Read by the batch backward only.
+    // [V][C][H][W] as egr_train_batch holds them (diffuse, specular, depth, normal, roughness, f0; NULL: zeros).
+    // A single grad launch reads its targets through the same six pointers (backward_chain.hpp: output_gradients): the framebuffer's pixel-major target_*
+    // buffers (egr_make_view; target_planes = 0), or the caller's own channel-major [C][H][W] images read in place (egr_raytrace_targets; target_planes = 1,
+    // NULL: zeros). Read by the backward kernels only.
     const float *batch_targets[6];
+    uint32_t target_planes; // single launches: value (pixel, channel) of target b is at pixel * (planes ? 1 : C) + channel * (planes ? num_pixels : 1)
+};
+// The caller's six target images of a grad launch that reads them in place (egr_raytrace_targets): diffuse, specular, depth, normal, roughness, f0.
+struct EgrTargetPlanes {
+    const float *chw[6];
 };
 #define EGR_BATCH_CAM_FLOATS 16 // per view: origin (3), rows of w2c (9), tanf(fov / 2), pad (3)
 #define EGR_BATCH_CARRY_FLOATS (11 * EGR_NSTEPS) // running sums of a view across a chunk boundary, per pixel and step: rgb 3, depth 1, normal 3, f0 3, roughness 1
@@ -278,7 +286,7 @@ int egr_bvh_check(egr_context *c, hipStream_t s, std::string &msg);
 // trace.hip
 void egr_trace_alloc(egr_context *c);
 void egr_trace_free(egr_context *c);
-void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s, const EgrGradImport *import_into = nullptr); // import_into (grad launches): the gather also adds the holder's gradients to these
+void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s, const EgrGradImport *import_into = nullptr, const EgrTargetPlanes *targets = nullptr); // import_into (grad launches): the gather also adds the holder's gradients to these; targets (grad launches): read instead of the framebuffer's target_* buffers
 void egr_render_views_launch(egr_context *c, const egr_view_batch *b, bool live_fresh, hipStream_t s);
 void egr_train_views_launch(egr_context *c, const egr_train_batch *b, bool live_fresh, hipStream_t s, const EgrGradImport *import_into = nullptr);
 uint32_t egr_num_tasks_for_rank(const egr_context *c);

@@ -350,6 +350,22 @@ struct Raytracer : torch::CustomClassHolder {
     c10::intrusive_ptr<PPLLDataHolder> ppll_forward_data, ppll_backward_data;
     egr_context *ctx = nullptr;
     Tensor pixel_mask; // debug_set_pixel_mask: the mask the context points at
+    // raytrace(targets=...) read its images in place and left framebuffer.target_* BEHIND them. The images are remembered (referenced, not copied) until the next
+    // set_targets_chw, or until a grad raytrace() WITHOUT targets - a launch that reads framebuffer.target_* - uploads them first: the upload the in-place launch
+    // skipped is made only for a caller that goes on to need it (the reference's caller leaves its targets in the framebuffer, and a bare raytrace() after it reads them)
+    Tensor behind_targets[6];
+    bool framebuffer_targets_behind = false;
+    void forget_behind_targets() {
+        for (auto &t : behind_targets) t = Tensor();
+        framebuffer_targets_behind = false;
+    }
+    void upload_behind_targets() {
+        if (!framebuffer_targets_behind) return;
+        const float *p[6];
+        for (int k = 0; k < 6; k++) p[k] = behind_targets[k].defined() ? behind_targets[k].data_ptr<float>() : nullptr;
+        check(egr_set_targets_chw(ctx, p[0], p[1], p[2], p[3], p[4], p[5], current_stream()), "raytrace");
+        forget_behind_targets();
+    }
 
     void check(int rc, const char *what) {
         if (rc != 0) throw std::runtime_error(std::string(what) + ": " + (ctx ? egr_last_error(ctx) : "no context"));
@@ -395,15 +411,38 @@ struct Raytracer : torch::CustomClassHolder {
     }
     // import_into (addition; grad mode only): the caller's eight gradient tensors, in the order of update_bvh_from's parameters. The launch's gather adds what it
     // leaves in the holder's gradients to them - `t.grad += holder.grad` for the eight, bit for bit, without the extra pass (egr_raytrace_import).
-    void raytrace(c10::optional<std::vector<Tensor>> import_into) { // raytracer.cpp:81-94
+    // targets (addition; grad mode only): the view's six target images in set_targets_chw's order (diffuse, specular, depth, normal, roughness, f0), each None
+    // (absent = zeros) or a contiguous fp32 [C,H,W] tensor on the tracer's device. The launch reads them where they are - no upload, framebuffer.target_* is
+    // neither read nor written (egr_raytrace_targets). The caller keeps them alive and unmodified until the launch has completed on the current stream.
+    void raytrace(c10::optional<std::vector<Tensor>> import_into, c10::optional<std::vector<c10::optional<Tensor>>> targets) { // raytracer.cpp:81-94
         const bool grads = torch::autograd::GradMode::is_enabled();
-        if (!import_into.has_value()) {
+        if (grads && !targets.has_value()) upload_behind_targets(); // this launch reads framebuffer.target_*
+        if (!import_into.has_value() && !targets.has_value()) {
             check(egr_raytrace(ctx, grads ? 1 : 0, current_stream()), "raytrace");
             return;
         }
-        TORCH_CHECK(grads, "raytrace: import_into needs grad mode (a no-grad launch has no gradients to import)");
-        const egr_gaussians dst = import_target("raytrace", *import_into);
-        check(egr_raytrace_import(ctx, &dst, current_stream()), "raytrace");
+        TORCH_CHECK(grads || !import_into.has_value(), "raytrace: import_into needs grad mode (a no-grad launch has no gradients to import)");
+        TORCH_CHECK(grads || !targets.has_value(), "raytrace: targets need grad mode (a no-grad launch reads no target)");
+        egr_gaussians dst{};
+        if (import_into.has_value()) dst = import_target("raytrace", *import_into);
+        const float *planes[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (targets.has_value()) {
+            TORCH_CHECK(targets->size() == 6, "raytrace: six targets expected (diffuse, specular, depth, normal, roughness, f0; None = absent), got ", targets->size());
+            const auto dev = framebuffer_data->output_rgb.device();
+            for (int k = 0; k < 6; k++) {
+                if (!(*targets)[k].has_value() || !(*targets)[k]->defined()) continue;
+                const Tensor &t = *(*targets)[k];
+                const std::vector<int64_t> want{TARGETS[k].channels, height, width};
+                TORCH_CHECK(t.device() == dev && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.sizes() == torch::IntArrayRef(want), "raytrace: target '", TARGETS[k].name,
+                            "' must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " (channel-major) on the tracer's device, got ", t.sizes(), " ", t.scalar_type(), " on ", t.device());
+                planes[k] = t.data_ptr<float>();
+            }
+        }
+        check(egr_raytrace_targets(ctx, 1, import_into.has_value() ? &dst : nullptr, targets.has_value() ? planes : nullptr, current_stream()), "raytrace");
+        if (targets.has_value()) {
+            for (int k = 0; k < 6; k++) behind_targets[k] = (*targets)[k].has_value() ? *(*targets)[k] : Tensor();
+            framebuffer_targets_behind = true;
+        }
     }
     egr_gaussians import_target(const char *who, const std::vector<Tensor> &t) {
         check_like_holder(who, t);
@@ -485,6 +524,7 @@ struct Raytracer : torch::CustomClassHolder {
             p[b] = keep[b].data_ptr<float>();
         }
         check(egr_set_targets_chw(ctx, p[0], p[1], p[2], p[3], p[4], p[5], current_stream()), "set_targets_chw");
+        forget_behind_targets(); // the framebuffer's targets are what the caller says again
     }
     // batched no-grad render (egr_render_views): R [V,3,3] (dataset c2w rotations), centers [V,3], fovy [V] (any device, moved like set_camera's),
     // `outputs` = names among final / rgb / depth / normal / f0 / roughness. render_views allocates them (zeros) in the framebuffer's HWC layout with a
@@ -658,7 +698,7 @@ struct Raytracer : torch::CustomClassHolder {
         using Self = c10::intrusive_ptr<Raytracer>;
         m.class_<Raytracer>("Raytracer")
             .def(torch::init<int64_t, int64_t, int64_t, int64_t, int64_t>())
-            .def("raytrace", &Raytracer::raytrace, "", {torch::arg("import_into") = c10::IValue()})
+            .def("raytrace", &Raytracer::raytrace, "", {torch::arg("import_into") = c10::IValue(), torch::arg("targets") = c10::IValue()})
             .def("denoise", &Raytracer::denoise)
             .def("reset_accumulators", &Raytracer::reset_accumulators)
             .def("update_bvh", &Raytracer::update_bvh, "", {torch::arg("fuse_live") = false})

@@ -854,13 +854,13 @@ EGR_DI uint32_t grad_table_flush(const DeviceView &v, uint32_t *gt_keys, float *
 //      done with: the wave empties it (two records per used slot, counted in `records`) and looks its hits up again.
 // (1): called by the lanes that hold a hit (inside their divergent block: `__ballot(true)` is the set of them); returns whether this lane still owns a contribution.
 EGR_DI bool primary_presum(const uint32_t pos, float (&gx)[EGR_GT_COMPS], const int lane) {
+#pragma clang fp contract(off) // a gx[c] that is a product would otherwise be contracted with the add below into an fma on the FETCHED value: the product then has two uses, and the fetch stays a v_mov_b32_dpp
     bool mine = true;
     {
         const unsigned long long em = __ballot(true);
 #define EGR_FETCH_DPP(x, ctrl) __builtin_amdgcn_update_dpp(0, (int)(x), ctrl, 0xF, 0xF, false)
-#define EGR_FETCH_SWZ(x, pat) __builtin_amdgcn_ds_swizzle((int)(x), pat) // bit-mask mode: lane ^ xor inside a group of 32 (no LDS memory touched)
-#define EGR_FETCH_X32(x, unused) __shfl_xor((int)(x), 32)
-#define EGR_FETCH_DPP4(x, unused) __builtin_amdgcn_update_dpp(0, __builtin_amdgcn_update_dpp(0, (int)(x), 0x141, 0xF, 0xF, false), 0x1B, 0xF, 0xF, false)
+// The fetch is an operand of the ADD and the select picks sum or old value: the compiler folds the fetch into v_add_f32_dpp (one instruction, then one
+// v_cndmask). Selecting the fetched value first (gx += take ? o : 0) leaves v_mov_b32_dpp + v_cndmask + v_add, and costs 84 VALU instructions more per row.
 #define EGR_COMBINE(d, FETCH, arg)                                                                            \
     {                                                                                                          \
         const bool pact = ((em >> ((uint32_t)lane ^ (d))) & 1ull) != 0ull;                                     \
@@ -868,8 +868,8 @@ EGR_DI bool primary_presum(const uint32_t pos, float (&gx)[EGR_GT_COMPS], const 
         const bool same = pact && pmine != 0u && mine && ppos == pos;                                          \
         const bool take = same && ((uint32_t)lane & (d)) == 0u;                                                \
         _Pragma("unroll") for (int c = 0; c < EGR_GT_COMPS; c++) {                                             \
-            const float o = __int_as_float(FETCH(__float_as_int(gx[c]), arg));                                 \
-            gx[c] += take ? o : 0.0f;                                                                          \
+            const float s = gx[c] + __int_as_float(FETCH(__float_as_int(gx[c]), arg));                         \
+            gx[c] = take ? s : gx[c];                                                                          \
         }                                                                                                      \
         if (same && !take) mine = false;                                                                       \
     }
@@ -877,9 +877,6 @@ EGR_DI bool primary_presum(const uint32_t pos, float (&gx)[EGR_GT_COMPS], const 
         EGR_COMBINE(8u, EGR_FETCH_DPP, 0x128) // row_ror 8: lane ^ 8
 #undef EGR_COMBINE
 #undef EGR_FETCH_DPP
-#undef EGR_FETCH_SWZ
-#undef EGR_FETCH_X32
-#undef EGR_FETCH_DPP4
     }
     return mine;
 }
@@ -1667,6 +1664,10 @@ DeviceView egr_make_view(const egr_context *c) {
     v.cube_mode = c->exact_stats ? 1 : 0;
     v.pixel_mask = c->pixel_mask;
     v.grad_overwrite = (c->grad_overwrite && !c->delta_pending) ? 1 : 0;
+    // (a single grad launch reads the framebuffer's pixel-major targets unless its caller hands it planes: egr_trace_launch)
+    const float *const fbt[6] = {c->fb.target_diffuse, c->fb.target_specular, c->fb.target_depth, c->fb.target_normal, c->fb.target_roughness, c->fb.target_f0};
+    for (int k = 0; k < 6; k++) v.batch_targets[k] = fbt[k];
+    v.target_planes = 0u;
     return v;
 }
 
@@ -1796,8 +1797,12 @@ template <class T, void (*KERNEL)(DeviceView, T *)> void export_per_step(egr_con
 
 } // namespace
 
-void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s, const EgrGradImport *import_into) {
-    const DeviceView v = egr_make_view(c);
+void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s, const EgrGradImport *import_into, const EgrTargetPlanes *targets) {
+    DeviceView v = egr_make_view(c);
+    if (targets) { // the backward reads the caller's channel-major images where they are: no upload, the framebuffer's target_* buffers are not touched
+        for (int k = 0; k < 6; k++) v.batch_targets[k] = targets->chw[k];
+        v.target_planes = 1u;
+    }
     launch_begin(c, v, grads, live_fresh, nullptr, s);
     if (v.num_tasks) {
         launch_forward_chain(c, v, v.num_tasks, grads ? ForwardKernel::single_grads : ForwardKernel::single, s);

@@ -174,6 +174,15 @@ class GaussianRaytracer:
         dst = [p.grad for p in (self.pc._scaling, self.pc._rotation, self.pc._xyz, self.pc._opacity, self.pc._diffuse, self.pc._normal, self.pc._roughness, self.pc._f0)]
         return dst if self._like_holder(dst, [g.scale, g.rotation, g.mean, g.opacity, g.rgb, g.normal, g.roughness, g.f0]) else None
 
+    TARGET_CHANNELS = (3, 3, 1, 3, 1, 3)  # diffuse, specular, depth, normal, roughness, f0 (the order of set_targets_chw)
+
+    def _targets_in_place(self, images, device):
+        """The six target images as raytrace(targets=...) takes them - None (absent) or a contiguous fp32 [C,H,W] tensor on the tracer's device - or None
+        when one of them is anything else (a CPU tensor, a view, another dtype, an empty tensor): the caller uploads through set_targets_chw then."""
+        ok = lambda t, c: t is None or (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == device and t.is_contiguous()
+                                        and tuple(t.shape) == (c, self.image_height, self.image_width))
+        return list(images) if all(ok(t, c) for t, c in zip(images, self.TARGET_CHANNELS)) else None
+
     @torch.no_grad()
     def _import_param_gradients(self):  # gaussian_raytracer.py:53-62
         g = self.cuda_module.get_gaussians()
@@ -245,9 +254,13 @@ class GaussianRaytracer:
             if not refit:
                 self._export_param_values()
             framebuffer = self.cuda_module.get_framebuffer()
+            # A grad launch reads the six images where they are (raytrace(targets=...): no copy, framebuffer.target_* untouched) when each is absent or a
+            # tensor the native checks take. Otherwise, and for a no-grad render:
             # CHW -> HWC into framebuffer.target_*, zeros when absent (gaussian_raytracer.py:109-137: six copy_ / zero_ calls) - as ONE launch over the
             # pixels of this rank's own tiles (egr_set_targets_chw; the kernel waits for nothing: a temporary's memory is stream-ordered)
-            self.cuda_module.set_targets_chw(target_diffuse, target_specular, target_depth, target_normal, target_roughness, target_f0)
+            targets = self._targets_in_place([target_diffuse, target_specular, target_depth, target_normal, target_roughness, target_f0], framebuffer.output_rgb.device) if grads else None
+            if targets is None:
+                self.cuda_module.set_targets_chw(target_diffuse, target_specular, target_depth, target_normal, target_roughness, target_f0)
         if refit:
             # raytrace() follows with the same parameter values: one pass over the cloud exports them, writes the snapshot AND the live records
             self._export_and_update_bvh()
@@ -256,7 +269,7 @@ class GaussianRaytracer:
             self._set_full_image(True)
         import_into = self._import_target() if grads else None  # (the launch's gather adds to the model's .grad itself)
         try:
-            self.cuda_module.raytrace(import_into)
+            self.cuda_module.raytrace(import_into, targets)  # (`targets` holds the images until the launch is enqueued; their memory is stream-ordered)
         finally:  # a raytrace that raises (stale BVH, exact-stats gate) must not leave a training rank tracing the whole image
             if not grads and not gathered:
                 self._set_full_image(False)

@@ -172,6 +172,15 @@ int egr_raytrace(egr_context *ctx, int grads_enabled, void *hip_stream);
  * With a count of 0 the pointers are not read and may be NULL. Refused (non-zero, egr_last_error, nothing launched): a NULL dst or dL_d* pointer, a dL_d* pointer that is the bound one, and a context with
  * egr_set_grad_overwrite on (a partition reduces its per-launch buffer before anything is imported). */
 int egr_raytrace_import(egr_context *ctx, const egr_gaussians *dst, void *hip_stream);
+/* Targets read in place (an additive symbol of library version 0.8): egr_raytrace with, optionally, the import of egr_raytrace_import (dst as there; NULL: no
+ * import) and, optionally, the six target images of the view read where the caller keeps them (targets; NULL: the launch reads framebuffer.target_* like
+ * egr_raytrace). `targets` is an array of six DEVICE pointers in the order of egr_set_targets_chw - diffuse, specular, depth, normal, roughness, f0 - each a
+ * contiguous channel-major fp32 image [C][H][W] of the context's size with C = 3, 3, 1, 3, 1, 3; a NULL entry = the target is absent and reads zero (what
+ * egr_set_targets_chw writes for it). The array itself is read during the call; the images must stay valid and unmodified until the launch has completed on
+ * its stream. Such a launch neither reads nor writes framebuffer.target_* and launches nothing for the targets: it leaves what egr_set_targets_chw with the
+ * same six pointers followed by egr_raytrace(1) / egr_raytrace_import leaves, except in framebuffer.target_*. A context of a partition reads the pixels of
+ * its own tiles only. Refused (non-zero, egr_last_error, nothing launched): targets or dst with grads_enabled == 0, and what egr_raytrace_import refuses in dst. */
+int egr_raytrace_targets(egr_context *ctx, int grads_enabled, const egr_gaussians *dst, const float *const *targets, void *hip_stream);
 
 /* Camera upload (replaces the caller's ten tiny tensor kernels of renderer/gaussian_raytracer.py:94-100, which stay valid): rotation_c2w_dataset =
  * the dataset's camera-to-world rotation `viewpoint_camera.R` (row-major 3x3 fp32), camera_center = `viewpoint_camera.camera_center` (3 fp32), both DEVICE
