@@ -45,6 +45,10 @@ egr_view_batch = _struct("egr_view_batch", [("num_views", C.c_uint32), ("samples
 TRAIN_BATCH_TARGETS = ("target_diffuse", "target_specular", "target_depth", "target_normal", "target_roughness", "target_f0")
 egr_train_batch = _struct("egr_train_batch", [("num_views", C.c_uint32), ("rotation_c2w_dataset", _F), ("camera_center", _F), ("vertical_fov_radians", _F),
                                               ("znear", C.c_float), ("zfar", C.c_float)] + [(k, _F) for k in TRAIN_BATCH_TARGETS])
+# per-object coverage of one view (egr_object_masks): the camera of ONE view as egr_view_batch gives it, the membership words, the requested bits (host), outputs
+egr_object_mask_query = _struct("egr_object_mask_query", [("rotation_c2w_dataset", _F), ("camera_center", _F), ("vertical_fov_radians", _F), ("znear", C.c_float),
+                                                          ("zfar", C.c_float), ("row_bits", C.c_void_p), ("bits", C.POINTER(C.c_uint8)), ("num_bits", C.c_uint32),
+                                                          ("masks", _F), ("hit", C.c_void_p), ("top", C.c_void_p)])
 EGR_MAX_PRUNE_ARRAYS = 32
 EGR_PRUNE_ROWS_PER_WG = 1024
 egr_prune_array = _struct("egr_prune_array", [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_uint32)])
@@ -205,6 +209,7 @@ def lib(path=None):
         L.egr_set_team_help.argtypes = [P, C.c_int]
         L.egr_render_views.argtypes = [P, C.POINTER(egr_view_batch), P]
         L.egr_set_batch_frames.argtypes = [P, C.c_int]
+        L.egr_object_masks.argtypes = [P, C.POINTER(egr_object_mask_query), P]
         L.egr_train_views.argtypes = [P, C.POINTER(egr_train_batch), P]
         L.egr_train_views_import.argtypes = [P, C.POINTER(egr_train_batch), C.POINTER(egr_gaussians), P]
         L.egr_get_counters.argtypes = [P, C.POINTER(egr_counters), P]
@@ -323,6 +328,17 @@ class RawRaytracer:
         b = egr_train_batch(num_views=num_views, rotation_c2w_dataset=rotation_c2w_dataset, camera_center=camera_center, vertical_fov_radians=vertical_fov_radians,
                             znear=znear, zfar=zfar, **{k: targets.get(k) for k in TRAIN_BATCH_TARGETS})
         self._check(self.L.egr_train_views(self.ctx, C.byref(b), self.stream))
+
+    def object_masks(self, rotation_c2w_dataset, camera_center, vertical_fov_radians, row_bits, bits, masks, hit=None, top=None, znear=0.01, zfar=999.9):
+        """egr_object_masks: per-object coverage of one view. The camera arrays, `row_bits` (uint32 [count]), `masks` (fp32 [K][H][W]) and the optional `hit`
+        (uint32 [H][W]) / `top` (int32 [H][W]) are integer device addresses; `bits`: the K requested selection bits (host integers) in output order."""
+        bits = [int(b) for b in bits]
+        if any(b < 0 or b > 255 for b in bits):
+            raise ValueError(f"selection bits must fit a byte, got {bits}")
+        b8 = (C.c_uint8 * max(len(bits), 1))(*bits)
+        q = egr_object_mask_query(rotation_c2w_dataset=rotation_c2w_dataset, camera_center=camera_center, vertical_fov_radians=vertical_fov_radians, znear=znear, zfar=zfar,
+                                  row_bits=row_bits, bits=C.cast(b8, C.POINTER(C.c_uint8)), num_bits=len(bits), masks=masks, hit=hit, top=top)
+        self._check(self.L.egr_object_masks(self.ctx, C.byref(q), self.stream))
 
     def set_batch_frames(self, frames):
         self._check(self.L.egr_set_batch_frames(self.ctx, frames))

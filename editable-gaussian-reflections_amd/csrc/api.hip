@@ -334,6 +334,28 @@ int egr_train_views_import(egr_context *c, const egr_train_batch *b, const egr_g
     return traced(c, stream, [&](hipStream_t s) { egr_train_views_launch(c, b, live_fresh, s, dst ? &imp : nullptr); });
 }
 
+int egr_object_masks(egr_context *c, const egr_object_mask_query *q, void *stream) {
+    if (!c) return 1;
+    auto refuse = [&](const char *what) { // (before any HIP call: nothing was touched, a fused update's live records stay valid for the next launch)
+        c->last_error = std::string("libegr_hip: egr_object_masks: ") + what;
+        return 1;
+    };
+    if (!q) return refuse("the query must be non-NULL");
+    if (!q->rotation_c2w_dataset || !q->camera_center || !q->vertical_fov_radians) return refuse("the three camera arrays must be non-NULL");
+    if (!q->row_bits || !q->bits || !q->masks) return refuse("row_bits, bits and masks must be non-NULL");
+    if (q->num_bits == 0 || q->num_bits > EGR_MAX_EDIT_OBJECTS) return refuse("num_bits must be 1 .. EGR_MAX_EDIT_OBJECTS (32)");
+    uint32_t seen = 0u;
+    for (uint32_t j = 0; j < q->num_bits; j++) {
+        if (q->bits[j] >= 32) return refuse("a selection bit must be < 32");
+        if ((seen >> q->bits[j]) & 1u) return refuse("a selection bit was given twice");
+        seen |= 1u << q->bits[j];
+    }
+    if (c->exact_stats || c->boxes_are_cubes) return refuse("the context is in exact-statistics mode (egr_set_exact_stats): per-object coverage exists for the product tree only");
+    const bool live_fresh = c->live_fresh; // (consumed as by egr_raytrace)
+    c->live_fresh = false;
+    return traced(c, stream, [&](hipStream_t s) { egr_object_masks_launch(c, q, live_fresh, s); });
+}
+
 int egr_set_batch_frames(egr_context *c, int frames) {
     if (!c || frames < 1) return 1;
     c->batch_frames = (uint32_t)frames;

@@ -76,6 +76,23 @@ EGR_DI void step_epilogue_lane(const DeviceView &v, int step, bool grads, int nu
     S.st(F_SEED, u2f(seed));
     if (write_seed) v.meta.random_seeds[tg.pixel_id] = (int32_t)seed; // shaders.cu:172
 }
+
+// R4 of the primary step for ONE scalar channel whose composited sum is `c` (egr_object_masks, forward_task.inc): the operations of o_rgb above -
+// rem, the refined reciprocal, c * inv_norm, c + rem * (...) - unfused like them, so a coverage sum leaves here with the bits output_rgb[0] holds for a
+// model whose diffuse colour is the object's 0/1 indicator.
+struct MaskTail {
+    float rem, inv_norm;
+};
+EGR_DI MaskTail mask_tail(const float T, const float full_T, const float eps_forward_normalization) {
+    const float rem = T - full_T;
+    const float normalization = fmaxf(1.0f - T, eps_forward_normalization);
+    const float rnorm = egr_rcp_refined(normalization);
+    return MaskTail{rem, egr_div_rn(1.0f, normalization, rnorm)};
+}
+EGR_DI float mask_value(const float c, const MaskTail &t) {
+    const float r = c * t.inv_norm;
+    return c + t.rem * r;
+}
 } // namespace
 #ifdef EGR_CONTRACT_AFTER_EPILOGUE // trace.hip: back to the translation unit's default for what follows
 #pragma clang fp contract(fast)

@@ -231,6 +231,9 @@ struct egr_context {
     float *batch_carry = nullptr;      // [EGR_BATCH_CARRY_FLOATS][H*W]
     float *batch_cams = nullptr;       // [batch_cams_cap + 1][EGR_BATCH_CAM_FLOATS] (the last record holds znear, zfar)
     uint32_t batch_cams_cap = 0;
+    // per-object coverage (egr_object_masks): the query's membership words in record order, allocated by the first call, freed by egr_destroy
+    uint32_t *object_bits = nullptr;   // [object_bits_cap]
+    uint32_t object_bits_cap = 0;
     // multi-view training (egr_train_views): the hit arena and per-task tables of a grad chunk, allocated by the first call, freed by egr_destroy. A batch
     // has buffers of its own, so the debug exports (egr_debug_get_step_hits / _hit_sequence_hash) keep describing the last egr_raytrace
     uint32_t train_alloc_frames = 0;   // frames the buffers below hold
@@ -289,6 +292,7 @@ void egr_trace_free(egr_context *c);
 void egr_trace_launch(egr_context *c, bool grads, bool live_fresh, hipStream_t s, const EgrGradImport *import_into = nullptr, const EgrTargetPlanes *targets = nullptr); // import_into (grad launches): the gather also adds the holder's gradients to these; targets (grad launches): read instead of the framebuffer's target_* buffers
 void egr_render_views_launch(egr_context *c, const egr_view_batch *b, bool live_fresh, hipStream_t s);
 void egr_train_views_launch(egr_context *c, const egr_train_batch *b, bool live_fresh, hipStream_t s, const EgrGradImport *import_into = nullptr);
+void egr_object_masks_launch(egr_context *c, const egr_object_mask_query *q, bool live_fresh, hipStream_t s);
 uint32_t egr_num_tasks_for_rank(const egr_context *c);
 void egr_build_task_order(egr_context *c);
 DeviceView egr_make_view(const egr_context *c);

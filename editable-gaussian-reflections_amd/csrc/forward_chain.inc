@@ -1,4 +1,5 @@
-// k_forward_chain / k_forward_batch / k_forward_batch_grads: the kernel body (included into all three; expects GRADS, CUBE, TEAM and BATCH). A wave takes
+// k_forward_chain / k_forward_batch / k_forward_batch_grads / k_forward_objects: the kernel body (included into all four; expects GRADS, CUBE, TEAM, BATCH and
+// OBJ - with OBJ the query `oq` and the wave's coverage sums `oacc`: the primary step only, no step epilogue). A wave takes
 // tiles from the XCD queues and runs each through all its bounce steps. BATCH (the frames of egr_render_views, or with GRADS the views of egr_train_views,
 // which then record hits into the batch's own arena and per-task tables, sized for tasks x frames): task index tq =
 // ((macro-tile group) * batch_frames + frame) << task_shift | sub-task - the frames of one macro tile are adjacent, so the samples of a
@@ -43,7 +44,7 @@
             // R4 / R5 of this step for the tile's rays
             const TaskGeom etg = task_geom(v, tb, lane);
             EGR_STATS(const unsigned long long tepi0 = __builtin_amdgcn_s_memtime();)
-            if (etg.inside) step_epilogue_lane(v, step, GRADS, num_bounces, etg, state_of(v, tq, lane), last_frame);
+            if (!OBJ && etg.inside) step_epilogue_lane(v, step, GRADS, num_bounces, etg, state_of(v, tq, lane), last_frame);
             EGR_STATS(tepi += __builtin_amdgcn_s_memtime() - tepi0;)
             EGR_TIMES_IS(9, chain_t[step + 1] = __builtin_amdgcn_s_memrealtime();)
         }

@@ -32,6 +32,6 @@
     const float transmittance_threshold = *v.cfg.transmittance_threshold;
     const float backfacing_max_dist = *v.cfg.backfacing_max_dist;
     const float backfacing_thr = *v.cfg.backfacing_invalid_normal_threshold;
-    const int num_bounces = min(*v.cfg.num_bounces, EGR_MAX_BOUNCES);
+    const int num_bounces = OBJ ? 0 : min(*v.cfg.num_bounces, EGR_MAX_BOUNCES); // (k_forward_objects: the primary step only, whatever the config says)
     const float far_plane = *v.cam.zfar;
     const FwdConst fc{exp_power, transmittance_threshold, backfacing_max_dist, backfacing_thr, far_plane, num_bounces, sentinels, app, wnodes};

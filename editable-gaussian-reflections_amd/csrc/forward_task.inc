@@ -1,11 +1,15 @@
 // k_forward_chain: ONE bounce step of ONE tile (R1 ray, R2 traversal + candidate evaluation, R3 compositing, raw step results).
 // Included into the task loop of the kernel; expects `step`, `tq`, `tb`, `near_plane`, GRADS, CUBE, BATCH (`bframe`, `bcam`, `last_frame`) and forward_decl.inc.
-// A `continue` ends this step of this tile.
+// A `continue` ends this step of this tile. OBJ (k_forward_objects: `oq`, `oacc`): the primary step composites per-object coverage instead of the appearance
+// and writes the query's outputs at the tile's end; it keeps no ray state and touches neither statistic.
         const uint32_t task = tq;
         const TaskGeom tg = task_geom(v, tb, lane); // (tb == tq outside a batch)
         const StateRef S = state_of(v, task, lane);
         const size_t chain_head = (size_t)step * (BATCH ? v.num_tasks * v.batch_frames : v.num_tasks) + task; // (a batch's task index carries the frame: its tables hold tasks x frames per step)
         if (GRADS && lane == 0) v.task_last_block[chain_head] = 0xFFFFFFFFu; // nothing recorded yet
+        if constexpr (OBJ) { // (k_forward_objects) this lane's coverage sums start at +0: oacc[j][lane], a column per lane that no other lane touches
+            for (uint32_t j = 0; j < oq.num_bits; j++) oacc[j * EGR_WAVE + (uint32_t)lane] = 0.0f;
+        }
 
         // ---- R1: ray for this step ----------------------------------------------------------------------
         bool active = tg.inside;
@@ -546,6 +550,25 @@
                     }
                 }
                 EGR_STATS(const unsigned long long tcs4 = __builtin_amdgcn_s_memtime(); tc_p1 += tcs4 - tcs3;)
+                if constexpr (OBJ) {
+                    // (k_forward_objects) instead of the appearance: the membership words of four hits at a time - record order, one independent load each - and
+                    // every hit's weight added, in hit order, to the sum of each object its row belongs to. The sums live in LDS and are addressed by the
+                    // lowest remaining bit (a row is in one or two objects): no array in registers, nothing indexed in private memory.
+#pragma unroll
+                    for (int g4 = 0; g4 < 8; g4 += 4) {
+                        uint32_t M[4];
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            M[j] = 0u;
+                            if ((runm >> (g4 + j)) & 1u) M[j] = oq.pos_bits[pj[g4 + j]];
+                        }
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            const float weight = wj[g4 + j];
+                            for (uint32_t m = M[j]; m != 0u; m &= m - 1u) oacc[(uint32_t)__builtin_ctz(m) * EGR_WAVE + (uint32_t)lane] += weight;
+                        }
+                    }
+                } else {
 #pragma unroll
                 for (int g4 = 0; g4 < 8; g4 += 4) {
                     float4 A0[4], A1[4];
@@ -571,6 +594,7 @@
                         }
                     }
                 }
+                }
                 EGR_STATS(asm volatile("" ::"v"(c_rough)); tc_app += __builtin_amdgcn_s_memtime() - tcs4;)
             }
             EGR_STATS(if (lane == 0 && step == 0) {
@@ -590,7 +614,26 @@
         EGR_STATS(if (lane == 0) atomicAdd(diag64(v.control, DG_TRAVERSAL_CYC, step > 0), tm1 - tm0), atomicAdd(diag64(v.control, DG_COMPOSITE_CYC, step > 0), __builtin_amdgcn_s_memtime() - tm1);)
         // ---- raw step results; R4/R5 (tail renormalisation, bounce sampling) follow in step_epilogue_lane (egr_epilogue.hpp),
         // which is compiled without fma contraction (see the note there).
-        if (active) {
+        if constexpr (OBJ) {
+            // (k_forward_objects) the tile's end: no ray state, no statistics, no step epilogue. Each pixel of the tile turns its sums into the R4 values of the
+            // primary step (egr_epilogue.hpp: mask_tail / mask_value, unfused) and writes masks[j][pixel] for every requested object, then the
+            // non-zero set and the largest coverage from the same registers (strict '>': ties go to the lowest index, a NaN never wins).
+            if (tg.inside) {
+                const MaskTail mt = mask_tail(T, full_T, *v.cfg.eps_forward_normalization);
+                uint32_t hit = 0u;
+                int32_t top = -1;
+                float best = -__builtin_inff();
+                for (uint32_t j = 0; j < oq.num_bits; j++) {
+                    const float m = mask_value(oacc[j * EGR_WAVE + (uint32_t)lane], mt);
+                    oq.masks[(size_t)j * v.num_pixels + tg.pixel_id] = m;
+                    if (m != 0.0f) hit |= 1u << j;
+                    if (m > best) best = m, top = (int32_t)j;
+                }
+                if (oq.hit) oq.hit[tg.pixel_id] = hit;
+                if (oq.top) oq.top[tg.pixel_id] = hit != 0u ? top : -1;
+            }
+        }
+        if (!OBJ && active) {
             S.st3(SF(step, S_RGB), c_rgb), S.st(SF(step, S_DEPTH), c_depth), S.st3(SF(step, S_NORMAL), c_n);
             S.st3(SF(step, S_F0), c_f0), S.st(SF(step, S_ROUGH), c_rough), S.st(SF(step, S_T), T), S.st(SF(step, S_TTOT), full_T);
             if (step == 0) {

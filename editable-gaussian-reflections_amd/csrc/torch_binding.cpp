@@ -579,6 +579,35 @@ struct Raytracer : torch::CustomClassHolder {
         }
         check(egr_render_views(ctx, &b, current_stream()), "render_views");
     }
+    // per-object coverage of one view (egr_object_masks): R [3,3], center [3] (any device, moved and converted like render_views'), row_bits int32 [N] on the
+    // tracer's device (editing.EditableGaussians.selection_mask), bits = the requested selection bits in output order. Returns (masks [K,H,W] fp32,
+    // hit int32 [H,W] - bit j = masks[j] != 0, output index 31 is the sign bit -, top int32 [H,W]). A query: nothing else of the tracer changes.
+    std::tuple<Tensor, Tensor, Tensor> object_masks(Tensor R, Tensor center, double fovy, double znear, double zfar, Tensor row_bits, std::vector<int64_t> bits) {
+        TORCH_CHECK(R.dim() == 2 && R.size(0) == 3 && R.size(1) == 3 && center.numel() == 3, "object_masks: R [3,3] and center [3] expected");
+        const auto dev = framebuffer_data->output_rgb.device();
+        TORCH_CHECK(row_bits.device() == dev && row_bits.scalar_type() == torch::kInt32 && row_bits.dim() == 1 && row_bits.is_contiguous() &&
+                        row_bits.size(0) == gaussian_data->mean.size(0),
+                    "object_masks: row_bits must be a contiguous int32 tensor [", gaussian_data->mean.size(0), "] on the tracer's device, got ", row_bits.sizes(), " ", row_bits.scalar_type(), " on ", row_bits.device());
+        TORCH_CHECK(!bits.empty() && bits.size() <= EGR_MAX_EDIT_OBJECTS, "object_masks: 1 .. ", EGR_MAX_EDIT_OBJECTS, " bits expected, got ", bits.size());
+        uint8_t b8[EGR_MAX_EDIT_OBJECTS];
+        for (size_t j = 0; j < bits.size(); j++) {
+            TORCH_CHECK(bits[j] >= 0 && bits[j] < 256, "object_masks: bit ", bits[j], " out of range");
+            b8[j] = (uint8_t)bits[j];
+        }
+        const auto [r, cc, fv, V] = batch_cameras("object_masks", R.unsqueeze(0), center.reshape({1, 3}), torch::full({1}, fovy, torch::dtype(torch::kFloat32)));
+        (void)V;
+        const auto fopts = framebuffer_data->output_rgb.options();
+        Tensor masks = torch::zeros({(int64_t)bits.size(), height, width}, fopts);
+        Tensor hit = torch::zeros({height, width}, fopts.dtype(torch::kInt32)), top = torch::full({height, width}, -1, fopts.dtype(torch::kInt32));
+        egr_object_mask_query q{};
+        q.rotation_c2w_dataset = r.data_ptr<float>(), q.camera_center = cc.data_ptr<float>(), q.vertical_fov_radians = fv.data_ptr<float>();
+        q.znear = (float)znear, q.zfar = (float)zfar;
+        q.row_bits = reinterpret_cast<const uint32_t *>(row_bits.data_ptr<int32_t>());
+        q.bits = b8, q.num_bits = (uint32_t)bits.size();
+        q.masks = masks.data_ptr<float>(), q.hit = reinterpret_cast<uint32_t *>(hit.data_ptr<int32_t>()), q.top = top.data_ptr<int32_t>();
+        check(egr_object_masks(ctx, &q, current_stream()), "object_masks");
+        return {masks, hit, top};
+    }
     // multi-view training launch (egr_train_views): R [V,3,3], centers [V,3], fovy [V] as for render_views; the six targets are channel-major [V,C,H,W]
     // fp32 tensors on the tracer's device (C = 3, depth / roughness 1; None or an empty tensor = absent = zeros). Adds the gradients of the V views to
     // the gradient tensors (or the per-launch buffer: one grad launch for the whole batch) as V sequential raytrace() calls with grad mode on would.
@@ -754,6 +783,7 @@ struct Raytracer : torch::CustomClassHolder {
             .def("set_camera", &Raytracer::set_camera)
             .def("render_views", &Raytracer::render_views)
             .def("render_views_into", &Raytracer::render_views_into)
+            .def("object_masks", &Raytracer::object_masks)
             .def("train_views", &Raytracer::train_views)
             .def("train_views_import", &Raytracer::train_views_import)
             .def("denoise_views", &Raytracer::denoise_views)

@@ -336,6 +336,18 @@ struct FwdConst { // launch constants of a forward wave
     const float4 *__restrict__ app;
     const uint4 *__restrict__ wnodes;
 };
+// egr_object_masks (k_forward_objects): what the primary step composites instead of the appearance, and where the tile's end writes it. A kernel argument of
+// that kernel alone (not part of DeviceView); the other three chain kernels hold an empty one that no code of theirs reads.
+struct ObjectQuery {
+    const uint32_t *pos_bits; // [n] membership word per RECORD (sorted position), bit j = the row belongs to the j-th REQUESTED object (k_object_bits)
+    uint32_t num_bits;        // K requested objects, 1 .. 32
+    float *masks;             // [K][H][W]
+    uint32_t *hit;            // [H][W] or NULL
+    int32_t *top;             // [H][W] or NULL
+};
+struct ObjectBitList { // the requested selection bits in output order (a kernel argument: no upload)
+    uint8_t bit[32];
+};
 struct WalkShared { // one wave's LDS
     uint32_t pstk[EGR_PSTK];  // (ray << 26 | wide node); entries beyond EGR_PSTK spill to the wave's global column
     uint32_t lbuf[EGR_LBUF];  // (ray << 26 | record) awaiting evaluation; a walk batch adds <= 8 GPOP x 8 and only runs when that fits
@@ -732,19 +744,56 @@ __global__ void __launch_bounds__(256) k_live(DeviceView v, int grads) {
 #define EGR_FWD_WAVES 4 // waves per SIMD the forward chain is built for (register budget 512 / EGR_FWD_WAVES)
 #endif
 template <bool GRADS, bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribute__((amdgpu_waves_per_eu(EGR_FWD_WAVES, EGR_FWD_WAVES))) k_forward_chain(DeviceView v) {
-    constexpr bool BATCH = false;
+    constexpr bool BATCH = false, OBJ = false;
+    [[maybe_unused]] const ObjectQuery oq{};
+    [[maybe_unused]] float *const oacc = nullptr;
 #include "forward_chain.inc"
 }
 // The same chain for a batch of no-grad frames (egr_render_views): the frame is part of the task index, the primary rays read the frame's
 // view record, and only the batch's last frame writes stats / random_seeds. Its own kernel, so that the launches of egr_raytrace keep theirs.
 template <bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribute__((amdgpu_waves_per_eu(EGR_FWD_WAVES, EGR_FWD_WAVES))) k_forward_batch(DeviceView v) {
-    constexpr bool GRADS = false, BATCH = true;
+    constexpr bool GRADS = false, BATCH = true, OBJ = false;
+    [[maybe_unused]] const ObjectQuery oq{};
+    [[maybe_unused]] float *const oacc = nullptr;
 #include "forward_chain.inc"
 }
 // ... and for the views of a multi-view training launch (egr_train_views): one sample per view, hits recorded for the backward into the batch's own arena.
 template <bool CUBE, int TEAM> __global__ void __launch_bounds__(EGR_WAVE * TEAM) __attribute__((amdgpu_waves_per_eu(EGR_FWD_WAVES, EGR_FWD_WAVES))) k_forward_batch_grads(DeviceView v) {
-    constexpr bool GRADS = true, BATCH = true;
+    constexpr bool GRADS = true, BATCH = true, OBJ = false;
+    [[maybe_unused]] const ObjectQuery oq{};
+    [[maybe_unused]] float *const oacc = nullptr;
 #include "forward_chain.inc"
+}
+// ... and for egr_object_masks: the primary step of ONE view of the batch path with per-object coverage in place of the appearance (forward_task.inc: OBJ).
+// Single-wave workgroups only, the product tree only. The coverage sums are [K][64] fp32 of DYNAMIC LDS behind the wave's WalkShared - K x 256 B, sized by
+// the launch, so a query for four objects keeps the chain's sixteen waves per CU and one for thirty-two runs at what 160 KB hold.
+#ifndef EGR_OBJ_WAVES
+#define EGR_OBJ_WAVES EGR_FWD_WAVES // waves per SIMD k_forward_objects is built for (3: 168 VGPRs and no spill, but twelve waves per CU at any K - measured slower)
+#endif
+#ifndef EGR_OBJ_MIN_SUMS
+#define EGR_OBJ_MIN_SUMS 1 // objects the LDS sums are sized for at least (32 = a fixed [32][64] array whatever K: the measurement of what sizing by K saves)
+#endif
+extern __shared__ float egr_object_sums[];
+__global__ void __launch_bounds__(EGR_WAVE) __attribute__((amdgpu_waves_per_eu(EGR_OBJ_WAVES, EGR_OBJ_WAVES))) k_forward_objects(DeviceView v, ObjectQuery oq) {
+    constexpr bool GRADS = false, BATCH = true, OBJ = true, CUBE = false;
+    constexpr int TEAM = 1;
+    float *const oacc = egr_object_sums;
+#include "forward_chain.inc"
+}
+// The membership words of a query in record order: word of position p = bit j set iff row_bits[gid_of_pos[p]] has the j-th requested selection bit. One
+// coalesced pass, so the chain's fetch is one load by the record index it already holds.
+__global__ void __launch_bounds__(256) k_object_bits(DeviceView v, const uint32_t *__restrict__ row_bits, ObjectBitList bits, uint32_t num_bits, uint32_t *__restrict__ pos_bits) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= v.n) return;
+    const uint32_t w = row_bits[v.gid_of_pos[p]];
+    uint32_t out = 0u;
+    for (uint32_t j = 0; j < num_bits; j++) out |= ((w >> bits.bit[j]) & 1u) << j;
+    pos_bits[p] = out;
+}
+// k_batch_prologue + k_batch_chunk_begin for a query: the per-launch control words and fresh queues. metadata is not touched.
+__global__ void k_objects_prologue(DeviceView v) {
+    reset_launch_words(v, threadIdx.x);
+    reset_chunk_words(v, threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1481,7 +1530,7 @@ __global__ void k_copy3(const float *__restrict__ src, float *__restrict__ dst, 
     K(k_forward_chain<true, false, 1>), K(k_forward_chain<true, false, EGR_TEAM>), K(k_backward_chain<1>), K(k_forward_chain<true, true, EGR_TEAM>), K(k_forward_chain<false, true, EGR_TEAM>), K(k_forward_chain<false, false, EGR_TEAM>),
     K(k_forward_chain<true, true, 1>), K(k_forward_chain<false, true, 1>), K(k_forward_chain<false, false, 1>), K(k_backward_chain<EGR_BWD_TEAM>), K(k_grad_gather<true, false>), K(k_grad_gather<false, false>),
     K(k_forward_batch<true, EGR_TEAM>), K(k_forward_batch<false, EGR_TEAM>), K(k_forward_batch<true, 1>), K(k_forward_batch<false, 1>), K(k_forward_batch_grads<true, EGR_TEAM>), K(k_forward_batch_grads<false, EGR_TEAM>),
-    K(k_forward_batch_grads<true, 1>), K(k_forward_batch_grads<false, 1>), K(k_backward_batch<EGR_BWD_TEAM>), K(k_backward_batch<1>), K(k_grad_gather<false, true>)
+    K(k_forward_batch_grads<true, 1>), K(k_forward_batch_grads<false, 1>), K(k_backward_batch<EGR_BWD_TEAM>), K(k_backward_batch<1>), K(k_grad_gather<false, true>), K(k_forward_objects)
 #undef K
 };
 
@@ -1563,6 +1612,7 @@ void egr_build_task_order(egr_context *c) {
 void egr_trace_free(egr_context *c) {
     egr_dev_free(c, c->batch_state), egr_dev_free(c, c->batch_carry), egr_dev_free(c, c->batch_cams);
     c->batch_alloc_frames = 0, c->batch_cams_cap = 0;
+    egr_dev_free(c, c->object_bits), c->object_bits_cap = 0;
     egr_dev_free(c, c->train_arena), egr_dev_free(c, c->train_last_block), egr_dev_free(c, c->train_cost), egr_dev_free(c, c->train_order);
     c->train_alloc_frames = 0, c->train_blocks_cap = 0;
     for (auto &o : c->task_orders) egr_dev_free(c, o.table);
@@ -1893,6 +1943,38 @@ void egr_train_views_launch(egr_context *c, const egr_train_batch *b, bool live_
     }
     launch_grad_gather(c, v, import_into, s);
     hipLaunchKernelGGL(k_batch_epilogue, dim3(1), dim3(64), 0, s, v, V);
+}
+
+// egr_object_masks: the batch path's machinery for ONE view and ONE frame - camera table, control words, queues, live records - around k_forward_objects.
+// No ray state (the variant keeps none), no k_finish*, no statistics reset, and the epilogue counts zero frames: total_num_calls, the framebuffer, both
+// statistics, random_seeds and grads_enabled stay as they were. The frame draws its seeds from total_num_calls + 1, as the next launch would.
+void egr_object_masks_launch(egr_context *c, const egr_object_mask_query *q, bool live_fresh, hipStream_t s) {
+    egr_batch_reserve(c, 0u, 1u);
+    if (c->object_bits_cap < c->g.count) { // the membership words in record order: grows with the cloud, freed by egr_destroy
+        EGR_HIP(hipDeviceSynchronize());
+        egr_dev_free(c, c->object_bits);
+        c->object_bits_cap = 0;
+        egr_dev_alloc(c, c->object_bits, (size_t)c->g.count);
+        c->object_bits_cap = c->g.count;
+    }
+    DeviceView v = batch_view(c, 1u, 1u);
+    v.team_help = 0; // single-wave workgroups always: nothing of the result may depend on timing
+    v.batch_frame0 = 0u, v.batch_frames = 1u;
+    ObjectBitList bits{};
+    for (uint32_t j = 0; j < q->num_bits; j++) bits.bit[j] = q->bits[j];
+    const ObjectQuery oq{c->object_bits, q->num_bits, q->masks, q->hit, q->top};
+    egr_stamp_begin(c, "prologue+live", s);
+    hipLaunchKernelGGL(k_batch_cameras, dim3(1), dim3(64), 0, s, q->rotation_c2w_dataset, q->camera_center, q->vertical_fov_radians, 1u, q->znear, q->zfar, c->batch_cams);
+    hipLaunchKernelGGL(k_objects_prologue, dim3(1), dim3(64), 0, s, v);
+    if (v.n && !live_fresh) hipLaunchKernelGGL(k_live, dim3((v.n + 255) / 256), dim3(256), 0, s, v, 0);
+    if (v.n) hipLaunchKernelGGL(k_object_bits, dim3((v.n + 255u) / 256u), dim3(256), 0, s, v, q->row_bits, bits, q->num_bits, c->object_bits);
+    egr_stamp_end(c, s);
+    if (v.num_tasks) {
+        egr_stamp_begin(c, "forward_objects", s);
+        hipLaunchKernelGGL(k_forward_objects, dim3(chain_slots(c, v.num_tasks)), dim3(EGR_WAVE), (size_t)std::max<uint32_t>(q->num_bits, EGR_OBJ_MIN_SUMS) * EGR_WAVE * sizeof(float), s, v, oq);
+        egr_stamp_end(c, s);
+    }
+    hipLaunchKernelGGL(k_batch_epilogue, dim3(1), dim3(64), 0, s, v, 0u);
 }
 
 void egr_export_step_hits(egr_context *c, int32_t *host_out, hipStream_t s) { export_per_step<int32_t, k_export_step_hits>(c, host_out, s); }

@@ -15,10 +15,16 @@ Deviations from the reference, all deliberate (DESIGN.md "Scene editing" has the
   * the "metalness" property range of make_editable names an attribute the reference's model does not have: it is refused here
   * duplicate_object gives the copy its own deep-copied box; the reference's viewer aliases the source's box and shifts both
   * at most 32 objects (one bit each)
+  * selection_masks (the viewer's selection mode, gaussian_viewer.py:292-321) is ONE primary pass for all objects instead of one full render per object:
+    one launch and one seed (the reference gives each object its own launch and jitter and advances total_num_calls by K; here the counter stays);
+    no mean(dim=0) over the three equal channels ((x + x + x) / 3 is not always x in fp32); colour edits do not reach the mask (upstream the indicator goes
+    through the object's diffuse edit, so a diffuse_override tints every object's mask and breaks the pick) while geometry edits (transform, scale,
+    removed) act through the tracer's exported state; no bounce is traced (rgb[0] does not depend on them)
 The HSV conventions are kornia's as the reference calls it (hexcone, hue in radians); kornia itself is not a dependency, so parity with it is unpinned."""
 import copy
 import ctypes as C
 import math
+import os
 from dataclasses import dataclass
 from types import SimpleNamespace
 
@@ -339,3 +345,48 @@ def render_edited(camera, raytracer, **kw):
     pc = raytracer.pc
     pc.dirty_check()
     return render(camera, raytracer, force_update_bvh=pc.is_dirty, **kw)
+
+
+@torch.no_grad()
+def selection_masks(camera, raytracer, names=None, znear=0.01, zfar=999.9):
+    """The viewer's selection mode (gaussian_viewer.py:292-321) in one call: per-object coverage of `camera`'s view. dirty_check(); if dirty, the edits are
+    exported and the tree refitted exactly as `render_edited` would, without a render; then ONE launch (Raytracer.object_masks) composites the primary step once
+    and splits every hit's weight over the objects its row belongs to. `names`: the objects asked for, in output order (default: every object but the key
+    "everything", in `pc.names` order; copies made by duplicate_object are covered through their own bit).
+
+    Returns SimpleNamespace(names, masks [K,H,W] fp32, hit int32 [H,W], top int32 [H,W]) on the device. masks[j] is, bit for bit, every channel of
+    `render(...).rgb[0]` on this tracer with object names[j]'s 0/1 indicator as the diffuse colour and the same seed; hit has bit j set where masks[j] != 0
+    (output index 31 is the sign bit); top is the index of the largest mask (ties: the lowest index), -1 where no object covers the pixel. A query: the
+    framebuffer, the statistics, random_seeds, total_num_calls, the gradients and the config stay as they were; the next render draws the seed this call
+    used. A partitioned tracer traces the whole image on the calling rank, as `render_views` does. See the module docstring for the deviations."""
+    pc = raytracer.pc
+    names = [n for n in pc.names if n != "everything"] if names is None else list(names)
+    bits = [pc.bits[n] for n in names]
+    pc.dirty_check()
+    if pc.is_dirty:
+        raytracer._export_and_update_bvh()
+    m = raytracer.cuda_module
+    R = torch.from_numpy(camera.R).float() if isinstance(camera.R, np.ndarray) else camera.R
+    row_bits = pc.selection_mask.to(m.get_framebuffer().output_rgb.device, torch.int32).contiguous()
+    raytracer._set_full_image(True)
+    try:
+        masks, hit, top = m.object_masks(R, torch.as_tensor(camera.camera_center), float(camera.FoVy), float(os.getenv("ZNEAR", znear)), float(os.getenv("ZFAR", zfar)),
+                                         row_bits, bits)
+    finally:
+        raytracer._set_full_image(False)
+    return SimpleNamespace(names=names, masks=masks, hit=hit, top=top)
+
+
+def pick(result, x, y, rule="last"):
+    """The object under pixel (x, y) of a `selection_masks` result, or None where no object covers it: one pixel read back. x and y are clamped to the image,
+    as the viewer clamps the cursor. rule="last" is the reference's (gaussian_viewer.py:728-745: the last name in order whose mask is non-zero wins - the
+    highest set bit of `hit`); rule="top" returns the object with the largest coverage."""
+    if rule not in ("last", "top"):
+        raise ValueError(f"rule must be 'last' or 'top', got {rule!r}")
+    H, W = result.hit.shape[-2:]
+    x, y = min(max(int(x), 0), W - 1), min(max(int(y), 0), H - 1)
+    if rule == "top":
+        j = int(result.top[y, x])
+        return result.names[j] if j >= 0 else None
+    h = int(result.hit[y, x]) & 0xFFFFFFFF  # (int32: output index 31 is the sign bit)
+    return result.names[h.bit_length() - 1] if h else None

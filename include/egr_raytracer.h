@@ -575,6 +575,43 @@ int egr_edit_apply(int device, uint32_t n, const egr_edit_arrays *src, const egr
                    const egr_edit_record *records, uint32_t num_records, void *hip_stream);
 const char *egr_edit_last_error(void);
 
+/* ---- Per-object coverage of one view (an additive symbol of library version 0.8, egr_version() is unchanged): what the reference's viewer computes when
+ * selection mode is entered (gaussian_viewer.py:292-321) - one image per object, each from a full render with the object's 0/1 indicator as the diffuse
+ * colour - as ONE primary pass (trace.hip: k_forward_objects).
+ *
+ * Take the camera of the query and the primary ray the NEXT launch would trace at a pixel: seeds from metadata.total_num_calls + 1, jitter as the config
+ * says, everything else from the context's current native tensors and tree. The ray's composited hits in order are i = 0 .. n-1 with weights
+ * w_i = T - next_T (forward_pass.cu:108-109). For the j-th requested selection bit b = bits[j]:
+ *     c    = sum in hit order, fp32, of w_i over the hits whose row has bit b set in row_bits   (plain adds, starting at +0)
+ *     mask = c + rem * (c * inv_norm)      rem = T - full_T, inv_norm = 1 / max(1 - T, eps_forward_normalization): R4 of the primary step, unfused
+ * which is, bit for bit, every channel of output_rgb[0] after egr_raytrace(grads_enabled = 0) on this context with accumulate_samples off and a model whose
+ * rgb is (1, 1, 1) on the rows of the object and (0, 0, 0) elsewhere (relu keeps 0 and 1; fma(1, w, c) = c + w, fma(0, w, c) = c).
+ *   masks  [K][H][W] fp32, K = num_bits, in the order of `bits`
+ *   hit    [H][W] or NULL: bit j set iff masks[j] != 0 at the pixel (j is the OUTPUT index, not the selection bit; a NaN counts as non-zero)
+ *   top    [H][W] or NULL: the output index with the largest mask under a strict `>` - ties go to the lowest index, a NaN never wins; -1 where hit == 0
+ * The call is a QUERY: framebuffer outputs and accumulators, stats.*, metadata (random_seeds, total_num_calls, grads_enabled), gradients, total_weight, the
+ * config and the hit arena of the last grad launch stay exactly as they were. No bounce is traced whatever num_bounces says. The per-launch egr_counters and
+ * egr_last_kernel_ms describe this launch afterwards (lifetime_launches does not grow); a candidate-list overflow is reported in egr_counters.status as by
+ * egr_render_views. The BVH gates, the partition (a rank traces its own tiles; other pixels are left untouched) and the debug pixel mask behave as for
+ * egr_render_views. Single-wave workgroups always: team help is ignored. A context in exact-statistics mode (egr_set_exact_stats) is refused: only the
+ * product tree has this kernel.
+ * Validation BEFORE any HIP call: a NULL query, row_bits, bits, masks or camera array, num_bits == 0 or > EGR_MAX_EDIT_OBJECTS, a bit >= 32 or given twice,
+ * an exact-statistics context: non-zero is returned, egr_last_error says why, nothing was touched. Asynchronous on the stream. */
+typedef struct egr_object_mask_query {
+    const float *rotation_c2w_dataset; /* [3][3] device pointer: the dataset's camera-to-world rotation, as egr_view_batch */
+    const float *camera_center;        /* [3] device pointer */
+    const float *vertical_fov_radians; /* [1] device pointer */
+    float znear;
+    float zfar;
+    const uint32_t *row_bits;          /* device, [count the tree was built for]: membership word per gaussian id (egr_edit_select's mask) */
+    const uint8_t *bits;               /* HOST, [num_bits]: distinct selection bits < 32, the output order */
+    uint32_t num_bits;                 /* K, 1 .. EGR_MAX_EDIT_OBJECTS */
+    float *masks;                      /* [K][H][W] required */
+    uint32_t *hit;                     /* [H][W] or NULL */
+    int32_t *top;                      /* [H][W] or NULL */
+} egr_object_mask_query;
+int egr_object_masks(egr_context *ctx, const egr_object_mask_query *q, void *hip_stream);
+
 /* ---- Fused evaluation metrics (not in the reference as one call; additive symbols of library version 0.8, egr_version() is unchanged): what train.py:103-134
  * (training_report) and render.py:216-228 followed by metrics.py do per test view with six tone-mapping chains and three reductions, for V views in TWO
  * launches (csrc/eval.hip). Context-free like egr_prune_* and egr_edit_*.
