@@ -52,6 +52,10 @@ egr_object_mask_query = _struct("egr_object_mask_query", [("rotation_c2w_dataset
 EGR_MAX_PRUNE_ARRAYS = 32
 EGR_PRUNE_ROWS_PER_WG = 1024
 egr_prune_array = _struct("egr_prune_array", [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_uint32)])
+# growing the cloud (csrc/grow.hip): one table entry of egr_grow_append - rows >= n come from `tail` (ROWS) or are the word `fill_bits` (FILL)
+EGR_GROW_TAIL_ROWS, EGR_GROW_TAIL_FILL = 0, 1
+egr_grow_array = _struct("egr_grow_array", [("src", C.c_void_p), ("dst", C.c_void_p), ("tail", C.c_void_p), ("width", C.c_uint32), ("tail_kind", C.c_uint32),
+                                            ("fill_bits", C.c_uint32)])
 
 # scene editing (csrc/edit.hip): selection objects (host), edit records (device) and the two tables of eight arrays
 EGR_MAX_EDIT_OBJECTS = 32
@@ -219,6 +223,11 @@ def lib(path=None):
         L.egr_prune_gather.argtypes = [C.c_int, C.POINTER(egr_prune_array), C.c_int, C.c_uint32, P, C.c_uint32, P]  # device, table, entries, n, src_index, count, stream
         L.egr_prune_last_error.argtypes = []
         L.egr_prune_last_error.restype = C.c_char_p
+        # growing the cloud (csrc/grow.hip). sample: device, first, n, seed, radius, clamp, out_points, stream; append: device, table, entries, n, m, stream
+        L.egr_grow_sample.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.c_float, C.c_float, P, P]
+        L.egr_grow_append.argtypes = [C.c_int, C.POINTER(egr_grow_array), C.c_int, C.c_uint32, C.c_uint32, P]
+        L.egr_grow_last_error.argtypes = []
+        L.egr_grow_last_error.restype = C.c_char_p
         # scene editing (csrc/edit.hip): device, n, xyz, f0, roughness, diffuse, objects (host), num_objects, mask, stream
         L.egr_edit_select.argtypes = [C.c_int, C.c_uint32, P, P, P, P, C.POINTER(egr_edit_object), C.c_uint32, P, P]
         L.egr_edit_apply.argtypes = [C.c_int, C.c_uint32, C.POINTER(egr_edit_arrays), C.POINTER(egr_edit_arrays), P, P, C.c_uint32, P]  # device, n, src, dst, mask, records (device), num_records, stream

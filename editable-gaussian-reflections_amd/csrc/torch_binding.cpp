@@ -939,6 +939,65 @@ static std::vector<Tensor> prune_gather(std::vector<Tensor> src, const Tensor &s
     return out;
 }
 
+// Growing the cloud, part 1 (egr_grow_sample, csrc/grow.hip): candidates first .. first + n of the far-field cloud as a new fp32 [n,3] tensor on `device`, on
+// the current stream. `first` and `seed` are unsigned 64-bit values carried in the schema's int (their bits: 2^63 + 5 is passed as -2^63 + 5).
+static Tensor grow_sample(int64_t first, int64_t n, int64_t seed, double radius, double clamp, c10::Device device) {
+    TORCH_CHECK(device.is_cuda(), "grow_sample: device must be a GPU (there is no CPU path), got ", device);
+    TORCH_CHECK(n >= 0 && n <= ((int64_t)1 << 26), "grow_sample: n must be in 0..2^26 (the limit of the tree), got ", n);
+    const c10::Device dev(torch::kCUDA, device.has_index() ? device.index() : c10::hip::current_device());
+    const c10::DeviceGuard guard(dev); // the output and current_stream() belong to `device`, which need not be the current one
+    Tensor out = torch::empty({n, 3}, torch::dtype(torch::kFloat32).device(dev));
+    if (n == 0) return out; // (an empty tensor has no storage to hand to the library)
+    const int rc = egr_grow_sample(dev.index(), (uint64_t)first, (uint32_t)n, (uint64_t)seed, (float)radius, (float)clamp, out.data_ptr<float>(), current_stream());
+    TORCH_CHECK(rc == 0, egr_grow_last_error());
+    return out;
+}
+// Growing the cloud, part 2 (egr_grow_append): out[k] = cat(src[k], new rows) for every tensor of `src` - contiguous GPU tensors of 4-byte elements with the
+// same leading size n - as one launch per EGR_MAX_PRUNE_ARRAYS tensors. The m new rows of entry k are tail[k] (same dtype and trailing shape, m rows) or,
+// where tail[k] is None, the word fill_bits[k] in every element (an fp32's or int32's bits, -2^31 .. 2^32 - 1). The outputs are new tensors.
+static std::vector<Tensor> grow_append(std::vector<Tensor> src, const c10::List<c10::optional<Tensor>> &tail, std::vector<int64_t> fill_bits, int64_t m) {
+    TORCH_CHECK(tail.size() == src.size() && fill_bits.size() == src.size(), "grow_append: src, tail and fill_bits must have one entry per tensor (", src.size(), ", ",
+                tail.size(), ", ", fill_bits.size(), ")");
+    std::vector<Tensor> out;
+    if (src.empty()) return out;
+    const int64_t n = src[0].dim() >= 1 ? src[0].size(0) : -1;
+    TORCH_CHECK(n >= 0, "grow_append: tensors with a leading (row) dimension are required");
+    TORCH_CHECK(m >= 0 && n + m <= ((int64_t)1 << 26), "grow_append: m must be >= 0 and n + m <= 2^26 rows (the limit of the tree), got n = ", n, ", m = ", m);
+    const c10::Device dev = src[0].device();
+    const c10::DeviceGuard guard(dev);
+    std::vector<egr_grow_array> table;
+    for (size_t k = 0; k < src.size(); k++) {
+        const Tensor &t = src[k];
+        TORCH_CHECK(t.is_cuda() && t.device() == dev && t.is_contiguous() && t.element_size() == 4 && t.dim() >= 1 && t.size(0) == n,
+                    "grow_append: contiguous GPU tensors of 4-byte elements with the same leading size are required (src[", k, "])");
+        TORCH_CHECK(fill_bits[k] >= -((int64_t)1 << 31) && fill_bits[k] < ((int64_t)1 << 32), "grow_append: fill_bits[", k, "] is not a 32-bit word");
+        auto shape = t.sizes().vec();
+        int64_t width = 1;
+        for (size_t d = 1; d < shape.size(); d++) width *= shape[d];
+        shape[0] = n + m;
+        egr_grow_array e{n ? t.data_ptr() : nullptr, nullptr, nullptr, (uint32_t)width, EGR_GROW_TAIL_FILL, (uint32_t)(uint64_t)fill_bits[k]};
+        const c10::optional<Tensor> add = tail.get(k);
+        if (add.has_value() && add->defined()) {
+            auto want = shape;
+            want[0] = m;
+            TORCH_CHECK(add->is_cuda() && add->device() == dev && add->is_contiguous() && add->scalar_type() == t.scalar_type() && add->sizes().vec() == want,
+                        "grow_append: tail[", k, "] must be a contiguous ", t.scalar_type(), " tensor ", c10::IntArrayRef(want), " on ", dev, ", got ", add->scalar_type(), " ",
+                        add->sizes(), " on ", add->device());
+            e.tail = m ? add->data_ptr() : nullptr, e.tail_kind = EGR_GROW_TAIL_ROWS;
+        }
+        out.push_back(torch::empty(shape, t.options()));
+        if (width == 0) continue; // (a [N,0] tensor has no elements to move)
+        e.dst = out.back().data_ptr();
+        table.push_back(e);
+    }
+    if (n + m == 0) return out; // (empty tensors have no storage to hand to the library)
+    for (size_t k0 = 0; k0 < table.size(); k0 += EGR_MAX_PRUNE_ARRAYS) {
+        const int rc = egr_grow_append(dev.index(), table.data() + k0, (int)std::min<size_t>(EGR_MAX_PRUNE_ARRAYS, table.size() - k0), (uint32_t)n, (uint32_t)m, current_stream());
+        TORCH_CHECK(rc == 0, egr_grow_last_error());
+    }
+    return out;
+}
+
 // Scene editing, part 1 (egr_edit_select, csrc/edit.hip): the membership mask of up to 32 objects. `objects`: a CPU int32 tensor [K, 17] holding K
 // egr_edit_object records as bits (editing.py packs them); xyz fp32 [N,3] on the GPU; f0 [N,3], roughness [N,1], diffuse [N,3] only where an object has
 // that property range. Returns int32 [N] (bit k = row belongs to object k) on the current stream, no host synchronisation.
@@ -1161,6 +1220,8 @@ TORCH_LIBRARY(egr, m) {
           "(Tensor src_index, Tensor count)",
           &prune_select);
     m.def("prune_gather(Tensor[] src, Tensor src_index, int count) -> Tensor[]", &prune_gather);
+    m.def("grow_sample(int first, int n, int seed, float radius, float clamp, Device device) -> Tensor", &grow_sample);
+    m.def("grow_append(Tensor[] src, Tensor?[] tail, int[] fill_bits, int m) -> Tensor[]", &grow_append);
     m.def("edit_select(Tensor xyz, Tensor? f0, Tensor? roughness, Tensor? diffuse, Tensor objects) -> Tensor", &edit_select);
     m.def("edit_apply(Tensor[] src, Tensor[] dst, Tensor mask, Tensor records) -> ()", &edit_apply);
     m.def("eval_metrics(Tensor final, Tensor? rgb, Tensor? target_final, Tensor? target_diffuse, Tensor? target_specular, bool want_display=False) -> "

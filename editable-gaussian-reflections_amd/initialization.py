@@ -187,7 +187,8 @@ def gaussians_from_cloud(points, colors, normals=None, init_scale=1.0, init_opa=
         rgb.clamp_(min=0.0, max=clamp_max)
     spacing = distCUDA2(mean).clamp(min=1e-7).sqrt()  # the distance to the three nearest neighbours, floored as upstream floors the squared one
     p = constant(init_opa, 1)
-    identity = torch.tensor([1.0, 0.0, 0.0, 0.0], device=dev)
+    rotation = constant(0.0, 4)
+    rotation[:, 0] = 1.0  # (filled on the device: a host list would be one more synchronising copy)
     return dict(rgb=rgb, normal=constant(0.0, 3) if normals is None else on_device(normals), f0=constant(init_f0, 3), roughness=constant(init_roughness, 1),
                 opacity=(p / (1.0 - p)).log(), scale=(spacing * init_scale).log().unsqueeze(1).expand(n, 3).contiguous(), mean=mean,
-                rotation=identity.expand(n, 4).contiguous())
+                rotation=rotation)

@@ -10,6 +10,7 @@ utils/general_utils.py:31-60 (pinned by tests/golden/expon_lr.npz, generated fro
 import importlib
 import math
 
+import numpy as np
 import torch
 
 importlib.import_module(__package__).load_library()
@@ -54,6 +55,25 @@ def filter_points_near_cameras(points, cam_centers, cam_znear):
     centers, znear = _camera_spheres(cam_centers, cam_znear, points.device)
     src_index, count = torch.ops.egr.prune_select(None, 1.0, 0.0, points, centers, znear, None)
     return torch.ops.egr.prune_gather([points], src_index, int(count.item()))[0]
+
+
+def farfield_candidates(n, seed, radius, clamp=3.0, first=0, device="cuda"):
+    """Candidates first .. first + n of the far-field cloud (csrc/grow.hip: egr_grow_sample) as a new fp32 [n,3] tensor: `randn().clamp(-clamp, clamp) * radius`
+    of gaussian_model.py:236 with a generator of our own - Philox4x32-10 keyed by `seed`, counter = the candidate's index, Box-Muller in fp64 (the header has
+    the definition, tests/grow_restatement.py restates it). Row r depends on (seed, first + r, radius, clamp) alone: not on n, the device, torch's version or
+    anything run before, so every rank of a partition draws the same points and a call can be split at any row. `seed` and `first` are unsigned 64-bit
+    integers (taken modulo 2^64)."""
+    as_i64 = lambda v: ((int(v) % (1 << 64)) ^ (1 << 63)) - (1 << 63)  # the op's schema carries the 64 bits in a signed int
+    return torch.ops.egr.grow_sample(as_i64(first), int(n), as_i64(seed), float(radius), float(clamp), torch.device(device))
+
+
+def _word_bits(value, dtype):
+    """The 32-bit word of `value` as an element of a 4-byte `dtype` (egr_grow_append's fill_bits)."""
+    if dtype == torch.float32:
+        return int(np.array(value, np.float32).view(np.uint32))
+    if dtype == torch.int32:
+        return int(np.array(value, np.int64).astype(np.int32).view(np.uint32))
+    raise ValueError(f"per-row extras must be float32 or int32 tensors, got {dtype}")
 
 
 class FusedTrainStep:
@@ -132,6 +152,79 @@ class FusedTrainStep:
             z = self.exp_avg[name].new_zeros((n_new,) + tuple(self.exp_avg[name].shape[1:]))
             self.exp_avg[name] = torch.cat([self.exp_avg[name], z], 0)
             self.exp_avg_sq[name] = torch.cat([self.exp_avg_sq[name], z.clone()], 0)
+
+    @torch.no_grad()
+    def grow_and_rebuild(self, new, extra=()):
+        """The growth step of train.py:259-260 (`add_farfield_points` from the new rows on, + `rebuild_bvh`) as ONE call (csrc/grow.hip): one out-of-place
+        append launch writes the 8 parameters (old rows + new rows), the 16 moments (old rows + zeros) and the caller's per-row extras (old rows + fill),
+        then the tree is rebuilt. `new`: the dict GaussianParams.append_points takes (mean, opacity, scale, rotation, rgb, normal, roughness, f0: GPU or CPU
+        tensors or arrays with m rows each). `extra`: (tensor, fill_value) pairs - further per-row tensors of the caller's model with 4-byte elements, e.g.
+        upstream's `_round_counter` with 0; they come back extended.
+        Leaves bit for bit what `pc.append_points(new); self.extend(m); rt.rebuild_bvh()` leave: every parameter a new tensor with a fresh zero `.grad`,
+        `steps` unchanged, and in the native holder the old rows' gradients and total_weight with their bits, the new rows' at zero (upstream adds the points
+        mid-interval without clearing total_weight). No host read-back. Returns (n_total, [extended extras]).
+        Raises ValueError, before anything is touched, for m == 0, for row counts that disagree, and for a model with `export_edited`
+        (editing.EditableGaussians keeps per-row selection masks that growth would leave stale: `duplicate_object` is the way to grow an edited scene)."""
+        pc = self.pc
+        if hasattr(pc, "export_edited"):
+            raise ValueError("grow_and_rebuild: an editing model keeps per-row selection masks that new rows would leave stale (use duplicate_object); nothing was changed")
+        dev, n = pc._xyz.device, pc._xyz.shape[0]
+        src, tail, fill, m = [], [], [], None
+        for _, attr, key in GROUPS:  # (the third name of a group is the key of `new`)
+            old = getattr(pc, attr)
+            if key not in new:
+                raise ValueError(f"grow_and_rebuild: new['{key}'] is missing (nothing was changed)")
+            v = new[key]
+            add = v.detach().to(dev, torch.float32) if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v), dtype=torch.float32, device=dev)
+            width = old.shape[1]
+            if add.numel() % width != 0 or (m is not None and add.numel() // width != m):
+                raise ValueError(f"grow_and_rebuild: new['{key}'] has {add.numel()} elements, expected {m if m is not None else 'a multiple of'} x {width} (nothing was changed)")
+            m = add.numel() // width
+            src.append(old), tail.append(add.reshape(m, width).contiguous()), fill.append(0)
+        if m == 0:
+            raise ValueError("grow_and_rebuild: no rows to add (nothing was changed)")
+        for moments in (self.exp_avg, self.exp_avg_sq):
+            for name, _, _ in GROUPS:
+                src.append(moments[name]), tail.append(None), fill.append(0)
+        for t, value in extra:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() >= 1 and t.shape[0] == n and t.element_size() == 4):
+                raise ValueError(f"grow_and_rebuild: per-row extras must be GPU tensors of 4-byte elements with {n} rows (nothing was changed)")
+            src.append(t.contiguous()), tail.append(None), fill.append(_word_bits(value, t.dtype))
+        out = torch.ops.egr.grow_append(src, tail, fill, m)
+        for k, (_, attr, _) in enumerate(GROUPS):
+            out[k].grad = torch.zeros_like(out[k])
+            setattr(pc, attr, out[k])
+        for k, (name, _, _) in enumerate(GROUPS):
+            self.exp_avg[name], self.exp_avg_sq[name] = out[8 + k], out[16 + k]
+        self.rt.rebuild_bvh()  # resize (keeps the old rows' gradients and weights, zeroes the new ones) + export + full build
+        return n + m, out[24:]
+
+    @torch.no_grad()
+    def add_farfield_points(self, num_points, radius, seed, cam_centers=None, cam_znear=None, clamp=3.0, init_scale=0.1, init_opa=0.1, init_diffuse=0.2, init_f0=0.04,
+                            init_roughness=0.0, normals=0.0, extra=()):
+        """gaussian_model.py:233-283 `add_farfield_points(scene)` + `raytracer.rebuild_bvh()` (train.py:259-260) as one call: `num_points` candidates
+        (`farfield_candidates(num_points, seed, radius, clamp)`; upstream: 75_000, radius = scene.cameras_extent * cfg.scene_extent_init_radius), those inside a
+        camera's znear sphere dropped (`filter_points_near_cameras`: the one read-back, the survivor count), the eight raw tensors from
+        `initialization.gaussians_from_cloud` - so scales and opacity carry the bits initialisation gives -, then `grow_and_rebuild`. The defaults are config.py:43-50
+        (init_scale_farfield, init_opa_farfield, init_diffuse_farfield, f0 0.04, roughness 0, normal 0). `extra` as in `grow_and_rebuild`.
+        Returns (n_added, [extended extras]). The result depends on the arguments alone: ranks that make the same call keep identical clouds.
+        Deviations from upstream: the points come from our generator, not torch.randn's stream (same distribution); the ADD_BOOK_INIT_PTS demo switch is not
+        built (pass such rows to `grow_and_rebuild`); `num_bounces` is switched by the caller, as train.py:257 does."""
+        from .initialization import gaussians_from_cloud
+
+        if hasattr(self.pc, "export_edited"):  # (before the sampling: nothing is launched for a model that cannot grow)
+            raise ValueError("add_farfield_points: an editing model cannot grow (see grow_and_rebuild); nothing was changed")
+        points = farfield_candidates(num_points, seed, radius, clamp, device=self.pc._xyz.device)
+        if cam_centers is not None:
+            points = filter_points_near_cameras(points, cam_centers, cam_znear)
+        k = points.shape[0]
+        if k == 0:
+            raise ValueError("add_farfield_points: no candidate lies outside the cameras' znear spheres (nothing was changed)")
+        constant = lambda value: torch.full((k, 3), float(value), dtype=torch.float32, device=points.device)
+        new = gaussians_from_cloud(points, constant(init_diffuse), normals=constant(normals), init_scale=init_scale, init_opa=init_opa, init_roughness=init_roughness,
+                                   init_f0=init_f0)
+        n_total, extras = self.grow_and_rebuild(new, extra)
+        return k, extras
 
     @torch.no_grad()
     def reset_state(self, name):

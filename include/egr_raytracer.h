@@ -480,6 +480,43 @@ int egr_prune_gather(int device, const egr_prune_array *arrays, int num_arrays, 
                      void *hip_stream);
 const char *egr_prune_last_error(void);
 
+/* ---- Growing the cloud (not in the reference as one call; additive symbols of library version 0.8, egr_version() is unchanged): what
+ * scene/gaussian_model.py:233-283 (add_farfield_points) does with torch.randn from the device generator and one torch.cat per tensor
+ * (cat_tensors_to_optimizer, gaussian_model.py:533-585), as ONE launch that writes the candidates and ONE out-of-place APPEND over all arrays
+ * (csrc/grow.hip). Context-free like egr_prune_*: the library allocates nothing, every call is asynchronous on the stream, and arguments are validated
+ * BEFORE any HIP call (non-zero return, egr_grow_last_error() says why). The camera filter between the two calls is egr_prune_select +
+ * egr_prune_gather on the candidates.
+ *
+ * egr_grow_sample: out_points [n][3] fp32; row r is candidate i = first + r and depends on (seed, i, radius, clamp) only - not on n, on the launch
+ * shape, on earlier calls or on the device: ranks that pass the same arguments hold the same points, and a call may be split at any row.
+ *   generator   Philox4x32-10 as published (Salmon et al., SC'11): multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten
+ *               rounds, counter words (i & 0xffffffff, i >> 32, 0, 0), key (seed & 0xffffffff, seed >> 32); it gives four words x0..x3.
+ *   uniforms    u_k = ((x_k >> 9) + 0.5) * 2^-23: 24 significant bits, exact in fp32 and fp64, never 0 or 1.
+ *   normals     Box-Muller in fp64, each rounded to fp32 once: z0 = sqrt(-2 ln u0) cos(2 pi u1), z1 = sqrt(-2 ln u0) sin(2 pi u1),
+ *               z2 = sqrt(-2 ln u2) cos(2 pi u3)  (|z| < 5.7 on this grid).
+ *   point       (x, y, z) = clamp(fp32(z_k), -clamp, +clamp) * radius in fp32. The reference: clamp 3, radius = cameras_extent * scene_extent_init_radius.
+ * Refused: a NULL out_points, n > 2^26, first + n overflowing 64 bits, a non-finite or negative radius or clamp. n == 0 returns 0 and launches nothing.
+ *
+ * egr_grow_append: for each of 1..EGR_MAX_PRUNE_ARRAYS table entries, in one launch, dst [n + m][width] takes in rows < n the words of src [n][width]
+ * and in rows >= n, by tail_kind, the words of tail [m][width] (EGR_GROW_TAIL_ROWS) or the word fill_bits (EGR_GROW_TAIL_FILL; tail is ignored).
+ * Elements are 4-byte words moved as bits (fp32 and int32 alike; NaN payloads and -0.0 survive). OUT OF PLACE ONLY: a dst range [n + m][width] that
+ * touches any src range, any tail range (src == dst included) or another dst is refused. Also refused: a NULL table or dst, src == NULL with n > 0,
+ * tail == NULL with EGR_GROW_TAIL_ROWS and m > 0, width 0, an unknown tail_kind, more than EGR_MAX_PRUNE_ARRAYS entries, n + m > 2^26 (the tree's
+ * limit). n == 0 is legal (the tail alone), m == 0 is legal (a copy); n + m == 0 returns 0 and launches nothing. */
+#define EGR_GROW_TAIL_ROWS 0u /* rows >= n come from `tail`    */
+#define EGR_GROW_TAIL_FILL 1u /* rows >= n are `fill_bits`     */
+typedef struct egr_grow_array {
+    const void *src;    /* [n][width] 4-byte elements; may be NULL when n == 0              */
+    void *dst;          /* [n + m][width], must not overlap any src, tail or other dst      */
+    const void *tail;   /* [m][width] (EGR_GROW_TAIL_ROWS); ignored for EGR_GROW_TAIL_FILL  */
+    uint32_t width;     /* elements per row, >= 1                                           */
+    uint32_t tail_kind; /* EGR_GROW_TAIL_ROWS or EGR_GROW_TAIL_FILL                         */
+    uint32_t fill_bits; /* the word of every new element (EGR_GROW_TAIL_FILL)               */
+} egr_grow_array;
+int egr_grow_sample(int device, uint64_t first, uint32_t n, uint64_t seed, float radius, float clamp, float *out_points, void *hip_stream);
+int egr_grow_append(int device, const egr_grow_array *arrays, int num_arrays, uint32_t n, uint32_t m, void *hip_stream);
+const char *egr_grow_last_error(void);
+
 /* ---- Scene editing (additive symbols of library version 0.8, egr_version() is unchanged): the reference's EditableGaussianModel
  * (scene/editable_gaussian_model.py: make_editable's selections and the seven getter overrides) as a SELECT that writes one bitmask per row and ONE
  * pass that applies every object's edit and writes the tracer's eight native arrays - edit and export in one launch (csrc/edit.hip).
