@@ -174,6 +174,44 @@ def voxel_extract(keys, acc, status, cap, min_count, voxel_scale, max_rows, coor
     return int(host[0]), int(host[1])
 
 
+# the training views in fp16 (csrc/viewset.hip): one source per kind for egr_viewset_ingest; the store and the outputs of a batch for egr_viewset_gather
+EGR_VIEWSET_KINDS, EGR_VIEWSET_DEPTH, EGR_VIEWSET_MAX_GATHER = 7, 3, 64
+EGR_VIEWSET_U8, EGR_VIEWSET_F32 = 0, 1
+VIEWSET_KINDS = ("render", "diffuse", "specular", "depth", "normal", "roughness", "f0")  # the order of every per-kind array
+VIEWSET_CHANNELS = (3, 3, 3, 1, 3, 1, 3)
+egr_viewset_source = _struct("egr_viewset_source", [("data", C.c_void_p), ("table", C.c_void_p), ("planes", C.c_void_p), ("channels", C.c_uint32), ("dtype", C.c_uint32)])
+egr_viewset_store = _struct("egr_viewset_store", [("planes", C.c_void_p * EGR_VIEWSET_KINDS), ("R", _F), ("centers", _F), ("fovy", _F), ("num_slots", C.c_uint32),
+                                                  ("num_filled", C.c_uint32), ("height", C.c_uint32), ("width", C.c_uint32)])
+egr_viewset_batch = _struct("egr_viewset_batch", [("targets", C.c_void_p * EGR_VIEWSET_KINDS), ("R", _F), ("centers", _F), ("fovy", _F)])
+
+
+def viewset_ingest(sources, num_views, src_height, src_width, height, width, first_slot, num_slots, depth_range, device=0, stream=0):
+    """egr_viewset_ingest on integer device addresses. `sources`: dict kind name -> (data, table or None, planes, channels, dtype); kinds left out are absent."""
+    L = lib()
+    unknown = set(sources) - set(VIEWSET_KINDS)
+    if unknown:
+        raise ValueError(f"unknown kinds {sorted(unknown)}; expected some of {VIEWSET_KINDS}")
+    table = (egr_viewset_source * EGR_VIEWSET_KINDS)()
+    for k, name in enumerate(VIEWSET_KINDS):
+        if name in sources:
+            data, tab, planes, channels, dtype = sources[name]
+            table[k] = egr_viewset_source(data=data, table=tab, planes=planes, channels=channels, dtype=dtype)
+    if L.egr_viewset_ingest(device, table, num_views, src_height, src_width, height, width, first_slot, num_slots, depth_range, C.c_void_p(stream)) != 0:
+        raise RuntimeError(L.egr_viewset_last_error().decode())
+
+
+def viewset_gather(planes, R, centers, fovy, num_slots, num_filled, height, width, indices, targets, out_R=None, out_centers=None, out_fovy=None, device=0, stream=0):
+    """egr_viewset_gather on integer device addresses. `planes`, `targets`: dicts kind name -> address (kinds left out: none / not wanted); `indices`: host integers."""
+    L = lib()
+    store = egr_viewset_store(R=R, centers=centers, fovy=fovy, num_slots=num_slots, num_filled=num_filled, height=height, width=width)
+    batch = egr_viewset_batch(R=out_R, centers=out_centers, fovy=out_fovy)
+    for k, name in enumerate(VIEWSET_KINDS):
+        store.planes[k], batch.targets[k] = planes.get(name), targets.get(name)
+    idx = (C.c_uint32 * max(len(indices), 1))(*[int(i) for i in indices])
+    if L.egr_viewset_gather(device, C.byref(store), idx, len(indices), C.byref(batch), C.c_void_p(stream)) != 0:
+        raise RuntimeError(L.egr_viewset_last_error().decode())
+
+
 _lib = None
 
 
@@ -251,6 +289,12 @@ def lib(path=None):
         L.egr_voxel_extract.argtypes = [C.c_int, P, P, P, C.c_uint64, C.c_uint32, C.c_double, C.c_uint64, P, P, P, P, C.POINTER(C.c_uint64 * 2), P, C.c_size_t, P]
         L.egr_voxel_last_error.argtypes = []
         L.egr_voxel_last_error.restype = C.c_char_p
+        # the training views in fp16 (csrc/viewset.hip). ingest: device, sources [7], V, Hs, Ws, H, W, first_slot, num_slots, depth_range, stream;
+        # gather: device, store, indices (host), V, out, stream
+        L.egr_viewset_ingest.argtypes = [C.c_int, C.POINTER(egr_viewset_source), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, P]
+        L.egr_viewset_gather.argtypes = [C.c_int, C.POINTER(egr_viewset_store), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(egr_viewset_batch), P]
+        L.egr_viewset_last_error.argtypes = []
+        L.egr_viewset_last_error.restype = C.c_char_p
         L.egr_last_error.argtypes = [P]
         L.egr_last_error.restype = C.c_char_p
         L.egr_version.restype = C.c_char_p

@@ -1201,6 +1201,101 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor, int64_t> voxel_extract(const T
     return {coords.narrow(0, 0, n), points.narrow(0, 0, n), colors.narrow(0, 0, n), counts.narrow(0, 0, n), (int64_t)host[1]};
 }
 
+// The training views in fp16, part 1 (egr_viewset_ingest, csrc/viewset.hip): the views of one chunk into slots first_slot .. first_slot + V of the store, in one
+// launch on the current stream. sources[kind]: a contiguous uint8 or fp32 [V,Hs,Ws,Cs] GPU tensor or None (absent); tables[kind]: the contiguous half [256] GPU
+// table of a uint8 source, None for fp32; planes[kind]: the store's contiguous half [slots,C,H,W]; depth_range: contiguous fp32 [slots,2]. One entry per kind each.
+static void viewset_ingest(const c10::List<c10::optional<Tensor>> &sources, const c10::List<c10::optional<Tensor>> &tables, std::vector<Tensor> planes, const Tensor &depth_range,
+                           int64_t first_slot) {
+    TORCH_CHECK(sources.size() == EGR_VIEWSET_KINDS && tables.size() == EGR_VIEWSET_KINDS && planes.size() == EGR_VIEWSET_KINDS,
+                "viewset_ingest: sources, tables and planes must have one entry per kind (", EGR_VIEWSET_KINDS, ")");
+    TORCH_CHECK(depth_range.is_cuda() && depth_range.scalar_type() == torch::kFloat32 && depth_range.is_contiguous() && depth_range.dim() == 2 && depth_range.size(1) == 2,
+                "viewset_ingest: depth_range must be a contiguous fp32 [slots,2] GPU tensor");
+    const c10::Device dev = depth_range.device();
+    const c10::DeviceGuard guard(dev);
+    const int64_t slots = depth_range.size(0);
+    TORCH_CHECK(first_slot >= 0 && first_slot <= slots, "viewset_ingest: first_slot must be in 0..slots, got ", first_slot);
+    egr_viewset_source table[EGR_VIEWSET_KINDS] = {};
+    int64_t V = -1, Hs = 0, Ws = 0, H = -1, W = -1;
+    for (size_t k = 0; k < EGR_VIEWSET_KINDS; k++) {
+        const Tensor &p = planes[k];
+        const int64_t C = (k == EGR_VIEWSET_DEPTH || k == 5) ? 1 : 3;
+        TORCH_CHECK(p.is_cuda() && p.device() == dev && p.scalar_type() == torch::kFloat16 && p.is_contiguous() && p.dim() == 4 && p.size(0) == slots && p.size(1) == C,
+                    "viewset_ingest: planes[", k, "] must be a contiguous half [", slots, ",", C, ",H,W] tensor on the store's device, got ", p.sizes());
+        if (H < 0) H = p.size(2), W = p.size(3);
+        TORCH_CHECK(p.size(2) == H && p.size(3) == W, "viewset_ingest: the planes of every kind must share one image size");
+        const c10::optional<Tensor> s = sources.get(k), t = tables.get(k);
+        const bool has_table = t.has_value() && t->defined();
+        if (has_table) {
+            TORCH_CHECK(t->is_cuda() && t->device() == dev && t->scalar_type() == torch::kFloat16 && t->is_contiguous() && t->numel() == 256,
+                        "viewset_ingest: tables[", k, "] must be a contiguous half [256] tensor on the store's device");
+            table[k].table = t->data_ptr();
+        }
+        if (!(s.has_value() && s->defined())) {
+            table[k].table = nullptr; // (the table of an absent kind is ignored)
+            continue;
+        }
+        TORCH_CHECK(s->is_cuda() && s->device() == dev && s->is_contiguous() && s->dim() == 4 && (s->scalar_type() == torch::kUInt8 || s->scalar_type() == torch::kFloat32),
+                    "viewset_ingest: sources[", k, "] must be a contiguous uint8 or fp32 [V,Hs,Ws,Cs] tensor on the store's device");
+        if (V < 0) V = s->size(0), Hs = s->size(1), Ws = s->size(2);
+        TORCH_CHECK(s->size(0) == V && s->size(1) == Hs && s->size(2) == Ws, "viewset_ingest: the sources of one call must share [V,Hs,Ws] (sources[", k, "] is ", s->sizes(), ")");
+        table[k].data = s->data_ptr(), table[k].planes = p.data_ptr(), table[k].channels = (uint32_t)s->size(3);
+        table[k].dtype = s->scalar_type() == torch::kUInt8 ? EGR_VIEWSET_U8 : EGR_VIEWSET_F32;
+    }
+    TORCH_CHECK(V >= 1, "viewset_ingest: at least one kind with at least one view is required");
+    TORCH_CHECK(Hs > 0 && Ws > 0 && H > 0 && W > 0 && std::max(std::max(V, Hs), std::max(std::max(Ws, H), W)) <= 65535, "viewset_ingest: V and the image sizes must be in 1..65535");
+    const int rc = egr_viewset_ingest(dev.index(), table, (uint32_t)V, (uint32_t)Hs, (uint32_t)Ws, (uint32_t)H, (uint32_t)W, (uint32_t)first_slot, (uint32_t)slots,
+                                      depth_range.data_ptr<float>(), current_stream());
+    TORCH_CHECK(rc == 0, egr_viewset_last_error());
+}
+// The training views in fp16, part 2 (egr_viewset_gather): rows v < len(indices) of the fp32 outputs = the stored views indices[v], exactly float(half), and their
+// camera rows, in one launch per 64 indices on the current stream - `indices` are host integers: no upload, no synchronisation. planes[kind]: the store's half
+// [slots,C,H,W]; R [slots,3,3], centers [slots,3], fovy [slots]: its camera table; out[kind]: a contiguous fp32 [>= V,C,H,W] tensor or None (not wanted);
+// out_R / out_centers / out_fovy: contiguous fp32 with >= V rows. Only the first V rows of an output are written.
+static void viewset_gather(std::vector<Tensor> planes, const Tensor &R, const Tensor &centers, const Tensor &fovy, int64_t num_filled, std::vector<int64_t> indices,
+                           const c10::List<c10::optional<Tensor>> &out, const Tensor &out_R, const Tensor &out_centers, const Tensor &out_fovy) {
+    TORCH_CHECK(planes.size() == EGR_VIEWSET_KINDS && out.size() == EGR_VIEWSET_KINDS, "viewset_gather: planes and out must have one entry per kind (", EGR_VIEWSET_KINDS, ")");
+    const int64_t V = (int64_t)indices.size();
+    TORCH_CHECK(V >= 1, "viewset_gather: at least one index is required");
+    TORCH_CHECK(fovy.is_cuda() && fovy.dim() == 1, "viewset_gather: fovy must be an fp32 [slots] GPU tensor");
+    const c10::Device dev = fovy.device();
+    const c10::DeviceGuard guard(dev);
+    const int64_t slots = fovy.size(0);
+    TORCH_CHECK(num_filled >= 0 && num_filled <= slots, "viewset_gather: num_filled must be in 0..slots");
+    auto f32 = [&](const Tensor &t, std::vector<int64_t> tail, int64_t rows, bool exact, const char *what) {
+        bool ok = t.is_cuda() && t.device() == dev && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.dim() == (int64_t)tail.size() + 1 &&
+                  (exact ? t.size(0) == rows : t.size(0) >= rows);
+        for (size_t d = 0; ok && d < tail.size(); d++) ok = t.size((int64_t)d + 1) == tail[d];
+        TORCH_CHECK(ok, "viewset_gather: ", what, " must be a contiguous fp32 tensor with ", exact ? "" : "at least ", rows, " rows of ", c10::IntArrayRef(tail), " on the store's device, got ",
+                    t.sizes());
+        return t.data_ptr<float>();
+    };
+    egr_viewset_store store = {};
+    egr_viewset_batch batch = {};
+    store.R = f32(R, {3, 3}, slots, true, "R"), store.centers = f32(centers, {3}, slots, true, "centers"), store.fovy = f32(fovy, {}, slots, true, "fovy");
+    batch.R = f32(out_R, {3, 3}, V, false, "out_R"), batch.centers = f32(out_centers, {3}, V, false, "out_centers"), batch.fovy = f32(out_fovy, {}, V, false, "out_fovy");
+    int64_t H = -1, W = -1;
+    for (size_t k = 0; k < EGR_VIEWSET_KINDS; k++) {
+        const Tensor &p = planes[k];
+        const int64_t C = (k == EGR_VIEWSET_DEPTH || k == 5) ? 1 : 3;
+        TORCH_CHECK(p.is_cuda() && p.device() == dev && p.scalar_type() == torch::kFloat16 && p.is_contiguous() && p.dim() == 4 && p.size(0) == slots && p.size(1) == C,
+                    "viewset_gather: planes[", k, "] must be a contiguous half [", slots, ",", C, ",H,W] tensor on the store's device, got ", p.sizes());
+        if (H < 0) H = p.size(2), W = p.size(3);
+        TORCH_CHECK(p.size(2) == H && p.size(3) == W, "viewset_gather: the planes of every kind must share one image size");
+        store.planes[k] = p.data_ptr();
+        const c10::optional<Tensor> o = out.get(k);
+        if (o.has_value() && o->defined()) batch.targets[k] = f32(*o, {C, H, W}, V, false, "out[kind]");
+    }
+    TORCH_CHECK(H > 0 && W > 0 && H <= 65535 && W <= 65535 && slots <= 0xFFFFFFFFll, "viewset_gather: image sizes must be in 1..65535");
+    store.num_slots = (uint32_t)slots, store.num_filled = (uint32_t)num_filled, store.height = (uint32_t)H, store.width = (uint32_t)W;
+    std::vector<uint32_t> idx((size_t)V);
+    for (int64_t v = 0; v < V; v++) {
+        TORCH_CHECK(indices[(size_t)v] >= 0 && indices[(size_t)v] < num_filled, "viewset_gather: index ", indices[(size_t)v], " is out of range: ", num_filled, " slots are filled");
+        idx[(size_t)v] = (uint32_t)indices[(size_t)v];
+    }
+    const int rc = egr_viewset_gather(dev.index(), &store, idx.data(), (uint32_t)V, &batch, current_stream());
+    TORCH_CHECK(rc == 0, egr_viewset_last_error());
+}
+
 // unit-test hook (egr_debug_lean_arith): (a / b, sqrt(a)) as the hot kernels' division and square root compute them
 static std::tuple<torch::Tensor, torch::Tensor> debug_lean_arith(const torch::Tensor &a, const torch::Tensor &b) {
     TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.numel() == b.numel(), "debug_lean_arith: two GPU tensors of one size expected");
@@ -1236,6 +1331,10 @@ TORCH_LIBRARY(egr, m) {
     m.def("voxel_extract(Tensor keys, Tensor acc, Tensor status, int min_count, float voxel_scale, int max_rows) -> "
           "(Tensor coords, Tensor points, Tensor colors, Tensor counts, int largest_count)",
           &voxel_extract);
+    m.def("viewset_ingest(Tensor?[] sources, Tensor?[] tables, Tensor[] planes, Tensor depth_range, int first_slot) -> ()", &viewset_ingest);
+    m.def("viewset_gather(Tensor[] planes, Tensor R, Tensor centers, Tensor fovy, int num_filled, int[] indices, Tensor?[] out, Tensor out_R, Tensor out_centers, "
+          "Tensor out_fovy) -> ()",
+          &viewset_gather);
 }
 
 TORCH_LIBRARY(raytracer, m) {

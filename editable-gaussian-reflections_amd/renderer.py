@@ -363,7 +363,6 @@ def train_views(cameras, raytracer: GaussianRaytracer, targets_available=True, z
     `render(cam)` with grad mode on leaves summed over the cameras, and advances total_num_calls by len(cameras); writes no images. NOTE: the
     gradient is the SUM over the views and total_weight grows by all of them (a V-view training step)."""
     cameras = list(cameras)
-    m = raytracer.cuda_module
     W, H = raytracer.image_width, raytracer.image_height
     with torch.no_grad():
         R, centers, fovy = _stack_cameras(cameras)
@@ -375,9 +374,16 @@ def train_views(cameras, raytracer: GaussianRaytracer, targets_available=True, z
                 continue
             zeros = torch.zeros((ch, H, W), dtype=torch.float32, device="cuda")
             targets.append(torch.stack([zeros if t is None else torch.as_tensor(t).to("cuda", torch.float32) for t in imgs]).contiguous())
+    train_stacked_views(raytracer, R, centers, fovy, targets, znear, zfar)
+
+
+def train_stacked_views(raytracer: GaussianRaytracer, R, centers, fovy, targets, znear=0.01, zfar=999.9):
+    """What `train_views` does once the batch is stacked (dataset.ViewSet.train comes here straight from its gather): R [V,3,3], centers [V,3], fovy [V] and the
+    six `targets` in the order of TRAIN_TARGETS - fp32 [V,C,H,W] on the tracer's device, or None (zeros) - are read in place by the launch."""
+    with torch.no_grad():
         raytracer._export_and_update_bvh()  # the launch follows with the same parameter values (fused live records)
         import_into = raytracer._import_target()
-        m.train_views_import(R, centers, fovy, float(os.getenv("ZNEAR", znear)), float(os.getenv("ZFAR", zfar)), *targets, import_into)
+        raytracer.cuda_module.train_views_import(R, centers, fovy, float(os.getenv("ZNEAR", znear)), float(os.getenv("ZFAR", zfar)), *targets, import_into)
     raytracer.all_reduce_grads()
     if raytracer.import_grads and import_into is None:
         raytracer._import_param_gradients()

@@ -779,6 +779,80 @@ int egr_voxel_extract(int device, const int64_t *keys, const int64_t *acc, int64
                       size_t workspace_bytes, void *hip_stream);
 const char *egr_voxel_last_error(void);
 
+/* ---- The training views, resident in fp16 (additive symbols of library version 0.8, egr_version() is unchanged): what scene/cameras.py:59-82
+ * (Camera.__init__: the 8-bit conversions and seven .half() images per view), dataset/blender_dataset.py:112-129 (_resize_image_tensor) and
+ * scene/scene.py:107-121 (autoadjust_zplanes: depth min / max per view) do per image with torch, as ONE launch per chunk of views into a store the caller
+ * owns, and ONE launch that turns a batch of stored views into the fp32 arrays the batch calls read (csrc/viewset.hip). Context-free like egr_grow_*: the
+ * library allocates nothing, every call is asynchronous on the stream, and arguments are validated BEFORE any HIP call (non-zero return,
+ * egr_viewset_last_error() says why, nothing was touched).
+ *
+ * The kinds, in this order everywhere: 0 render, 1 diffuse, 2 specular, 3 depth, 4 normal, 5 roughness, 6 f0. The store holds, per kind, fp16 planes
+ * [num_slots][C][height][width] (channel-major, as Camera holds them) with C = 3, except C = 1 for depth and roughness; a row of depth_range
+ * [num_slots][2] fp32 per slot; and, for egr_viewset_gather, the camera rows R [num_slots][9], centers [num_slots][3], fovy [num_slots] in fp32.
+ *
+ * egr_viewset_ingest: views first_slot .. first_slot + num_views of the store from sources[kind].data [num_views][src_height][src_width][channels]
+ * (pixel-major, the dataset's layout) of uint8 (EGR_VIEWSET_U8) or fp32 (EGR_VIEWSET_F32). A kind whose data is NULL is ABSENT: its planes are not
+ * written (a store that started as zeros keeps zeros there). channels is 3 for the colour kinds and 1 or 3 for depth and roughness, which take CHANNEL 0
+ * of a 3-channel source.
+ *   resize     when src_height != height: torch's adaptive average ("area"). The caller's sizes must satisfy width == (uint32_t)((double)height *
+ *              ((double)src_width / (double)src_height)) (_resize_image_tensor's output size in Python floats); with src_height == height, src_width ==
+ *              width. Window i of an axis covers floor(i * src / dst) up to but excluding ceil((i + 1) * src / dst).
+ *   fp32       the fp32 sum of the window in row-major order starting from +0, ONE correctly rounded IEEE division by the element count, then
+ *              round-to-nearest-even to half: above 65504 (from 65520) is inf, NaN stays NaN, -0 and subnormals as IEEE rounds them. Without resize: the
+ *              value itself, rounded to half.
+ *   uint8      the integer sum of the window floor-divided by the count (= .float() -> area -> .byte() upstream), then sources[kind].table[byte]: 256 halfs
+ *              in device memory that the caller computed (Camera.__init__'s expressions; there is no pow on the device). uint8 depth is refused, as upstream.
+ *              A uint8 source is read as the ALIGNED 32-bit words that contain its bytes: up to 3 bytes past its end inside the last word are read and ignored.
+ *   range      depth_range[slot] = (min, max) of the STORED half depth plane as fp32 when depth is present (else the row is not written). The call first
+ *              sets the rows to (+inf, -inf); the ingest launch reduces order-preserving integer keys (bits ^ (sign ? ~0 : 1 << 31): -0 < +0) per wave and
+ *              per workgroup, and each workgroup then makes one integer atomic per end on the fp32 bit pattern itself (signed min / unsigned max by the
+ *              sign bit), so min and max do not depend on arrival order and need no decoding pass. Any NaN in the plane gives (NaN, NaN), as torch's
+ *              amin / amax: a NaN is the extreme pattern of its end (0xFFC00000 / 0x7FC00000) and wins against every number in any order.
+ * Refused: a NULL table of sources or depth_range, num_views, a size == 0 or > 65535, a window of more than 2^24 elements, the size rule above, first_slot +
+ * num_views > num_slots, every kind absent, channels other than 1 or 3 (or 1 for a colour kind), an unknown dtype, uint8 depth, a uint8 source
+ * without its table, an fp32 source WITH a table, present data without planes, an fp32 source that is not 4-byte aligned, planes that are not 2-byte
+ * aligned, an output (the written planes, the written depth_range rows) that overlaps an input (data, table) or another output.
+ *
+ * egr_viewset_gather: for v < num_views, out->targets[kind][v] (fp32 [num_views][C][height][width], NULL = not wanted) = (float)planes[kind][indices[v]] -
+ * exactly float(half) - and out->R / centers / fovy [v] = the store's rows indices[v] (each NULL = not wanted). `indices` is a HOST array read during the
+ * call: it travels in the kernel arguments, EGR_VIEWSET_MAX_GATHER per launch (more views make more launches); no upload, no synchronisation. Repeats and any
+ * order are allowed. Refused: a NULL store, out or indices, num_views == 0, height or width == 0, an index >= num_filled, num_filled > num_slots, a wanted
+ * kind without planes, a wanted camera row without its store array, nothing wanted, an output that is not 4-byte aligned, an output that overlaps the store
+ * or another output. */
+#define EGR_VIEWSET_KINDS 7
+#define EGR_VIEWSET_DEPTH 3 /* the kind whose min / max is reduced */
+#define EGR_VIEWSET_U8 0u
+#define EGR_VIEWSET_F32 1u
+#define EGR_VIEWSET_MAX_GATHER 64 /* view indices per launch */
+typedef struct egr_viewset_source {
+    const void *data;  /* [num_views][src_height][src_width][channels]; NULL = the kind is absent  */
+    const void *table; /* 256 halfs, device memory: required for uint8, must be NULL for fp32     */
+    void *planes;      /* the store's fp16 [num_slots][C][height][width] of this kind            */
+    uint32_t channels; /* 1 or 3                                                                */
+    uint32_t dtype;    /* EGR_VIEWSET_U8 or EGR_VIEWSET_F32                                      */
+} egr_viewset_source;
+typedef struct egr_viewset_store {
+    const void *planes[EGR_VIEWSET_KINDS]; /* fp16 [num_slots][C][height][width]; NULL where no kind is wanted */
+    const float *R;                        /* [num_slots][9]  */
+    const float *centers;                  /* [num_slots][3]  */
+    const float *fovy;                     /* [num_slots]     */
+    uint32_t num_slots;
+    uint32_t num_filled; /* indices must be below this */
+    uint32_t height;
+    uint32_t width;
+} egr_viewset_store;
+typedef struct egr_viewset_batch {
+    float *targets[EGR_VIEWSET_KINDS]; /* fp32 [num_views][C][height][width]; NULL = not wanted */
+    float *R;                          /* [num_views][9]; NULL = not wanted */
+    float *centers;                    /* [num_views][3] */
+    float *fovy;                       /* [num_views]    */
+} egr_viewset_batch;
+int egr_viewset_ingest(int device, const egr_viewset_source *sources, uint32_t num_views, uint32_t src_height, uint32_t src_width, uint32_t height,
+                       uint32_t width, uint32_t first_slot, uint32_t num_slots, float *depth_range, void *hip_stream);
+int egr_viewset_gather(int device, const egr_viewset_store *store, const uint32_t *indices, uint32_t num_views, const egr_viewset_batch *out,
+                       void *hip_stream);
+const char *egr_viewset_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif
