@@ -116,6 +116,42 @@ def ssim_images(num_views, height, width, pred, gt, ssim_sum, ssim, workspace, d
         raise RuntimeError(L.egr_eval_last_error().decode())
 
 
+# evaluation frames (csrc/frames.hip): seven kinds in fixed order, prediction and ground truth as bytes, exact 8-bit metrics
+EGR_FRAMES_KINDS, EGR_FRAMES_ALL_KINDS = 7, 0x7F
+EGR_FRAMES_ROUND_SAVE, EGR_FRAMES_ROUND_TRUNC = 0, 1
+EGR_FRAMES_DEPTH_MAX, EGR_FRAMES_DEPTH_MINMAX = 0, 1
+EGR_FRAMES_SEPARATE, EGR_FRAMES_SIDE_BY_SIDE = 0, 1
+EGR_FRAMES_PIXELS_PER_WG, EGR_FRAMES_RANGE_BLOCKS = 4096, 64
+FRAMES_KINDS = ("render", "diffuse", "specular", "depth", "normal", "roughness", "f0")  # bit k of `kinds`, the order of every per-kind array
+FRAMES_PREDICTIONS = ("final", "rgb", "depth", "normal", "roughness", "f0")
+egr_frames_args = _struct("egr_frames_args", [(k, C.c_uint32) for k in ("num_views", "height", "width", "kinds", "rounding", "depth_mode", "layout", "reserved")]
+                          + [(k, _F) for k in FRAMES_PREDICTIONS] + [("targets", C.c_void_p * EGR_FRAMES_KINDS), ("frames", _U8), ("sse8", C.c_void_p), ("psnr8", C.c_void_p),
+                                                                     ("depth_range", _F), ("workspace", C.c_void_p)])
+
+
+def frames_workspace_bytes(num_views, height, width):
+    """EGR_FRAMES_WORKSPACE_BYTES(V, H, W) of the header: per view EGR_FRAMES_RANGE_BLOCKS pairs of uint32 keys and one partial of 21 uint32 sums per workgroup of
+    EGR_FRAMES_PIXELS_PER_WG pixels, rounded up to a multiple of 8."""
+    return (num_views * (EGR_FRAMES_RANGE_BLOCKS * 8 + ((height * width + EGR_FRAMES_PIXELS_PER_WG - 1) // EGR_FRAMES_PIXELS_PER_WG) * (21 * 4)) + 7) & ~7
+
+
+def eval_frames(num_views, height, width, frames, sse8, psnr8, workspace, predictions=None, targets=None, kinds=EGR_FRAMES_ALL_KINDS, rounding=EGR_FRAMES_ROUND_SAVE,
+                depth_mode=EGR_FRAMES_DEPTH_MAX, layout=EGR_FRAMES_SEPARATE, depth_range=None, device=0, stream=0):
+    """egr_eval_frames on integer device addresses (include/egr_raytracer.h has the shapes; None = NULL). `predictions`: dict name of FRAMES_PREDICTIONS -> address;
+    `targets`: dict kind name of FRAMES_KINDS -> address. `workspace`: frames_workspace_bytes() bytes, 8-byte aligned."""
+    L = lib()
+    predictions, targets = predictions or {}, targets or {}
+    unknown = (set(predictions) - set(FRAMES_PREDICTIONS)) | (set(targets) - set(FRAMES_KINDS))
+    if unknown:
+        raise ValueError(f"unknown names {sorted(unknown)}; expected predictions of {FRAMES_PREDICTIONS} and targets of {FRAMES_KINDS}")
+    a = egr_frames_args(num_views=num_views, height=height, width=width, kinds=kinds, rounding=rounding, depth_mode=depth_mode, layout=layout, frames=frames, sse8=sse8,
+                        psnr8=psnr8, depth_range=depth_range, workspace=workspace, **{k: predictions.get(k) for k in FRAMES_PREDICTIONS})
+    for k, name in enumerate(FRAMES_KINDS):
+        a.targets[k] = targets.get(name)
+    if L.egr_eval_frames(device, C.byref(a), C.c_void_p(stream)) != 0:
+        raise RuntimeError(L.egr_eval_last_error().decode())
+
+
 # the dense-init cloud (csrc/initcloud.hip): a hash table of voxels in three caller-owned device buffers
 EGR_VOXEL_STATUS_WORDS = 8
 EGR_VOXEL_MIN_CAPACITY, EGR_VOXEL_MAX_CAPACITY = 1024, 1 << 31
@@ -279,6 +315,7 @@ def lib(path=None):
         # fused SSIM (csrc/ssim.hip): device, V, H, W, final, rgb, target_final, target_diffuse, target_specular, ssim_sum, ssim, workspace, stream
         L.egr_eval_ssim.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P, P, P, P, P, P]
         L.egr_ssim_images.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P, P, P]  # device, V, H, W, pred, gt, ssim_sum, ssim, workspace, stream
+        L.egr_eval_frames.argtypes = [C.c_int, C.POINTER(egr_frames_args), P]  # evaluation frames (csrc/frames.hip): device, args, stream
         # the dense-init cloud (csrc/initcloud.hip). accumulate: device, keys, acc, status, cap, V, H, W, c2w, origin, view_size, depth, colour, colour_u8, colour_table,
         # voxel_scale, colour_max, positions_out, stream
         L.egr_voxel_accumulate.argtypes = [C.c_int, P, P, P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P, P, P, P, C.c_double, C.c_double, P, P]

@@ -1127,6 +1127,61 @@ static std::tuple<Tensor, Tensor> ssim_images(const Tensor &pred, const Tensor &
     return {sum, mean};
 }
 
+// Evaluation frames (egr_eval_frames, csrc/frames.hip): the predictions as render_views hands them out - final [V,H,W,3], rgb / normal / f0 [V,3,H,W,3], depth /
+// roughness [V,3,H,W,1] - and the channel-major targets [V,3,H,W] ([V,1,H,W] for depth and roughness), every one optional, contiguous fp32 on one GPU. `kinds` is the
+// bitmask of the header, `rounding` and `depth_mode` its constants. Returns (frames uint8 [V,7,2,H,W,3] or, side by side, [V,7,H,2W,3]; sse8 int64 [V,7,3]; psnr8 fp64
+// [V,7,2]; depth_range fp32 [V,2]) on the device, allocated with empty: slots the call does not write are unspecified. At most three launches on the current stream, no
+// host synchronisation.
+static std::tuple<Tensor, Tensor, Tensor, Tensor> eval_frames(const c10::optional<Tensor> &final, const c10::optional<Tensor> &rgb, const c10::optional<Tensor> &depth,
+                                                              const c10::optional<Tensor> &normal, const c10::optional<Tensor> &roughness, const c10::optional<Tensor> &f0,
+                                                              const c10::optional<Tensor> &t_final, const c10::optional<Tensor> &t_diffuse, const c10::optional<Tensor> &t_specular,
+                                                              const c10::optional<Tensor> &t_depth, const c10::optional<Tensor> &t_normal, const c10::optional<Tensor> &t_roughness,
+                                                              const c10::optional<Tensor> &t_f0, int64_t kinds, int64_t rounding, int64_t depth_mode, bool side_by_side) {
+    struct In { const c10::optional<Tensor> *t; const char *name; bool pixel_major; int64_t channels; };
+    const In in[13] = {{&final, "final", true, 3}, {&rgb, "rgb", true, 3}, {&depth, "depth", true, 1}, {&normal, "normal", true, 3}, {&roughness, "roughness", true, 1}, {&f0, "f0", true, 3},
+                       {&t_final, "t_final", false, 3}, {&t_diffuse, "t_diffuse", false, 3}, {&t_specular, "t_specular", false, 3}, {&t_depth, "t_depth", false, 1},
+                       {&t_normal, "t_normal", false, 3}, {&t_roughness, "t_roughness", false, 1}, {&t_f0, "t_f0", false, 3}};
+    const Tensor *first = nullptr;
+    int64_t V = 0, H = 0, W = 0;
+    for (int i = 0; i < 13 && !first; i++) {
+        if (!in[i].t->has_value() || !(*in[i].t)->defined()) continue;
+        first = &**in[i].t;
+        const int64_t want_dim = i == 0 || !in[i].pixel_major ? 4 : 5;
+        TORCH_CHECK(first->dim() == want_dim, "eval_frames: ", in[i].name, " must have ", want_dim, " dimensions, got ", first->sizes());
+        V = first->size(0), H = first->size(want_dim - (in[i].pixel_major ? 3 : 2)), W = first->size(want_dim - (in[i].pixel_major ? 2 : 1));
+    }
+    TORCH_CHECK(first && first->is_cuda(), "eval_frames: at least one GPU tensor is required");
+    TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && H <= 0x7FFFFFFF && W <= 0x7FFFFFFF, "eval_frames: at least one view and one pixel are required");
+    TORCH_CHECK(kinds >= 0 && kinds <= 0xFFFFFFFFll && rounding >= 0 && rounding <= 0xFFFFFFFFll && depth_mode >= 0 && depth_mode <= 0xFFFFFFFFll, "eval_frames: kinds, rounding and depth_mode are the header's unsigned constants");
+    const auto dev = first->device();
+    const c10::DeviceGuard guard(dev); // the outputs, the workspace and current_stream() belong to the inputs' device, which need not be the current one
+    const float *p[13];
+    for (int i = 0; i < 13; i++) {
+        p[i] = nullptr;
+        if (!in[i].t->has_value() || !(*in[i].t)->defined()) continue;
+        const Tensor &t = **in[i].t;
+        const std::vector<int64_t> want = i == 0 ? std::vector<int64_t>{V, H, W, 3} : in[i].pixel_major ? std::vector<int64_t>{V, EGR_NUM_STEPS, H, W, in[i].channels} : std::vector<int64_t>{V, in[i].channels, H, W};
+        TORCH_CHECK(t.is_cuda() && t.device() == dev && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.sizes() == torch::IntArrayRef(want), "eval_frames: ", in[i].name,
+                    " must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " on one GPU, got ", t.sizes());
+        p[i] = t.data_ptr<float>();
+    }
+    const auto opt = [&](torch::ScalarType ty) { return torch::dtype(ty).device(dev); };
+    Tensor frames = side_by_side ? torch::empty({V, EGR_FRAMES_KINDS, H, 2 * W, 3}, opt(torch::kUInt8)) : torch::empty({V, EGR_FRAMES_KINDS, 2, H, W, 3}, opt(torch::kUInt8));
+    Tensor sse8 = torch::empty({V, EGR_FRAMES_KINDS, 3}, opt(torch::kInt64)), psnr8 = torch::empty({V, EGR_FRAMES_KINDS, 2}, opt(torch::kFloat64));
+    Tensor range = torch::empty({V, 2}, opt(torch::kFloat32));
+    Tensor workspace = torch::empty({(int64_t)((EGR_FRAMES_WORKSPACE_BYTES(V, H, W) + 7) / 8)}, opt(torch::kFloat64)); // (whole doubles that hold every byte; freed stream-ordered by the caching allocator)
+    egr_frames_args a{};
+    a.num_views = (uint32_t)V, a.height = (uint32_t)H, a.width = (uint32_t)W;
+    a.kinds = (uint32_t)kinds, a.rounding = (uint32_t)rounding, a.depth_mode = (uint32_t)depth_mode, a.layout = side_by_side ? EGR_FRAMES_SIDE_BY_SIDE : EGR_FRAMES_SEPARATE;
+    a.final = p[0], a.rgb = p[1], a.depth = p[2], a.normal = p[3], a.roughness = p[4], a.f0 = p[5];
+    for (int k = 0; k < EGR_FRAMES_KINDS; k++) a.targets[k] = p[6 + k];
+    a.frames = frames.data_ptr<uint8_t>(), a.sse8 = sse8.data_ptr<int64_t>(), a.psnr8 = psnr8.data_ptr<double>(), a.depth_range = range.data_ptr<float>();
+    a.workspace = workspace.data_ptr();
+    const int rc = egr_eval_frames(dev.index(), &a, current_stream());
+    TORCH_CHECK(rc == 0, egr_eval_last_error());
+    return {frames, sse8, psnr8, range};
+}
+
 // The dense-init cloud (egr_voxel_*, csrc/initcloud.hip). The table is three caller-owned GPU tensors: keys int64 [cap] (filled with -1), acc int64 [cap,4] and
 // status int64 [8] (zeroed). voxel_accumulate adds V views in one launch: c2w fp64 [V,3,3], origin fp64 [V,3], view_size fp64 [V] (the caller's host fp64 camera
 // set-up, uploaded), depth fp32 [V,H,W], colour fp32 or uint8 [V,H,W,3] (uint8 with the 256-entry fp32 table), positions_out fp64 [V,H,W,3] or None.
@@ -1324,6 +1379,10 @@ TORCH_LIBRARY(egr, m) {
           &eval_metrics);
     m.def("eval_ssim(Tensor final, Tensor? rgb, Tensor? target_final, Tensor? target_diffuse, Tensor? target_specular) -> (Tensor ssim_sum, Tensor ssim)", &eval_ssim);
     m.def("ssim_images(Tensor pred, Tensor gt) -> (Tensor ssim_sum, Tensor ssim)", &ssim_images);
+    m.def("eval_frames(Tensor? final, Tensor? rgb, Tensor? depth, Tensor? normal, Tensor? roughness, Tensor? f0, Tensor? t_final, Tensor? t_diffuse, Tensor? t_specular, "
+          "Tensor? t_depth, Tensor? t_normal, Tensor? t_roughness, Tensor? t_f0, int kinds, int rounding, int depth_mode, bool side_by_side) -> "
+          "(Tensor frames, Tensor sse8, Tensor psnr8, Tensor depth_range)",
+          &eval_frames);
     m.def("voxel_accumulate(Tensor keys, Tensor acc, Tensor status, Tensor c2w, Tensor origin, Tensor view_size, Tensor depth, Tensor colour, Tensor? colour_table, "
           "float voxel_scale, float colour_max, Tensor? positions_out=None) -> ()",
           &voxel_accumulate);

@@ -7,6 +7,8 @@
 * `transforms_{train,test}.json` (dataset/blender_dataset.py:30-75): `camera_angle_x` + frames sorted by `file_path`, each with a
   camera-to-world `transform_matrix` that is converted from Blender (Y up, Z back) to COLMAP axes and inverted.
 * `cfg.json` = `vars(Config)` (train.py:68-69).
+* the PNG frames of render.py:231-292 (`torchvision.utils.save_image`) that metrics.py reads back: `write_png` / `read_png`, 8-bit grey / RGB, one zlib
+  stream, with `zlib` and `struct` of the standard library alone (no PIL import anywhere in the package).
 
 Host-side Python like the reference's own loaders; numpy only. The PLY reader handles ascii / binary little / big endian files
 whose first element has scalar properties (what both writers above and plyfile produce); later elements are ignored.
@@ -14,6 +16,8 @@ whose first element has scalar properties (what both writers above and plyfile p
 import json
 import math
 import os
+import struct
+import zlib
 
 import numpy as np
 
@@ -166,3 +170,130 @@ def save_cfg(path, cfg):
 def load_cfg(path):
     with open(path) as f:
         return json.load(f)
+
+
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2}  # what write_png applies (one type for the whole image); read_png decodes all five
+_PNG_CHANNELS = {0: 1, 2: 3, 6: 4}  # colour type -> samples per pixel, of the types read_png takes
+
+
+def _png_chunk(kind, data):
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def encode_png(array, level=6, filter="up"):
+    """The bytes of an 8-bit PNG of `array`: uint8 [H,W,3] (colour type 2) or [H,W] (colour type 0), not interlaced, ONE IDAT chunk holding one zlib stream of
+    `level` (0..9). `filter` is applied to every row, vectorised in numpy: "none", "sub" (minus the pixel to the left) or "up" (minus the row above)."""
+    a = np.asarray(array)
+    if a.dtype != np.uint8 or not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"write_png: a uint8 [H,W,3] or [H,W] array with H, W >= 1 is required, got {a.dtype} {a.shape}")
+    if filter not in PNG_FILTERS:
+        raise ValueError(f"write_png: filter must be one of {sorted(PNG_FILTERS)}, got {filter!r}")
+    if not 0 <= int(level) <= 9:
+        raise ValueError(f"write_png: level must be in 0..9, got {level}")
+    H, W = a.shape[:2]
+    bpp = 1 if a.ndim == 2 else 3
+    rows = np.ascontiguousarray(a).reshape(H, W * bpp)
+    raw = np.empty((H, 1 + W * bpp), dtype=np.uint8)
+    raw[:, 0] = PNG_FILTERS[filter]
+    body = raw[:, 1:]
+    body[...] = rows
+    if filter == "sub":
+        body[:, bpp:] -= rows[:, :-bpp]  # (uint8 arithmetic wraps modulo 256, as the format asks)
+    elif filter == "up":
+        body[1:] -= rows[:-1]
+    ihdr = struct.pack(">IIBBBBB", W, H, 8, 0 if a.ndim == 2 else 2, 0, 0, 0)
+    return PNG_SIGNATURE + _png_chunk(b"IHDR", ihdr) + _png_chunk(b"IDAT", zlib.compress(raw.tobytes(), int(level))) + _png_chunk(b"IEND", b"")
+
+
+def write_png(path_or_file, array, level=6, filter="up"):
+    """Writes `encode_png(array, level, filter)` to a path or to a binary file object. Returns the number of bytes written."""
+    data = encode_png(array, level, filter)
+    if hasattr(path_or_file, "write"):
+        path_or_file.write(data)
+    else:
+        with open(path_or_file, "wb") as f:
+            f.write(data)
+    return len(data)
+
+
+def decode_png(data):
+    """The uint8 array of an 8-bit, non-interlaced grey ([H,W]), RGB ([H,W,3]) or RGBA ([H,W,4]) PNG held in `data`. All five filter types are decoded and every
+    chunk's CRC is verified. Everything else is refused by name: 16-bit (or 1 / 2 / 4-bit) samples, palette and grey-alpha images, interlacing, a bad CRC."""
+    data = bytes(data)
+    if data[:8] != PNG_SIGNATURE:
+        raise ValueError("read_png: not a PNG file (bad signature)")
+    at, header, idat, ended = 8, None, [], False
+    while at < len(data) and not ended:
+        if at + 12 > len(data):
+            raise ValueError("read_png: truncated chunk")
+        (n,), kind = struct.unpack(">I", data[at : at + 4]), data[at + 4 : at + 8]
+        body = data[at + 8 : at + 8 + n]
+        if at + 12 + n > len(data):
+            raise ValueError("read_png: truncated chunk " + kind.decode("latin-1"))
+        if struct.unpack(">I", data[at + 8 + n : at + 12 + n])[0] != (zlib.crc32(kind + body) & 0xFFFFFFFF):
+            raise ValueError("read_png: bad CRC in chunk " + kind.decode("latin-1"))
+        at += 12 + n
+        if header is None and kind != b"IHDR":
+            raise ValueError("read_png: the first chunk is not IHDR")
+        if kind == b"IHDR":
+            header = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            idat.append(body)
+        elif kind == b"IEND":
+            ended = True
+    if header is None or not ended:
+        raise ValueError("read_png: IHDR or IEND is missing")
+    W, H, depth, colour, compression, filt, interlace = header
+    if colour == 3:
+        raise ValueError("read_png: palette images are not supported")
+    if depth == 16:
+        raise ValueError("read_png: 16-bit images are not supported")
+    if depth != 8:
+        raise ValueError(f"read_png: {depth}-bit images are not supported")
+    if colour not in _PNG_CHANNELS:
+        raise ValueError(f"read_png: colour type {colour} (grey with alpha) is not supported")
+    if interlace != 0:
+        raise ValueError("read_png: interlaced images are not supported")
+    if compression != 0 or filt != 0 or W < 1 or H < 1:
+        raise ValueError("read_png: unknown compression or filter method, or an empty image")
+    bpp = _PNG_CHANNELS[colour]
+    stride = W * bpp
+    raw = np.frombuffer(zlib.decompress(b"".join(idat)), dtype=np.uint8)
+    if raw.size != H * (stride + 1):
+        raise ValueError(f"read_png: {raw.size} bytes of image data, expected {H * (stride + 1)}")
+    raw = raw.reshape(H, stride + 1)
+    types, out = raw[:, 0], raw[:, 1:].copy()
+    if types.max() > 4:
+        raise ValueError(f"read_png: unknown filter type {int(types.max())}")
+    zero = np.zeros(stride, dtype=np.uint8)
+    for y in np.flatnonzero(types):  # (rows of type 0 are done)
+        t, row, up = int(types[y]), out[y], (out[y - 1] if y else zero)
+        if t == 2:
+            row += up
+        elif t == 1:  # a running sum per channel, modulo 256
+            out[y] = np.cumsum(row.reshape(W, bpp), axis=0, dtype=np.uint64).astype(np.uint8).reshape(-1)
+        else:  # average and Paeth depend on the decoded pixel to the left: pixel by pixel, the channels of a pixel at once
+            r, u = row.reshape(W, bpp).astype(np.int32), up.reshape(W, bpp).astype(np.int32)
+            a = np.zeros(bpp, dtype=np.int32)
+            c = np.zeros(bpp, dtype=np.int32)
+            for x in range(W):
+                b = u[x]
+                if t == 3:
+                    pred = (a + b) >> 1
+                else:
+                    pa, pb, pc = np.abs(b - c), np.abs(a - c), np.abs(a + b - 2 * c)
+                    pred = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+                a = (r[x] + pred) & 0xFF
+                r[x] = a
+                c = b
+            out[y] = r.astype(np.uint8).reshape(-1)
+    return out.reshape(H, W) if bpp == 1 else out.reshape(H, W, bpp)
+
+
+def read_png(path_or_file):
+    """`decode_png` of a path or of a binary file object."""
+    if hasattr(path_or_file, "read"):
+        return decode_png(path_or_file.read())
+    with open(path_or_file, "rb") as f:
+        return decode_png(f.read())

@@ -721,6 +721,75 @@ int egr_eval_ssim(int device, uint32_t num_views, uint32_t height, uint32_t widt
 int egr_ssim_images(int device, uint32_t num_views, uint32_t height, uint32_t width, const float *pred, const float *gt, double *ssim_sum, double *ssim,
                     void *workspace, void *hip_stream);
 
+/* ---- Evaluation frames and exact 8-bit metrics (additive symbols of library version 0.8, egr_version() is unchanged): the fourteen images render.py:218-292
+ * writes per test view - seven kinds, prediction and ground truth - as bytes ready for a PNG encoder, and the PSNR metrics.py measures on those bytes, for V views
+ * in at most THREE launches (csrc/frames.hip). Context-free; errors are reported through egr_eval_last_error(). Every pointer of the arguments may be NULL
+ * except frames, sse8, psnr8 and workspace.
+ *
+ * Seven kinds in fixed order; bit k of `kinds` selects kind k. Both sides of a kind go through the same value map before quantisation:
+ *   0 render     final [V][H][W][3]                          against targets[0] (original)   D(x): the tone curve and clamp of egr_eval_metrics - the same device
+ *   1 diffuse    rgb[v][0], rgb = [V][3][H][W][3]            against targets[1]              function, bit for bit
+ *   2 specular   rgb[v][1] + rgb[v][2] (one fp32 add)        against targets[2]              D(x)
+ *   3 depth      depth[v][0], depth = [V][3][H][W][1]        against targets[3], one channel EGR_FRAMES_DEPTH_MAX: x / hi (render.py:250-255);
+ *                                                                                            EGR_FRAMES_DEPTH_MINMAX: (x - lo) / (hi - lo) (train.py:152).
+ *                lo, hi = the minimum and maximum of THAT view's target depth (a NaN takes both ends, as torch's amin / amax); one correctly rounded division
+ *   4 normal     normal[v][0], [V][3][H][W][3]               against targets[4]              x / 2 + 0.5: two fp32 roundings, no contraction
+ *   5 roughness  roughness[v][0], [V][3][H][W][1]            against targets[5], one channel identity
+ *   6 f0         f0[v][0], [V][3][H][W][3]                   against targets[6]              identity
+ * The predictions are pixel-major, as egr_render_views writes them; the targets are channel-major fp32 [V][C][H][W]. One-channel kinds are replicated to three
+ * channels (save_image / make_grid, repeat(3, 1, 1)).
+ * The byte of a mapped value x, every fp32 operation rounded on its own:
+ *   EGR_FRAMES_ROUND_SAVE    x * 255, + 0.5, clamp to [0, 255], truncate: torchvision's save_image. torchvision is not available where this library is tested:
+ *                            the rule is stated here as a DEFINITION and is not pinned by a fixture.
+ *   EGR_FRAMES_ROUND_TRUNC   clamp to [0, 1], * 255, truncate: format_image of render.py:303.
+ *   NaN gives byte 0 - torch leaves that conversion unspecified, so this is a definition of this library -, +inf gives 255 and -inf gives 0.
+ * Outputs (device):
+ *   frames       uint8, interleaved RGB. EGR_FRAMES_SEPARATE: [V][7][2 sides][H][W][3], side 0 the prediction, side 1 the ground truth. EGR_FRAMES_SIDE_BY_SIDE:
+ *                [V][7][H][2W][3], prediction left and ground truth right (the vs_target images of training_report, the cat(dim = 2) of the videos).
+ *   sse8         [V][7][3] int64: the exact sum over the pixels of (pred_byte - gt_byte)^2 per channel. Integers: no summation order, no rounding.
+ *   psnr8        [V][7][2] fp64, from sse8 on the device with mse = sse8 / (255^2 n): [0] the reference's per-channel-then-mean flavour, [1] 10 log10(1 / mse) over
+ *                all three channels = PeakSignalNoiseRatio(data_range = 1) on to_tensor bytes, what metrics.py measures. An mse of 0 gives +inf.
+ *   depth_range  [V][2] fp32 or NULL: (lo, hi), written when depth is selected and its target given.
+ * Which slots are written: those of the selected kinds only. A selected kind writes its prediction side when its prediction is given and its ground-truth side
+ * when its target is given; both sides of depth need targets[3], without it the depth kind writes no frame. A selected kind that lacks either side reports
+ * sse8 = -1 and psnr8 = NaN. Slots of unselected kinds, and sides that are not written, keep what they hold.
+ * k_frames_range (only when depth is written) stores one (min, max) per workgroup, k_frames_write (EGR_FRAMES_BLOCKS x V workgroups of 256 threads, one lane per
+ * four consecutive pixels: 16-byte loads, 12 bytes stored per frame when H * W % 4 == 0 - side by side: and W % 4 == 0 -, element-wise accesses with the same
+ * results otherwise) stores one partial of 21 integer sums per workgroup, k_frames_finish (one workgroup per view) adds them. No atomics, no memset.
+ * workspace: EGR_FRAMES_WORKSPACE_BYTES(V, H, W) bytes of device memory, 8-byte aligned, owned by the caller, free for reuse once the stream has passed the call.
+ * Refused BEFORE any HIP call (non-zero, egr_eval_last_error() says why): V == 0 (or > 65535), H or W == 0, an empty or unknown kinds / rounding / depth_mode /
+ * layout, diffuse or specular selected with its target but without rgb, a NULL frames / sse8 / psnr8 / workspace, a misaligned workspace, an output that overlaps
+ * an input or another output. Asynchronous on the stream. */
+#define EGR_FRAMES_KINDS 7
+#define EGR_FRAMES_ALL_KINDS 0x7Fu
+#define EGR_FRAMES_ROUND_SAVE 0u
+#define EGR_FRAMES_ROUND_TRUNC 1u
+#define EGR_FRAMES_DEPTH_MAX 0u
+#define EGR_FRAMES_DEPTH_MINMAX 1u
+#define EGR_FRAMES_SEPARATE 0u
+#define EGR_FRAMES_SIDE_BY_SIDE 1u
+#define EGR_FRAMES_PIXELS_PER_WG 4096u /* pixels one workgroup of k_frames_write covers: one partial (21 uint32 sums) of workspace */
+#define EGR_FRAMES_RANGE_BLOCKS 64u    /* depth-range partials (two uint32 keys each) per view */
+#define EGR_FRAMES_BLOCKS(H, W) (((size_t)(H) * (size_t)(W) + EGR_FRAMES_PIXELS_PER_WG - 1) / EGR_FRAMES_PIXELS_PER_WG)
+/* (rounded up to a multiple of 8: the partials are 84 bytes each) */
+#define EGR_FRAMES_WORKSPACE_BYTES(V, H, W) ((((size_t)(V) * (EGR_FRAMES_RANGE_BLOCKS * 8 + EGR_FRAMES_BLOCKS(H, W) * (21 * 4))) + 7) & ~(size_t)7)
+typedef struct egr_frames_args {
+    uint32_t num_views, height, width;
+    uint32_t kinds;      /* bit k selects kind k; EGR_FRAMES_ALL_KINDS */
+    uint32_t rounding;   /* EGR_FRAMES_ROUND_* */
+    uint32_t depth_mode; /* EGR_FRAMES_DEPTH_* */
+    uint32_t layout;     /* EGR_FRAMES_SEPARATE or EGR_FRAMES_SIDE_BY_SIDE */
+    uint32_t reserved;   /* 0 */
+    const float *final, *rgb, *depth, *normal, *roughness, *f0; /* predictions, pixel-major */
+    const float *targets[EGR_FRAMES_KINDS];                     /* channel-major, in kind order */
+    uint8_t *frames;
+    int64_t *sse8;
+    double *psnr8;
+    float *depth_range;
+    void *workspace;
+} egr_frames_args;
+int egr_eval_frames(int device, const egr_frames_args *args, void *hip_stream);
+
 /* ---- The dense-init cloud (additive symbols of library version 0.8, egr_version() is unchanged): what prepare_initial_ply.py:52-104 does on the CPU with every
  * pixel of every view in memory - unproject by the depth image, snap to a voxel of 1 / voxel_scale, average the diffuse colours per voxel, keep the voxels
  * seen by at least min_count pixels - as a streamed scatter-reduce into a hash table the caller owns (csrc/initcloud.hip). Context-free like egr_prune_*.
