@@ -555,6 +555,27 @@ int egr_debug_get_bvh_state(egr_context *c, float frame[6], uint32_t info[4], vo
     });
 }
 
+int egr_debug_get_tree(egr_context *c, uint64_t *keys, uint32_t *gid_of_pos, uint32_t *pos_of_gid, int32_t *left, int32_t *right, float *dp,
+                       uint32_t *wnodes, float *bsph, uint32_t *level_start, void *stream) {
+    if (!c) return 1;
+    return guarded(c, [&] {
+        EGR_HIP(hipStreamSynchronize((hipStream_t)stream));
+        const size_t n = c->n_built, nb = n > 1 ? n - 1 : 0, nw = c->num_wide; // (binary nodes exist from two leaves on)
+        auto fetch = [&](void *dst, const void *src, size_t bytes) {
+            if (dst && bytes) EGR_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+        };
+        fetch(keys, c->keys_out, n * sizeof(uint64_t));
+        fetch(gid_of_pos, c->vals_out, n * sizeof(uint32_t));
+        fetch(pos_of_gid, c->pos_of_gid, n * sizeof(uint32_t));
+        fetch(left, c->k_left, nb * sizeof(int32_t));
+        fetch(right, c->k_right, nb * sizeof(int32_t));
+        fetch(dp, c->k_dp, nb * EGR_DP_STRIDE * sizeof(float));
+        fetch(wnodes, c->wnodes, nw * EGR_WIDTH * sizeof(uint4));
+        fetch(bsph, c->bsph, n * sizeof(float4));
+        if (level_start) std::copy(c->level_start.begin(), c->level_start.end(), level_start);
+    });
+}
+
 const char *egr_last_error(egr_context *c) { return c ? c->last_error.c_str() : "libegr_hip: null context"; }
 
 } // extern "C"

@@ -259,9 +259,8 @@ __global__ void __launch_bounds__(BS) k_karras(int n, const uint64_t *__restrict
 // One thread per leaf climbs; the second arrival at a node owns it (atomic counter). The tree is spread over all XCDs whose L2s
 // are not coherent (cdna guide, Guideline 16): every payload word is written and read with agent-scope atomic accesses (sc1,
 // write-through / cache-bypassing), the writer drains its stores before the counter RMW, which itself is acq_rel at agent scope.
-// Record per binary internal node: box lo[3], hi[3], T[1..7] (16 floats, 3 unused). Runs once per rebuild.
+// Record per binary internal node: box lo[3], hi[3], T[1..7] (EGR_DP_STRIDE = 16 floats, 3 unused; egr_debug_get_tree exports them). Runs once per rebuild.
 // ---------------------------------------------------------------------------------------------------------
-#define EGR_DP_STRIDE 16
 __device__ __forceinline__ float ld_agent(const float *p) {
     return __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
@@ -393,13 +392,20 @@ __global__ void __launch_bounds__(BS) k_collapse_level(int n, uint32_t count, co
 
 // ---- 16-bit box quantisation in the build frame. u = (x - origin) * scale + 2 (cells); lo rounds down one extra
 // cell, hi up one extra cell; 0 / 65535 are the out-of-frame sentinels (decoded as -inf / +inf by the traversal).
+// The fp32 u is off by up to three roundings of half an ulp at 65535 (1.5 * 2^-8 cells), and every integer is an fp32 number: a u just below an integer
+// rounds ONTO it, and floorf(u) - 1 would land on floor(u), one cell further in than the extra cell promises (0.15 % of the cells, measured). So the floor
+// is taken EGR_QUANT_SLACK = 2^-6 cells further out (more than the error plus the rounding of that shift): the cell is floor(u) - 1 of the exact u, or
+// one cell beyond it where u lies less than 2^-5 past an integer. Whether a side left the frame is decided on u itself, as ever.
+#define EGR_QUANT_SLACK 0.015625f
 __device__ __forceinline__ uint32_t quant_lo(float x, float o, float s) {
-    float u = (x - o) * s + 2.0f;
-    return (u >= 2.0f) ? (uint32_t)fminf(floorf(u) - 1.0f, 65534.0f) : 0u;
+    const float u = (x - o) * s + 2.0f;
+    const uint32_t c = (uint32_t)fminf(fmaxf(floorf(u - EGR_QUANT_SLACK) - 1.0f, 1.0f), 65534.0f); // (selected below: no branch per side)
+    return (u >= 2.0f) ? c : 0u;
 }
 __device__ __forceinline__ uint32_t quant_hi(float x, float o, float s) {
-    float u = (x - o) * s + 2.0f;
-    return (u <= 65533.0f) ? (uint32_t)fmaxf(ceilf(u) + 1.0f, 1.0f) : 65535u;
+    const float u = (x - o) * s + 2.0f;
+    const uint32_t c = (uint32_t)fmaxf(fminf(ceilf(u + EGR_QUANT_SLACK) + 1.0f, 65534.0f), 1.0f);
+    return (u <= 65533.0f) ? c : 65535u;
 }
 __device__ __forceinline__ void unpack_box(uint4 q, uint32_t lo[3], uint32_t hi[3]) {
     lo[0] = q.x & 0xFFFFu, lo[1] = q.x >> 16, lo[2] = q.y & 0xFFFFu, hi[0] = q.y >> 16, hi[1] = q.z & 0xFFFFu, hi[2] = q.z >> 16;
@@ -419,7 +425,9 @@ __global__ void __launch_bounds__(BS) k_refit_wide_level(uint32_t begin, uint32_
     if (link == EGR_EMPTY_SLOT) {
     } else if (link & EGR_LEAF_FLAG) {
         const uint32_t gid = gid_of_pos[link & ~EGR_LEAF_FLAG];
-        const float *bx = aabb + 6 * (size_t)gid;
+        const float2 *bx2 = reinterpret_cast<const float2 *>(aabb + 6 * (size_t)gid); // (24-byte rows: three 8-byte loads)
+        const float2 b0 = bx2[0], b1 = bx2[1], b2 = bx2[2];
+        const float bx[6] = {b0.x, b0.y, b1.x, b1.y, b2.x, b2.y};
         if (bx[0] <= bx[3]) {
             const float fo[3] = {fr.ox, fr.oy, fr.oz}, fs[3] = {fr.sx, fr.sy, fr.sz};
 #pragma unroll

@@ -198,7 +198,8 @@ struct egr_context {
     uint32_t *vals_in = nullptr, *vals_out = nullptr;
     int32_t *k_left = nullptr, *k_right = nullptr, *k_parent = nullptr; // Karras arrays (index space: internal i, leaf n-1+j)
     uint32_t *k_first = nullptr, *k_last = nullptr;
-    float *k_dp = nullptr;       // SAH collapse: [n_alloc][16] box + T(1..7) per binary internal node (bvh.hip: k_sah_bottom_up)
+#define EGR_DP_STRIDE 16
+    float *k_dp = nullptr;       // SAH collapse: [n_alloc][EGR_DP_STRIDE] box + T(1..7) per binary internal node (bvh.hip: k_sah_bottom_up)
     uint32_t *k_flags = nullptr; // its arrival counters
     uint32_t *scratch_u32 = nullptr; // bounds (6), depth histogram, cursors
     // launch scratch

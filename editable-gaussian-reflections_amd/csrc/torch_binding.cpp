@@ -722,6 +722,22 @@ struct Raytracer : torch::CustomClassHolder {
         for (int k = 0; k < 4; k++) i.data_ptr<int64_t>()[k] = (int64_t)info[k];
         return {f, i};
     }
+    // The built tree on the host (egr_debug_get_tree), in this order: keys int64 [n] (the bits of the uint64 keys), gid_of_pos int32 [n], pos_of_gid int32 [n],
+    // left int32 [n-1], right int32 [n-1], dp float32 [n-1,16], wnodes int32 [nw,8,4] (the bits of the uint32 words), bsph float32 [n,4], level_start int32 [depth+1]
+    std::vector<Tensor> debug_tree() {
+        float frame[6];
+        uint32_t info[4] = {0u, 0u, 0u, 0u};
+        check(egr_debug_get_bvh_state(ctx, frame, info, current_stream()), "debug_tree");
+        const int64_t n = info[3], nb = n > 1 ? n - 1 : 0, nw = info[1], levels = (int64_t)info[2] + 1;
+        Tensor keys = torch::zeros({n}, torch::kInt64), gop = torch::zeros({n}, torch::kInt32), pog = torch::zeros({n}, torch::kInt32);
+        Tensor left = torch::zeros({nb}, torch::kInt32), right = torch::zeros({nb}, torch::kInt32), dp = torch::zeros({nb, 16}, torch::kFloat32);
+        Tensor wn = torch::zeros({nw, 8, 4}, torch::kInt32), bs = torch::zeros({n, 4}, torch::kFloat32), ls = torch::zeros({levels}, torch::kInt32);
+        auto u32 = [](Tensor &t) { return reinterpret_cast<uint32_t *>(t.data_ptr<int32_t>()); };
+        check(egr_debug_get_tree(ctx, reinterpret_cast<uint64_t *>(keys.data_ptr<int64_t>()), u32(gop), u32(pog), left.data_ptr<int32_t>(), right.data_ptr<int32_t>(),
+                                 dp.data_ptr<float>(), u32(wn), bs.data_ptr<float>(), u32(ls), current_stream()),
+              "debug_tree");
+        return {keys, gop, pog, left, right, dp, wn, bs, ls};
+    }
 
     static void bind(torch::Library &m) {
         using Self = c10::intrusive_ptr<Raytracer>;
@@ -804,6 +820,7 @@ struct Raytracer : torch::CustomClassHolder {
             .def("debug_instances", &Raytracer::debug_instances)
             .def("debug_backward_records", &Raytracer::debug_backward_records)
             .def("debug_bvh_state", &Raytracer::debug_bvh_state)
+            .def("debug_tree", &Raytracer::debug_tree)
             .def("debug_step_hits", &Raytracer::debug_step_hits)
             .def("debug_hit_sequence_hash", &Raytracer::debug_hit_sequence_hash);
     }

@@ -403,6 +403,21 @@ int egr_debug_check_bvh(egr_context *ctx, void *hip_stream);
  * frame and carries the -inf / +inf sentinel cells, so the walks run their sentinel decode), wide nodes, depth of the wide tree, gaussian count the tree was
  * built for}. Host pointers; synchronises. */
 int egr_debug_get_bvh_state(egr_context *ctx, float frame[6], uint32_t info[4], void *hip_stream);
+/* The tree the last rebuild produced (and the last refit re-boxed), stage by stage, for tests that restate the builder on the CPU (read-only; an additive
+ * symbol like the one above). One stream synchronisation, then device-to-host copies only: no kernel runs. Every pointer is a host pointer and may be
+ * NULL (that array is skipped). With n = info[3], nw = info[1] and depth = info[2] of egr_debug_get_bvh_state:
+ *   keys        uint64 [n]         the 63-bit Morton keys in sorted order (x bit highest of each triple, 21 bits per axis)
+ *   gid_of_pos  uint32 [n]         gaussian id at every sorted position (the sort's values); pos_of_gid uint32 [n] is its inverse
+ *   left, right int32  [n - 1]     children of the binary (Karras) node i; ids: internal i -> i, leaf at sorted position j -> (n - 1) + j
+ *   dp          float  [n - 1][16] the collapse's row of binary node i, raw: 0-2 box lo xyz, 3-5 box hi xyz, 6-12 T(i, 1..7); 13-15 unused, never written
+ *   wnodes      uint32 [nw][8][4]  the wide nodes: per slot lo.x | lo.y << 16, lo.z | hi.x << 16, hi.y | hi.z << 16 (16-bit cells of the build frame),
+ *                                  link (EGR_LEAF_FLAG | sorted position, child node index, or EGR_EMPTY_SLOT)
+ *   bsph        float  [n][4]      bounding spheres in record order (sorted position): centre xyz, squared radius (< 0: unusable gaussian)
+ *   level_start uint32 [depth + 1] wide nodes of level L are level_start[L] .. level_start[L + 1] - 1 (root = level 0)
+ * left, right and dp are empty for n <= 1 (a single gaussian hangs under a root that no binary node stands for); for n = 0 everything but
+ * level_start = {0} is empty. The unsorted keys are not kept: the collapse reuses their buffer. */
+int egr_debug_get_tree(egr_context *ctx, uint64_t *keys, uint32_t *gid_of_pos, uint32_t *pos_of_gid, int32_t *left, int32_t *right, float *dp,
+                       uint32_t *wnodes, float *bsph, uint32_t *level_start, void *hip_stream);
 
 const char *egr_last_error(egr_context *ctx);
 const char *egr_version(void);
