@@ -87,11 +87,16 @@ def eval_workspace_bytes(num_views, height, width):
     return num_views * ((height * width + EGR_EVAL_PIXELS_PER_WG - 1) // EGR_EVAL_PIXELS_PER_WG) * (9 * 8)
 
 
+def _check(rc, last_error):
+    """A context-free call's status: non-zero raises the message of its module's egr_<x>_last_error (per module and per thread)."""
+    if rc != 0:
+        raise RuntimeError(last_error().decode())
+
+
 def eval_metrics(num_views, height, width, final, rgb, target_final, target_diffuse, target_specular, sse, psnr, workspace, display=None, device=0, stream=0):
     """egr_eval_metrics on integer device addresses (include/egr_raytracer.h has the shapes; None = NULL). `workspace`: eval_workspace_bytes() bytes, 8-byte aligned."""
     L = lib()
-    if L.egr_eval_metrics(device, num_views, height, width, final, rgb, target_final, target_diffuse, target_specular, sse, psnr, display, workspace, C.c_void_p(stream)) != 0:
-        raise RuntimeError(L.egr_eval_last_error().decode())
+    _check(L.egr_eval_metrics(device, num_views, height, width, final, rgb, target_final, target_diffuse, target_specular, sse, psnr, display, workspace, C.c_void_p(stream)), L.egr_eval_last_error)
 
 
 EGR_SSIM_TILE = 32
@@ -105,15 +110,13 @@ def ssim_workspace_bytes(num_views, height, width):
 def eval_ssim(num_views, height, width, final, rgb, target_final, target_diffuse, target_specular, ssim_sum, ssim, workspace, device=0, stream=0):
     """egr_eval_ssim on integer device addresses (include/egr_raytracer.h has the shapes; None = NULL). `workspace`: ssim_workspace_bytes() bytes, 8-byte aligned."""
     L = lib()
-    if L.egr_eval_ssim(device, num_views, height, width, final, rgb, target_final, target_diffuse, target_specular, ssim_sum, ssim, workspace, C.c_void_p(stream)) != 0:
-        raise RuntimeError(L.egr_eval_last_error().decode())
+    _check(L.egr_eval_ssim(device, num_views, height, width, final, rgb, target_final, target_diffuse, target_specular, ssim_sum, ssim, workspace, C.c_void_p(stream)), L.egr_eval_last_error)
 
 
 def ssim_images(num_views, height, width, pred, gt, ssim_sum, ssim, workspace, device=0, stream=0):
     """egr_ssim_images on integer device addresses: pred, gt [V][3][H][W] display images. `workspace`: ssim_workspace_bytes() bytes, 8-byte aligned."""
     L = lib()
-    if L.egr_ssim_images(device, num_views, height, width, pred, gt, ssim_sum, ssim, workspace, C.c_void_p(stream)) != 0:
-        raise RuntimeError(L.egr_eval_last_error().decode())
+    _check(L.egr_ssim_images(device, num_views, height, width, pred, gt, ssim_sum, ssim, workspace, C.c_void_p(stream)), L.egr_eval_last_error)
 
 
 # evaluation frames (csrc/frames.hip): seven kinds in fixed order, prediction and ground truth as bytes, exact 8-bit metrics
@@ -148,8 +151,7 @@ def eval_frames(num_views, height, width, frames, sse8, psnr8, workspace, predic
                         psnr8=psnr8, depth_range=depth_range, workspace=workspace, **{k: predictions.get(k) for k in FRAMES_PREDICTIONS})
     for k, name in enumerate(FRAMES_KINDS):
         a.targets[k] = targets.get(name)
-    if L.egr_eval_frames(device, C.byref(a), C.c_void_p(stream)) != 0:
-        raise RuntimeError(L.egr_eval_last_error().decode())
+    _check(L.egr_eval_frames(device, C.byref(a), C.c_void_p(stream)), L.egr_eval_last_error)
 
 
 # the dense-init cloud (csrc/initcloud.hip): a hash table of voxels in three caller-owned device buffers
@@ -188,16 +190,14 @@ def voxel_accumulate(keys, acc, status, cap, num_views, height, width, c2w, orig
                      colour_max=32768.0, positions_out=None, device=0, stream=0):
     """egr_voxel_accumulate on integer device addresses (include/egr_raytracer.h has the shapes; None = NULL)."""
     L = lib()
-    if L.egr_voxel_accumulate(device, keys, acc, status, cap, num_views, height, width, c2w, origin, view_size, depth, colour, colour_u8, colour_table, voxel_scale, colour_max,
-                              positions_out, C.c_void_p(stream)) != 0:
-        raise RuntimeError(L.egr_voxel_last_error().decode())
+    _check(L.egr_voxel_accumulate(device, keys, acc, status, cap, num_views, height, width, c2w, origin, view_size, depth, colour, colour_u8, colour_table, voxel_scale, colour_max,
+                                  positions_out, C.c_void_p(stream)), L.egr_voxel_last_error)
 
 
 def voxel_rehash(keys, acc, status, cap, src_keys, src_acc, src_cap, device=0, stream=0):
     """egr_voxel_rehash on integer device addresses."""
     L = lib()
-    if L.egr_voxel_rehash(device, keys, acc, status, cap, src_keys, src_acc, src_cap, C.c_void_p(stream)) != 0:
-        raise RuntimeError(L.egr_voxel_last_error().decode())
+    _check(L.egr_voxel_rehash(device, keys, acc, status, cap, src_keys, src_acc, src_cap, C.c_void_p(stream)), L.egr_voxel_last_error)
 
 
 def voxel_extract(keys, acc, status, cap, min_count, voxel_scale, max_rows, coords, points, colors, counts, workspace, workspace_bytes, device=0, stream=0):
@@ -205,8 +205,7 @@ def voxel_extract(keys, acc, status, cap, min_count, voxel_scale, max_rows, coor
     Returns (n, largest count)."""
     L = lib()
     host = (C.c_uint64 * 2)()
-    if L.egr_voxel_extract(device, keys, acc, status, cap, min_count, voxel_scale, max_rows, coords, points, colors, counts, host, workspace, workspace_bytes, C.c_void_p(stream)) != 0:
-        raise RuntimeError(L.egr_voxel_last_error().decode())
+    _check(L.egr_voxel_extract(device, keys, acc, status, cap, min_count, voxel_scale, max_rows, coords, points, colors, counts, host, workspace, workspace_bytes, C.c_void_p(stream)), L.egr_voxel_last_error)
     return int(host[0]), int(host[1])
 
 
@@ -232,8 +231,7 @@ def viewset_ingest(sources, num_views, src_height, src_width, height, width, fir
         if name in sources:
             data, tab, planes, channels, dtype = sources[name]
             table[k] = egr_viewset_source(data=data, table=tab, planes=planes, channels=channels, dtype=dtype)
-    if L.egr_viewset_ingest(device, table, num_views, src_height, src_width, height, width, first_slot, num_slots, depth_range, C.c_void_p(stream)) != 0:
-        raise RuntimeError(L.egr_viewset_last_error().decode())
+    _check(L.egr_viewset_ingest(device, table, num_views, src_height, src_width, height, width, first_slot, num_slots, depth_range, C.c_void_p(stream)), L.egr_viewset_last_error)
 
 
 def viewset_gather(planes, R, centers, fovy, num_slots, num_filled, height, width, indices, targets, out_R=None, out_centers=None, out_fovy=None, device=0, stream=0):
@@ -244,8 +242,7 @@ def viewset_gather(planes, R, centers, fovy, num_slots, num_filled, height, widt
     for k, name in enumerate(VIEWSET_KINDS):
         store.planes[k], batch.targets[k] = planes.get(name), targets.get(name)
     idx = (C.c_uint32 * max(len(indices), 1))(*[int(i) for i in indices])
-    if L.egr_viewset_gather(device, C.byref(store), idx, len(indices), C.byref(batch), C.c_void_p(stream)) != 0:
-        raise RuntimeError(L.egr_viewset_last_error().decode())
+    _check(L.egr_viewset_gather(device, C.byref(store), idx, len(indices), C.byref(batch), C.c_void_p(stream)), L.egr_viewset_last_error)
 
 
 _lib = None

@@ -38,11 +38,8 @@ void egr_stamp_end(egr_context *c, hipStream_t s) {
 namespace {
 template <class F> int guarded(egr_context *c, F &&f) {
     try {
-        int prev = 0;
-        EGR_HIP(hipGetDevice(&prev));
-        if (prev != c->device) EGR_HIP(hipSetDevice(c->device));
+        EgrDeviceScope scope(c->device); // the caller's device is back on every way out, a throwing f() included
         f();
-        if (prev != c->device) EGR_HIP(hipSetDevice(prev));
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) throw EgrCheck{e, "kernel launch"};
         return 0;
@@ -527,9 +524,10 @@ __global__ void k_debug_lean_arith(const float *__restrict__ a, const float *__r
 }
 int egr_debug_lean_arith(int device, const float *a, const float *b, float *quot, float *root, uint32_t n, void *stream) {
     if (!a || !b || !quot || !root) return 1;
-    if (hipSetDevice(device) != hipSuccess) return 1;
-    if (n) hipLaunchKernelGGL(k_debug_lean_arith, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, a, b, quot, root, n);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    std::string unused; // (a test hook: it reports through its return value alone)
+    return egr_on_device(device, unused, "egr_debug_lean_arith", [&] {
+        if (n) egr_launch(k_debug_lean_arith, dim3((n + 255u) / 256u), dim3(256), (hipStream_t)stream, a, b, quot, root, n);
+    });
 }
 
 int egr_debug_check_bvh(egr_context *c, void *stream) {

@@ -16,6 +16,7 @@
 #include <string>
 
 #include "../../include/egr_raytracer.h"
+#include "egr_host.hpp"
 
 namespace {
 
@@ -189,16 +190,6 @@ __global__ void __launch_bounds__(EDIT_THREADS) k_edit_apply(ApplyArgs a) {
 
 thread_local std::string g_edit_error;
 
-int fail(const char *fn, const std::string &what) {
-    g_edit_error = std::string("libegr_hip: ") + fn + ": " + what;
-    return 1;
-}
-
-bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
 constexpr int EDIT_ARRAYS = 8;
 constexpr uint32_t EDIT_WIDTH[EDIT_ARRAYS] = {3, 4, 3, 1, 3, 3, 1, 3}; // egr_edit_arrays, in field order
 
@@ -208,64 +199,53 @@ extern "C" const char *egr_edit_last_error(void) { return g_edit_error.c_str(); 
 
 extern "C" int egr_edit_select(int device, uint32_t n, const float *xyz, const float *f0, const float *roughness, const float *diffuse,
                                const egr_edit_object *objects, uint32_t num_objects, uint32_t *mask, void *hip_stream) {
+    const char *fn = "egr_edit_select";
     // ---- validation: before any HIP call
-    if (!mask) return fail("egr_edit_select", "mask is a required output");
-    if (num_objects > EGR_MAX_EDIT_OBJECTS) return fail("egr_edit_select", "more than EGR_MAX_EDIT_OBJECTS (32) objects");
-    if (num_objects != 0 && !objects) return fail("egr_edit_select", "num_objects > 0 needs objects");
-    if (n > EDIT_MAX_ROWS) return fail("egr_edit_select", "n exceeds 2^26 rows (the limit of the tree)");
-    if (n != 0 && !xyz) return fail("egr_edit_select", "xyz is required");
+    if (!mask) return egr_fail(g_edit_error, fn, "mask is a required output");
+    if (num_objects > EGR_MAX_EDIT_OBJECTS) return egr_fail(g_edit_error, fn, "more than EGR_MAX_EDIT_OBJECTS (32) objects");
+    if (num_objects != 0 && !objects) return egr_fail(g_edit_error, fn, "num_objects > 0 needs objects");
+    if (n > EDIT_MAX_ROWS) return egr_fail(g_edit_error, fn, "n exceeds 2^26 rows (the limit of the tree)");
+    if (n != 0 && !xyz) return egr_fail(g_edit_error, fn, "xyz is required");
     SelectArgs a{};
     for (uint32_t k = 0; k < num_objects; k++) {
         const uint32_t f = objects[k].flags;
         if (((f & EGR_EDIT_SEL_RANGE_F0) && !f0) || ((f & EGR_EDIT_SEL_RANGE_ROUGHNESS) && !roughness) || ((f & EGR_EDIT_SEL_RANGE_DIFFUSE) && !diffuse))
-            return fail("egr_edit_select", "an object has a property range whose array is NULL");
-        if (num_objects < 32u && (objects[k].exclude >> num_objects)) return fail("egr_edit_select", "an object excludes an object that does not exist");
+            return egr_fail(g_edit_error, fn, "an object has a property range whose array is NULL");
+        if (num_objects < 32u && (objects[k].exclude >> num_objects)) return egr_fail(g_edit_error, fn, "an object excludes an object that does not exist");
         a.obj[k] = objects[k];
     }
     if (n == 0) return 0;
-    const size_t mbytes = (size_t)n * 4;
-    if (overlap(mask, mbytes, xyz, (size_t)n * 12) || (f0 && overlap(mask, mbytes, f0, (size_t)n * 12)) || (roughness && overlap(mask, mbytes, roughness, (size_t)n * 4)) ||
-        (diffuse && overlap(mask, mbytes, diffuse, (size_t)n * 12)))
-        return fail("egr_edit_select", "mask overlaps an input");
+    const EgrRange out = {mask, (uint64_t)n * 4}, in[4] = {{xyz, (uint64_t)n * 12}, {f0, (uint64_t)n * 12}, {roughness, (uint64_t)n * 4}, {diffuse, (uint64_t)n * 12}};
+    if (egr_find_clash(&out, 1, in, 4)) return egr_fail(g_edit_error, fn, "mask overlaps an input");
     a.xyz = xyz, a.f0 = f0, a.roughness = roughness, a.diffuse = diffuse, a.mask = mask, a.n = n, a.num_objects = num_objects;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_edit_select, dim3((n + EDIT_THREADS - 1) / EDIT_THREADS), dim3(EDIT_THREADS), 0, (hipStream_t)hip_stream, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail("egr_edit_select", hipGetErrorString(e));
-    return 0;
+    return egr_on_device(device, g_edit_error, fn, [&] { egr_launch(k_edit_select, dim3((n + EDIT_THREADS - 1) / EDIT_THREADS), dim3(EDIT_THREADS), (hipStream_t)hip_stream, a); });
 }
 
 extern "C" int egr_edit_apply(int device, uint32_t n, const egr_edit_arrays *src, const egr_edit_arrays *dst, const uint32_t *mask,
                               const egr_edit_record *records, uint32_t num_records, void *hip_stream) {
+    const char *fn = "egr_edit_apply";
     // ---- validation: before any HIP call
-    if (!src || !dst) return fail("egr_edit_apply", "src and dst are required");
-    if (num_records > EGR_MAX_EDIT_OBJECTS) return fail("egr_edit_apply", "more than EGR_MAX_EDIT_OBJECTS (32) records");
-    if (n > EDIT_MAX_ROWS) return fail("egr_edit_apply", "n exceeds 2^26 rows (the limit of the tree)");
-    if (num_records != 0 && (!mask || !records)) return fail("egr_edit_apply", "num_records > 0 needs mask and records");
+    if (!src || !dst) return egr_fail(g_edit_error, fn, "src and dst are required");
+    if (num_records > EGR_MAX_EDIT_OBJECTS) return egr_fail(g_edit_error, fn, "more than EGR_MAX_EDIT_OBJECTS (32) records");
+    if (n > EDIT_MAX_ROWS) return egr_fail(g_edit_error, fn, "n exceeds 2^26 rows (the limit of the tree)");
+    if (num_records != 0 && (!mask || !records)) return egr_fail(g_edit_error, fn, "num_records > 0 needs mask and records");
     float *const *s = &src->scale, *const *d = &dst->scale; // eight float * fields in a row (static_assert above: 64 bytes)
     for (int k = 0; k < EDIT_ARRAYS; k++)
-        if (!s[k] || !d[k]) return fail("egr_edit_apply", "a NULL array in src or dst");
+        if (!s[k] || !d[k]) return egr_fail(g_edit_error, fn, "a NULL array in src or dst");
     if (n == 0) return 0;
+    // in place is allowed here (dst[k] == src[k] exactly), so the pairs are walked by hand: egr_find_clash knows out-of-place launches only
+    const EgrRange m = {num_records ? mask : nullptr, (uint64_t)n * 4}, r = {records, (uint64_t)num_records * sizeof(egr_edit_record)};
     for (int k = 0; k < EDIT_ARRAYS; k++) {
-        const size_t dbytes = (size_t)n * EDIT_WIDTH[k] * 4;
+        const EgrRange dk = {d[k], (uint64_t)n * EDIT_WIDTH[k] * 4};
         for (int j = 0; j < EDIT_ARRAYS; j++) {
-            const size_t jbytes = (size_t)n * EDIT_WIDTH[j] * 4;
-            if (!(j == k && s[j] == d[k]) && overlap(d[k], dbytes, s[j], jbytes))
-                return fail("egr_edit_apply", "partial overlap: a dst array must be its own src array or touch no src array");
-            if (j != k && overlap(d[k], dbytes, d[j], jbytes)) return fail("egr_edit_apply", "partial overlap: two dst arrays overlap");
+            const uint64_t jbytes = (uint64_t)n * EDIT_WIDTH[j] * 4;
+            if (!(j == k && s[j] == d[k]) && egr_overlap(dk, EgrRange{s[j], jbytes}))
+                return egr_fail(g_edit_error, fn, "partial overlap: a dst array must be its own src array or touch no src array");
+            if (j != k && egr_overlap(dk, EgrRange{d[j], jbytes})) return egr_fail(g_edit_error, fn, "partial overlap: two dst arrays overlap");
         }
-        if (num_records != 0 && (overlap(d[k], dbytes, mask, (size_t)n * 4) || overlap(d[k], dbytes, records, (size_t)num_records * sizeof(egr_edit_record))))
-            return fail("egr_edit_apply", "partial overlap: a dst array overlaps the mask or the records");
+        if (egr_overlap(dk, m) || egr_overlap(dk, r)) return egr_fail(g_edit_error, fn, "partial overlap: a dst array overlaps the mask or the records");
     }
     ApplyArgs a{};
     a.src = *src, a.dst = *dst, a.mask = mask, a.records = records, a.n = n, a.num_records = num_records;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_edit_apply, dim3((n + EDIT_THREADS - 1) / EDIT_THREADS), dim3(EDIT_THREADS), 0, (hipStream_t)hip_stream, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail("egr_edit_apply", hipGetErrorString(e));
-    return 0;
+    return egr_on_device(device, g_edit_error, fn, [&] { egr_launch(k_edit_apply, dim3((n + EDIT_THREADS - 1) / EDIT_THREADS), dim3(EDIT_THREADS), (hipStream_t)hip_stream, a); });
 }

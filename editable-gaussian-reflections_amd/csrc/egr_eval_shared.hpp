@@ -7,6 +7,8 @@
 #include <cmath>
 #include <string>
 
+#include "egr_host.hpp"
+
 // D(x) = clamp(tonemap(x), 0, 1), operation by operation as torch evaluates it in fp32 (every product and sum rounded on its own: no fused multiply-add).
 // NaN propagates: a negative quotient gives NaN from the power, +-huge inputs give inf / inf, and the clamp is written with comparisons, which keep a NaN
 // (fminf / fmaxf would drop it).
@@ -29,5 +31,5 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v; // lane 0 holds the sum (a fixed tree: the same order on every run)
 }
 
-// Sets the calling thread's egr_eval_last_error() to "libegr_hip: <function>: <what>" and returns 1 (csrc/eval.hip).
-int egr_eval_fail(const char *function, const std::string &what);
+// What egr_eval_last_error() returns: the one string eval.hip (which defines it), ssim.hip and frames.hip hand to egr_fail / egr_on_device.
+extern thread_local std::string g_eval_error;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/egr_raytracer.h"
+#include "egr_host.hpp" // EgrCheck / EGR_HIP, EgrDeviceScope
 
 #define EGR_NSTEPS EGR_NUM_STEPS
 #define EGR_WAVE 64
@@ -26,15 +27,6 @@
 #define EGR_EXT_NONE 0xFFFFFFFFu
 #define EGR_HIT_BLOCK_ROWS 8  // composited-hit arena block: 8 rows x 64 lanes x 16 B (+1 header row)
 #define EGR_MAX_DEPTH_BINS 256
-
-struct EgrCheck {
-    hipError_t e;
-    const char *what;
-};
-inline void egr_hip_check(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw EgrCheck{e, what};
-}
-#define EGR_HIP(expr) egr_hip_check((expr), #expr)
 
 // ---- per-Gaussian records (internal layout in HBM) -----------------------------------------------------
 // inst_w : float4[4N]   64-B test record: rows of W = M^-1 (world->object; snapshot at update/rebuild) + live

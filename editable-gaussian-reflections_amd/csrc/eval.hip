@@ -127,27 +127,17 @@ __global__ void __launch_bounds__(EVAL_THREADS) k_eval_finish(EvalArgs a) {
     }
 }
 
-thread_local std::string g_eval_error;
-
-int fail(const std::string &what) { return egr_eval_fail("egr_eval_metrics", what); }
-
-bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
 } // namespace
 
-int egr_eval_fail(const char *function, const std::string &what) {
-    g_eval_error = std::string("libegr_hip: ") + function + ": " + what;
-    return 1;
-}
+thread_local std::string g_eval_error; // (egr_eval_shared.hpp: shared with ssim.hip and frames.hip)
 
 extern "C" const char *egr_eval_last_error(void) { return g_eval_error.c_str(); }
 
 extern "C" int egr_eval_metrics(int device, uint32_t num_views, uint32_t height, uint32_t width, const float *final, const float *rgb, const float *target_final,
                                 const float *target_diffuse, const float *target_specular, double *sse, double *psnr, float *display, void *workspace,
                                 void *hip_stream) {
+    const char *fn = "egr_eval_metrics";
+    auto fail = [&](const std::string &what) { return egr_fail(g_eval_error, fn, what); };
     // ---- validation: before any HIP call
     if (num_views == 0 || num_views > EVAL_MAX_VIEWS) return fail("num_views must be in 1..65535");
     if (height == 0 || width == 0) return fail("height and width must be >= 1");
@@ -159,29 +149,17 @@ extern "C" int egr_eval_metrics(int device, uint32_t num_views, uint32_t height,
     const size_t blocks = EGR_EVAL_BLOCKS(height, width);
     if (blocks > 0x7FFFFFFFull) return fail("the image is too large");
     const size_t image = (size_t)num_views * hw * 3 * sizeof(float);
-    const struct { const void *p; size_t bytes; } in[5] = {{final, image}, {rgb, 3 * image}, {target_final, image}, {target_diffuse, image}, {target_specular, image}};
-    const struct { const void *p; size_t bytes; } out[4] = {{sse, (size_t)num_views * 9 * 8}, {psnr, (size_t)num_views * 6 * 8}, {display, 6 * image},
-                                                            {workspace, EGR_EVAL_WORKSPACE_BYTES(num_views, height, width)}};
-    for (int o = 0; o < 4; o++) {
-        for (int i = 0; i < 5; i++)
-            if (overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes)) return fail("an output (sse, psnr, display, workspace) overlaps an input");
-        for (int q = o + 1; q < 4; q++)
-            if (overlap(out[o].p, out[o].bytes, out[q].p, out[q].bytes)) return fail("two outputs (sse, psnr, display, workspace) overlap");
-    }
+    const EgrRange in[5] = {{final, image}, {rgb, 3 * image}, {target_final, image}, {target_diffuse, image}, {target_specular, image}};
+    const EgrRange out[4] = {{sse, (uint64_t)num_views * 9 * 8}, {psnr, (uint64_t)num_views * 6 * 8}, {display, 6 * image}, {workspace, EGR_EVAL_WORKSPACE_BYTES(num_views, height, width)}};
+    if (const EgrClash clash = egr_find_clash(out, 4, in, 5))
+        return fail(clash.kind == EGR_CLASH_INPUT ? "an output (sse, psnr, display, workspace) overlaps an input" : "two outputs (sse, psnr, display, workspace) overlap");
     EvalArgs a{};
     a.final = final, a.rgb = rgb, a.target[0] = target_final, a.target[1] = target_diffuse, a.target[2] = target_specular;
     a.partial = (double *)workspace, a.sse = sse, a.psnr = psnr, a.display = display;
     a.hw = hw, a.blocks = (uint32_t)blocks;
     hipStream_t s = (hipStream_t)hip_stream;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_eval_partial, dim3(a.blocks, num_views), dim3(EVAL_THREADS), 0, s, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_eval_finish, dim3(num_views), dim3(EVAL_THREADS), 0, s, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail(hipGetErrorString(e));
-    return 0;
+    return egr_on_device(device, g_eval_error, fn, [&] {
+        egr_launch(k_eval_partial, dim3(a.blocks, num_views), dim3(EVAL_THREADS), s, a);
+        egr_launch(k_eval_finish, dim3(num_views), dim3(EVAL_THREADS), s, a);
+    });
 }

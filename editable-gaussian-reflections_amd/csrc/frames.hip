@@ -351,24 +351,13 @@ __global__ void __launch_bounds__(FR_THREADS) k_frames_finish(FramesArgs a) {
     }
 }
 
-int fail(const std::string &what) { return egr_eval_fail("egr_eval_frames", what); }
-
-struct Range {
-    const void *p;
-    size_t bytes;
-    const char *name;
-};
-
-bool overlap(const Range &a, const Range &b) {
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a.p && b.p && a.bytes != 0 && b.bytes != 0 && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
 const char *const KIND_NAMES[EGR_FRAMES_KINDS] = {"render", "diffuse", "specular", "depth", "normal", "roughness", "f0"};
 
 } // namespace
 
 extern "C" int egr_eval_frames(int device, const egr_frames_args *args, void *hip_stream) {
+    const char *fn = "egr_eval_frames";
+    auto fail = [&](const std::string &what) { return egr_fail(g_eval_error, fn, what); };
     // ---- validation: before any HIP call
     if (!args) return fail("args is required");
     const egr_frames_args &g = *args;
@@ -387,20 +376,19 @@ extern "C" int egr_eval_frames(int device, const egr_frames_args *args, void *hi
     const size_t blocks = EGR_FRAMES_BLOCKS(g.height, g.width);
     if (blocks > 0x7FFFFFFFull) return fail("the image is too large");
     const size_t V = g.num_views, plane = (size_t)hw * sizeof(float);
-    const Range in[13] = {{g.final, V * 3 * plane, "final"}, {g.rgb, V * 9 * plane, "rgb"}, {g.depth, V * 3 * plane, "depth"}, {g.normal, V * 9 * plane, "normal"},
-                          {g.roughness, V * 3 * plane, "roughness"}, {g.f0, V * 9 * plane, "f0"}, {g.targets[0], V * 3 * plane, "target render"},
-                          {g.targets[1], V * 3 * plane, "target diffuse"}, {g.targets[2], V * 3 * plane, "target specular"}, {g.targets[3], V * plane, "target depth"},
-                          {g.targets[4], V * 3 * plane, "target normal"}, {g.targets[5], V * plane, "target roughness"}, {g.targets[6], V * 3 * plane, "target f0"}};
-    const Range out[5] = {{g.frames, V * EGR_FRAMES_KINDS * 2 * (size_t)hw * 3, "frames"}, {g.sse8, V * FR_SUMS * 8, "sse8"}, {g.psnr8, V * EGR_FRAMES_KINDS * 2 * 8, "psnr8"},
-                          {g.depth_range, V * 2 * 4, "depth_range"}, {g.workspace, EGR_FRAMES_WORKSPACE_BYTES(g.num_views, g.height, g.width), "workspace"}};
+    const char *const in_name[13] = {"final", "rgb", "depth", "normal", "roughness", "f0", "target render", "target diffuse", "target specular", "target depth", "target normal",
+                                     "target roughness", "target f0"};
+    const EgrRange in[13] = {{g.final, V * 3 * plane}, {g.rgb, V * 9 * plane}, {g.depth, V * 3 * plane}, {g.normal, V * 9 * plane}, {g.roughness, V * 3 * plane},
+                             {g.f0, V * 9 * plane}, {g.targets[0], V * 3 * plane}, {g.targets[1], V * 3 * plane}, {g.targets[2], V * 3 * plane}, {g.targets[3], V * plane},
+                             {g.targets[4], V * 3 * plane}, {g.targets[5], V * plane}, {g.targets[6], V * 3 * plane}};
+    const char *const out_name[5] = {"frames", "sse8", "psnr8", "depth_range", "workspace"};
+    const EgrRange out[5] = {{g.frames, V * EGR_FRAMES_KINDS * 2 * (size_t)hw * 3}, {g.sse8, V * FR_SUMS * 8}, {g.psnr8, V * EGR_FRAMES_KINDS * 2 * 8}, {g.depth_range, V * 2 * 4},
+                             {g.workspace, EGR_FRAMES_WORKSPACE_BYTES(g.num_views, g.height, g.width)}};
     for (int i = 0; i < 13; i++)
-        if ((uintptr_t)in[i].p & 3u) return fail(std::string(in[i].name) + " is not 4-byte aligned");
-    for (int o = 0; o < 5; o++) {
-        for (int i = 0; i < 13; i++)
-            if (overlap(out[o], in[i])) return fail(std::string("an output (") + out[o].name + ") overlaps an input (" + in[i].name + ")");
-        for (int q = o + 1; q < 5; q++)
-            if (overlap(out[o], out[q])) return fail(std::string("two outputs (") + out[o].name + ", " + out[q].name + ") overlap");
-    }
+        if ((uintptr_t)in[i].p & 3u) return fail(std::string(in_name[i]) + " is not 4-byte aligned");
+    if (const EgrClash clash = egr_find_clash(out, 5, in, 13))
+        return fail(clash.kind == EGR_CLASH_INPUT ? std::string("an output (") + out_name[clash.out] + ") overlaps an input (" + in_name[clash.other] + ")"
+                                                  : std::string("two outputs (") + out_name[clash.out] + ", " + out_name[clash.other] + ") overlap");
     FramesArgs a{};
     const float *pred[EGR_FRAMES_KINDS] = {g.final, g.rgb, g.rgb ? g.rgb + (size_t)hw * 3 : nullptr, g.depth, g.normal, g.roughness, g.f0};
     const uint64_t steps = EGR_NUM_STEPS;
@@ -416,19 +404,9 @@ extern "C" int egr_eval_frames(int device, const egr_frames_args *args, void *hi
     a.range_blocks = (uint32_t)(range_blocks < EGR_FRAMES_RANGE_BLOCKS ? range_blocks : EGR_FRAMES_RANGE_BLOCKS);
     a.rounding = g.rounding, a.depth_mode = g.depth_mode, a.layout = g.layout;
     hipStream_t s = (hipStream_t)hip_stream;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess && (a.kinds & (1u << FR_DEPTH))) {
-        hipLaunchKernelGGL(k_frames_range, dim3(a.range_blocks, g.num_views), dim3(FR_THREADS), 0, s, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && a.kinds) { // (depth alone without its target: nothing to write, -1 and NaN to report)
-        hipLaunchKernelGGL(k_frames_write, dim3(a.blocks, g.num_views), dim3(FR_THREADS), 0, s, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_frames_finish, dim3(g.num_views), dim3(FR_THREADS), 0, s, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail(hipGetErrorString(e));
-    return 0;
+    return egr_on_device(device, g_eval_error, fn, [&] {
+        if (a.kinds & (1u << FR_DEPTH)) egr_launch(k_frames_range, dim3(a.range_blocks, g.num_views), dim3(FR_THREADS), s, a);
+        if (a.kinds) egr_launch(k_frames_write, dim3(a.blocks, g.num_views), dim3(FR_THREADS), s, a); // (depth alone without its target: nothing to write, -1 and NaN to report)
+        egr_launch(k_frames_finish, dim3(g.num_views), dim3(FR_THREADS), s, a);
+    });
 }

@@ -17,6 +17,7 @@
 #include <string>
 
 #include "../../include/egr_raytracer.h"
+#include "egr_host.hpp"
 
 namespace {
 
@@ -76,73 +77,55 @@ __global__ void __launch_bounds__(GROW_THREADS) k_grow_append(AppendArgs a) {
 
 thread_local std::string g_grow_error;
 
-int fail(const char *fn, const std::string &what) {
-    g_grow_error = std::string("libegr_hip: ") + fn + ": " + what;
-    return 1;
-}
-
-// (an empty range touches nothing)
-bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return abytes != 0 && bbytes != 0 && a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
 } // namespace
 
 extern "C" const char *egr_grow_last_error(void) { return g_grow_error.c_str(); }
 
 extern "C" int egr_grow_sample(int device, uint64_t first, uint32_t n, uint64_t seed, float radius, float clamp, float *out_points, void *hip_stream) {
+    const char *fn = "egr_grow_sample";
     // ---- validation: before any HIP call
-    if (!out_points) return fail("egr_grow_sample", "out_points is a required output");
-    if (n > GROW_MAX_ROWS) return fail("egr_grow_sample", "n exceeds 2^26 rows (the limit of the tree)");
-    if (first > UINT64_MAX - n) return fail("egr_grow_sample", "first + n overflows 64 bits");
-    if (!std::isfinite(radius) || radius < 0.0f) return fail("egr_grow_sample", "radius must be finite and not negative");
-    if (!std::isfinite(clamp) || clamp < 0.0f) return fail("egr_grow_sample", "clamp must be finite and not negative");
+    if (!out_points) return egr_fail(g_grow_error, fn, "out_points is a required output");
+    if (n > GROW_MAX_ROWS) return egr_fail(g_grow_error, fn, "n exceeds 2^26 rows (the limit of the tree)");
+    if (first > UINT64_MAX - n) return egr_fail(g_grow_error, fn, "first + n overflows 64 bits");
+    if (!std::isfinite(radius) || radius < 0.0f) return egr_fail(g_grow_error, fn, "radius must be finite and not negative");
+    if (!std::isfinite(clamp) || clamp < 0.0f) return egr_fail(g_grow_error, fn, "clamp must be finite and not negative");
     if (n == 0) return 0;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_grow_sample, dim3((n + GROW_THREADS - 1) / GROW_THREADS), dim3(GROW_THREADS), 0, (hipStream_t)hip_stream, first, n, seed, radius, clamp, out_points);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail("egr_grow_sample", hipGetErrorString(e));
-    return 0;
+    return egr_on_device(device, g_grow_error, fn, [&] {
+        egr_launch(k_grow_sample, dim3((n + GROW_THREADS - 1) / GROW_THREADS), dim3(GROW_THREADS), (hipStream_t)hip_stream, first, n, seed, radius, clamp, out_points);
+    });
 }
 
 extern "C" int egr_grow_append(int device, const egr_grow_array *arrays, int num_arrays, uint32_t n, uint32_t m, void *hip_stream) {
+    const char *fn = "egr_grow_append";
     // ---- validation: before any HIP call
-    if (!arrays || num_arrays < 1 || num_arrays > EGR_MAX_PRUNE_ARRAYS) return fail("egr_grow_append", "1..EGR_MAX_PRUNE_ARRAYS table entries are required");
-    if ((uint64_t)n + m > GROW_MAX_ROWS) return fail("egr_grow_append", "n + m exceeds 2^26 rows (the limit of the tree)");
+    if (!arrays || num_arrays < 1 || num_arrays > EGR_MAX_PRUNE_ARRAYS) return egr_fail(g_grow_error, fn, "1..EGR_MAX_PRUNE_ARRAYS table entries are required");
+    if ((uint64_t)n + m > GROW_MAX_ROWS) return egr_fail(g_grow_error, fn, "n + m exceeds 2^26 rows (the limit of the tree)");
     AppendArgs a{};
     uint32_t wmax = 1;
     for (int k = 0; k < num_arrays; k++) {
         const egr_grow_array &T = arrays[k];
-        if (!T.dst || T.width == 0) return fail("egr_grow_append", "table entry without dst, or with width 0");
-        if (T.tail_kind != EGR_GROW_TAIL_ROWS && T.tail_kind != EGR_GROW_TAIL_FILL) return fail("egr_grow_append", "unknown tail_kind (EGR_GROW_TAIL_ROWS or EGR_GROW_TAIL_FILL)");
-        if (!T.src && n > 0) return fail("egr_grow_append", "table entry without src although n > 0");
-        if (T.tail_kind == EGR_GROW_TAIL_ROWS && !T.tail && m > 0) return fail("egr_grow_append", "EGR_GROW_TAIL_ROWS entry without tail although m > 0");
+        if (!T.dst || T.width == 0) return egr_fail(g_grow_error, fn, "table entry without dst, or with width 0");
+        if (T.tail_kind != EGR_GROW_TAIL_ROWS && T.tail_kind != EGR_GROW_TAIL_FILL) return egr_fail(g_grow_error, fn, "unknown tail_kind (EGR_GROW_TAIL_ROWS or EGR_GROW_TAIL_FILL)");
+        if (!T.src && n > 0) return egr_fail(g_grow_error, fn, "table entry without src although n > 0");
+        if (T.tail_kind == EGR_GROW_TAIL_ROWS && !T.tail && m > 0) return egr_fail(g_grow_error, fn, "EGR_GROW_TAIL_ROWS entry without tail although m > 0");
         a.t[k] = T;
         wmax = std::max(wmax, T.width);
     }
     // out of place only: no dst may touch anything the launch reads, or another dst
+    EgrRange dst[EGR_MAX_PRUNE_ARRAYS], in[2 * EGR_MAX_PRUNE_ARRAYS]; // in: every src, then every tail (a fill has none)
     for (int k = 0; k < num_arrays; k++) {
-        const size_t dbytes = ((size_t)n + m) * arrays[k].width * 4;
-        for (int j = 0; j < num_arrays; j++) {
-            if (overlap(arrays[k].dst, dbytes, arrays[j].src, (size_t)n * arrays[j].width * 4))
-                return fail("egr_grow_append", "dst overlaps a src (src == dst or overlapping ranges): the append runs out of place");
-            if (arrays[j].tail_kind == EGR_GROW_TAIL_ROWS && overlap(arrays[k].dst, dbytes, arrays[j].tail, (size_t)m * arrays[j].width * 4))
-                return fail("egr_grow_append", "dst overlaps a tail: the append runs out of place");
-            if (j != k && overlap(arrays[k].dst, dbytes, arrays[j].dst, ((size_t)n + m) * arrays[j].width * 4)) return fail("egr_grow_append", "two dst ranges overlap");
-        }
+        const egr_grow_array &T = arrays[k];
+        dst[k] = EgrRange{T.dst, ((uint64_t)n + m) * T.width * 4};
+        in[k] = EgrRange{T.src, (uint64_t)n * T.width * 4};
+        in[num_arrays + k] = EgrRange{T.tail_kind == EGR_GROW_TAIL_ROWS ? T.tail : nullptr, (uint64_t)m * T.width * 4};
     }
+    if (const EgrClash clash = egr_find_clash(dst, num_arrays, in, 2 * num_arrays))
+        return egr_fail(g_grow_error, fn, clash.kind == EGR_CLASH_OUTPUT ? "two dst ranges overlap"
+                                          : clash.other < num_arrays     ? "dst overlaps a src (src == dst or overlapping ranges): the append runs out of place"
+                                                                         : "dst overlaps a tail: the append runs out of place");
     if ((uint64_t)n + m == 0) return 0;
     a.n = n, a.m = m;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        const size_t total = ((size_t)n + m) * wmax; // words of the widest entry: one thread per 16 bytes of it, the loops stride over the rest
-        const uint32_t bx = (uint32_t)std::min<size_t>((total / 4 + GROW_THREADS) / GROW_THREADS, 65535u * 16u);
-        hipLaunchKernelGGL(k_grow_append, dim3(bx, (uint32_t)num_arrays), dim3(GROW_THREADS), 0, (hipStream_t)hip_stream, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail("egr_grow_append", hipGetErrorString(e));
-    return 0;
+    const size_t total = ((size_t)n + m) * wmax; // words of the widest entry: one thread per 16 bytes of it, the loops stride over the rest
+    const uint32_t bx = (uint32_t)std::min<size_t>((total / 4 + GROW_THREADS) / GROW_THREADS, 65535u * 16u);
+    return egr_on_device(device, g_grow_error, fn, [&] { egr_launch(k_grow_append, dim3(bx, (uint32_t)num_arrays), dim3(GROW_THREADS), (hipStream_t)hip_stream, a); });
 }

@@ -28,6 +28,7 @@
 #include <string>
 
 #include "../../include/egr_raytracer.h"
+#include "egr_host.hpp"
 
 namespace {
 
@@ -262,31 +263,6 @@ __global__ void __launch_bounds__(VOXEL_THREADS) k_voxel_write(ExtractArgs a) {
 
 thread_local std::string g_voxel_error;
 
-int fail(const char *fn, const std::string &what) {
-    g_voxel_error = std::string("libegr_hip: ") + fn + ": " + what;
-    return 1;
-}
-
-struct Range {
-    const void *p;
-    uint64_t bytes;
-};
-
-bool overlap(const Range &a, const Range &b) {
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a.p && b.p && a.bytes && b.bytes && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
-bool any_overlap(const Range *out, int num_out, const Range *in, int num_in) { // an output with an input, or two outputs
-    for (int o = 0; o < num_out; o++) {
-        for (int i = 0; i < num_in; i++)
-            if (overlap(out[o], in[i])) return true;
-        for (int q = o + 1; q < num_out; q++)
-            if (overlap(out[o], out[q])) return true;
-    }
-    return false;
-}
-
 bool bad_cap(uint64_t cap) { return cap < EGR_VOXEL_MIN_CAPACITY || cap > EGR_VOXEL_MAX_CAPACITY || (cap & (cap - 1)) != 0; }
 bool misaligned(const void *p) { return ((uintptr_t)p & 7u) != 0; }
 const char *CAP_TEXT = "the capacity must be a power of two in EGR_VOXEL_MIN_CAPACITY..EGR_VOXEL_MAX_CAPACITY";
@@ -303,72 +279,57 @@ extern "C" int egr_voxel_accumulate(int device, int64_t *keys, int64_t *acc, int
                                     void *hip_stream) {
     const char *fn = "egr_voxel_accumulate";
     // ---- validation: before any HIP call
-    if (!keys || !acc || !status) return fail(fn, "keys, acc and status are required");
+    if (!keys || !acc || !status) return egr_fail(g_voxel_error, fn, "keys, acc and status are required");
     if (misaligned(keys) || misaligned(acc) || misaligned(status) || misaligned(c2w) || misaligned(origin) || misaligned(view_size) || misaligned(positions_out))
-        return fail(fn, "the table and the fp64 arrays must be 8-byte aligned");
-    if (bad_cap(cap)) return fail(fn, CAP_TEXT);
-    if (num_views == 0 || num_views > 65535u) return fail(fn, "num_views must be in 1..65535");
-    if (height == 0 || width == 0 || height > (1u << 20) || width > (1u << 20)) return fail(fn, "height and width must be in 1..2^20");
-    if (!c2w || !origin || !view_size || !depth) return fail(fn, "c2w, origin, view_size and depth are required");
-    if ((colour != nullptr) == (colour_u8 != nullptr)) return fail(fn, "exactly one of colour (fp32) and colour_u8 is required");
-    if (colour_u8 && !colour_table) return fail(fn, "colour_u8 needs the 256-entry colour_table");
-    if (!(voxel_scale > 0.0) || !std::isfinite(voxel_scale)) return fail(fn, "voxel_scale must be positive and finite");
-    if (!(colour_max > 0.0) || !(colour_max <= 1073741824.0)) return fail(fn, "colour_max must be in (0, 2^30]");
+        return egr_fail(g_voxel_error, fn, "the table and the fp64 arrays must be 8-byte aligned");
+    if (bad_cap(cap)) return egr_fail(g_voxel_error, fn, CAP_TEXT);
+    if (num_views == 0 || num_views > 65535u) return egr_fail(g_voxel_error, fn, "num_views must be in 1..65535");
+    if (height == 0 || width == 0 || height > (1u << 20) || width > (1u << 20)) return egr_fail(g_voxel_error, fn, "height and width must be in 1..2^20");
+    if (!c2w || !origin || !view_size || !depth) return egr_fail(g_voxel_error, fn, "c2w, origin, view_size and depth are required");
+    if ((colour != nullptr) == (colour_u8 != nullptr)) return egr_fail(g_voxel_error, fn, "exactly one of colour (fp32) and colour_u8 is required");
+    if (colour_u8 && !colour_table) return egr_fail(g_voxel_error, fn, "colour_u8 needs the 256-entry colour_table");
+    if (!(voxel_scale > 0.0) || !std::isfinite(voxel_scale)) return egr_fail(g_voxel_error, fn, "voxel_scale must be positive and finite");
+    if (!(colour_max > 0.0) || !(colour_max <= 1073741824.0)) return egr_fail(g_voxel_error, fn, "colour_max must be in (0, 2^30]");
     const uint64_t pixels = (uint64_t)num_views * height * width;
-    if (pixels >= (1ull << 40)) return fail(fn, "more than 2^40 pixels in one call");
-    const Range out[4] = {{keys, cap * 8}, {acc, cap * 32}, {status, EGR_VOXEL_STATUS_WORDS * 8}, {positions_out, pixels * 24}};
-    const Range in[7] = {{c2w, (uint64_t)num_views * 72}, {origin, (uint64_t)num_views * 24}, {view_size, (uint64_t)num_views * 8}, {depth, pixels * 4},
+    if (pixels >= (1ull << 40)) return egr_fail(g_voxel_error, fn, "more than 2^40 pixels in one call");
+    const EgrRange out[4] = {{keys, cap * 8}, {acc, cap * 32}, {status, EGR_VOXEL_STATUS_WORDS * 8}, {positions_out, pixels * 24}};
+    const EgrRange in[7] = {{c2w, (uint64_t)num_views * 72}, {origin, (uint64_t)num_views * 24}, {view_size, (uint64_t)num_views * 8}, {depth, pixels * 4},
                          {colour, pixels * 12}, {colour_u8, pixels * 3}, {colour_table, colour_u8 ? 1024u : 0u}};
-    if (any_overlap(out, 4, in, 7)) return fail(fn, "the table, status or positions_out overlaps an input or another output");
+    if (egr_find_clash(out, 4, in, 7)) return egr_fail(g_voxel_error, fn, "the table, status or positions_out overlaps an input or another output");
     AccArgs a{};
     a.keys = (ull *)keys, a.acc = (ull *)acc, a.status = (ull *)status, a.cap = cap;
     a.c2w = c2w, a.origin = origin, a.view_size = view_size, a.depth = depth, a.colour = colour, a.colour_u8 = colour_u8, a.table = colour_table;
     a.positions_out = positions_out, a.voxel_scale = voxel_scale, a.colour_max = colour_max;
     a.V = num_views, a.H = height, a.W = width;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        const dim3 grid((width + VOXEL_TILE - 1) / VOXEL_TILE, (height + VOXEL_TILE - 1) / VOXEL_TILE, num_views); // <= 65536 x 65536 x 65535
-        hipLaunchKernelGGL(k_voxel_accumulate, grid, dim3(VOXEL_THREADS), 0, (hipStream_t)hip_stream, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail(fn, hipGetErrorString(e));
-    return 0;
+    const dim3 grid((width + VOXEL_TILE - 1) / VOXEL_TILE, (height + VOXEL_TILE - 1) / VOXEL_TILE, num_views); // <= 65536 x 65536 x 65535
+    return egr_on_device(device, g_voxel_error, fn, [&] { egr_launch(k_voxel_accumulate, grid, dim3(VOXEL_THREADS), (hipStream_t)hip_stream, a); });
 }
 
 extern "C" int egr_voxel_rehash(int device, int64_t *keys, int64_t *acc, int64_t *status, uint64_t cap, const int64_t *src_keys, const int64_t *src_acc,
                                 uint64_t src_cap, void *hip_stream) {
     const char *fn = "egr_voxel_rehash";
     // ---- validation: before any HIP call
-    if (!keys || !acc || !status || !src_keys || !src_acc) return fail(fn, "keys, acc, status, src_keys and src_acc are required");
-    if (misaligned(keys) || misaligned(acc) || misaligned(status) || misaligned(src_keys) || misaligned(src_acc)) return fail(fn, "the tables must be 8-byte aligned");
-    if (bad_cap(cap) || bad_cap(src_cap)) return fail(fn, CAP_TEXT);
-    const Range out[3] = {{keys, cap * 8}, {acc, cap * 32}, {status, EGR_VOXEL_STATUS_WORDS * 8}};
-    const Range in[2] = {{src_keys, src_cap * 8}, {src_acc, src_cap * 32}};
-    if (any_overlap(out, 3, in, 2)) return fail(fn, "the new table or status overlaps the old table or another output: a rehash runs out of place");
+    if (!keys || !acc || !status || !src_keys || !src_acc) return egr_fail(g_voxel_error, fn, "keys, acc, status, src_keys and src_acc are required");
+    if (misaligned(keys) || misaligned(acc) || misaligned(status) || misaligned(src_keys) || misaligned(src_acc)) return egr_fail(g_voxel_error, fn, "the tables must be 8-byte aligned");
+    if (bad_cap(cap) || bad_cap(src_cap)) return egr_fail(g_voxel_error, fn, CAP_TEXT);
+    const EgrRange out[3] = {{keys, cap * 8}, {acc, cap * 32}, {status, EGR_VOXEL_STATUS_WORDS * 8}};
+    const EgrRange in[2] = {{src_keys, src_cap * 8}, {src_acc, src_cap * 32}};
+    if (egr_find_clash(out, 3, in, 2)) return egr_fail(g_voxel_error, fn, "the new table or status overlaps the old table or another output: a rehash runs out of place");
     RehashArgs a{(ull *)keys, (ull *)acc, (ull *)status, cap, (const ull *)src_keys, (const ull *)src_acc, src_cap};
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_voxel_rehash, dim3((uint32_t)(src_cap / VOXEL_THREADS)), dim3(VOXEL_THREADS), 0, (hipStream_t)hip_stream, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail(fn, hipGetErrorString(e));
-    return 0;
+    return egr_on_device(device, g_voxel_error, fn, [&] { egr_launch(k_voxel_rehash, dim3((uint32_t)(src_cap / VOXEL_THREADS)), dim3(VOXEL_THREADS), (hipStream_t)hip_stream, a); });
 }
 
 extern "C" size_t egr_voxel_extract_workspace_bytes(int device, uint64_t max_rows) {
     const char *fn = "egr_voxel_extract_workspace_bytes";
     if (max_rows == 0 || max_rows > EGR_VOXEL_MAX_CAPACITY) {
-        fail(fn, "max_rows must be in 1..EGR_VOXEL_MAX_CAPACITY");
-        return 0;
+        egr_fail(g_voxel_error, fn, "max_rows must be in 1..EGR_VOXEL_MAX_CAPACITY");
+        return 0; // (a size, not a status: 0 is the failure)
     }
-    hipError_t e = hipSetDevice(device);
     size_t bytes = 0;
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, bytes, (ull *)nullptr, (ull *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)max_rows, 0, 63, 0);
-    if (e != hipSuccess) {
-        fail(fn, hipGetErrorString(e));
-        return 0;
-    }
-    return (size_t)pair_bytes(max_rows) + ((bytes + 15) & ~(size_t)15) + 16;
+    const int rc = egr_on_device(device, g_voxel_error, fn, [&] {
+        EGR_HIP(rocprim::radix_sort_pairs(nullptr, bytes, (ull *)nullptr, (ull *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)max_rows, 0, 63, 0));
+    });
+    return rc ? 0 : (size_t)pair_bytes(max_rows) + ((bytes + 15) & ~(size_t)15) + 16;
 }
 
 extern "C" int egr_voxel_extract(int device, const int64_t *keys, const int64_t *acc, int64_t *status, uint64_t cap, uint32_t min_count, double voxel_scale,
@@ -376,18 +337,18 @@ extern "C" int egr_voxel_extract(int device, const int64_t *keys, const int64_t 
                                  void *workspace, size_t workspace_bytes, void *hip_stream) {
     const char *fn = "egr_voxel_extract";
     // ---- validation: before any HIP call
-    if (!keys || !acc || !status) return fail(fn, "keys, acc and status are required");
-    if (misaligned(keys) || misaligned(acc) || misaligned(status)) return fail(fn, "the table must be 8-byte aligned");
-    if (bad_cap(cap)) return fail(fn, CAP_TEXT);
-    if (!(voxel_scale > 0.0) || !std::isfinite(voxel_scale)) return fail(fn, "voxel_scale must be positive and finite");
-    if (max_rows == 0 || max_rows > cap) return fail(fn, "max_rows must be in 1..cap");
-    if (!coords || !points || !colors || !counts || !host_rows_and_largest) return fail(fn, "coords, points, colors, counts and host_rows_and_largest are required outputs");
-    if (!workspace || ((uintptr_t)workspace & 15u)) return fail(fn, "a 16-byte aligned workspace of egr_voxel_extract_workspace_bytes(device, max_rows) is required");
-    if (workspace_bytes < pair_bytes(max_rows) + 16) return fail(fn, "the workspace is smaller than egr_voxel_extract_workspace_bytes(device, max_rows)");
-    const Range out[6] = {{status, EGR_VOXEL_STATUS_WORDS * 8}, {coords, max_rows * 12}, {points, max_rows * 12}, {colors, max_rows * 12}, {counts, max_rows * 4},
-                          {workspace, workspace_bytes}};
-    const Range in[2] = {{keys, cap * 8}, {acc, cap * 32}};
-    if (any_overlap(out, 6, in, 2)) return fail(fn, "an output (status, coords, points, colors, counts, workspace) overlaps the table or another output");
+    if (!keys || !acc || !status) return egr_fail(g_voxel_error, fn, "keys, acc and status are required");
+    if (misaligned(keys) || misaligned(acc) || misaligned(status)) return egr_fail(g_voxel_error, fn, "the table must be 8-byte aligned");
+    if (bad_cap(cap)) return egr_fail(g_voxel_error, fn, CAP_TEXT);
+    if (!(voxel_scale > 0.0) || !std::isfinite(voxel_scale)) return egr_fail(g_voxel_error, fn, "voxel_scale must be positive and finite");
+    if (max_rows == 0 || max_rows > cap) return egr_fail(g_voxel_error, fn, "max_rows must be in 1..cap");
+    if (!coords || !points || !colors || !counts || !host_rows_and_largest) return egr_fail(g_voxel_error, fn, "coords, points, colors, counts and host_rows_and_largest are required outputs");
+    if (!workspace || ((uintptr_t)workspace & 15u)) return egr_fail(g_voxel_error, fn, "a 16-byte aligned workspace of egr_voxel_extract_workspace_bytes(device, max_rows) is required");
+    if (workspace_bytes < pair_bytes(max_rows) + 16) return egr_fail(g_voxel_error, fn, "the workspace is smaller than egr_voxel_extract_workspace_bytes(device, max_rows)");
+    const EgrRange out[6] = {{status, EGR_VOXEL_STATUS_WORDS * 8}, {coords, max_rows * 12}, {points, max_rows * 12}, {colors, max_rows * 12}, {counts, max_rows * 4},
+                             {workspace, workspace_bytes}};
+    const EgrRange in[2] = {{keys, cap * 8}, {acc, cap * 32}};
+    if (egr_find_clash(out, 6, in, 2)) return egr_fail(g_voxel_error, fn, "an output (status, coords, points, colors, counts, workspace) overlaps the table or another output");
     ExtractArgs a{};
     a.keys = (const ull *)keys, a.acc = (const ull *)acc, a.status = (ull *)status, a.cap = cap, a.max_rows = max_rows;
     uint8_t *w = (uint8_t *)workspace;
@@ -398,30 +359,23 @@ extern "C" int egr_voxel_extract(int device, const int64_t *keys, const int64_t 
     a.coords = coords, a.points = points, a.colors = colors, a.counts = counts;
     a.min_count = min_count, a.voxel_scale = (float)voxel_scale;
     hipStream_t s = (hipStream_t)hip_stream;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipMemsetAsync(status + 4, 0, 16, s); // the largest count and the number of rows of THIS extraction
-    if (e == hipSuccess) {
+    return egr_on_device(device, g_voxel_error, fn, [&]() -> int {
+        EGR_HIP(hipMemsetAsync(status + 4, 0, 16, s)); // the largest count and the number of rows of THIS extraction
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((cap + VOXEL_COMPACT_CHUNK - 1) / VOXEL_COMPACT_CHUNK, 256u * 8u);
-        hipLaunchKernelGGL(k_voxel_compact, dim3(blocks), dim3(VOXEL_THREADS), 0, s, a);
-        e = hipGetLastError();
-    }
-    uint64_t host[2] = {0, 0}; // largest count, rows
-    if (e == hipSuccess) e = hipMemcpyAsync(host, status + 4, 16, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s); // the one read-back: the number of rows sizes the sort and the last launch
-    if (e != hipSuccess) return fail(fn, hipGetErrorString(e));
-    host_rows_and_largest[0] = host[1], host_rows_and_largest[1] = host[0];
-    if (host[1] > max_rows) return fail(fn, "more rows than max_rows: nothing was written");
-    a.n = host[1];
-    if (a.n == 0) return 0;
-    // only the n selected pairs are sorted; the workspace was sized for max_rows >= n, and a shortfall is refused, never overrun
-    size_t need = 0;
-    e = rocprim::radix_sort_pairs(nullptr, need, a.pair_keys[0], a.pair_keys[1], a.pair_slots[0], a.pair_slots[1], (size_t)a.n, 0, 63, s);
-    if (e == hipSuccess && need > sort_room) return fail(fn, "the workspace is smaller than egr_voxel_extract_workspace_bytes(device, max_rows)");
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(sort_tmp, need, a.pair_keys[0], a.pair_keys[1], a.pair_slots[0], a.pair_slots[1], (size_t)a.n, 0, 63, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_voxel_write, dim3((uint32_t)((a.n + VOXEL_THREADS - 1) / VOXEL_THREADS)), dim3(VOXEL_THREADS), 0, s, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail(fn, hipGetErrorString(e));
-    return 0;
+        egr_launch(k_voxel_compact, dim3(blocks), dim3(VOXEL_THREADS), s, a);
+        uint64_t host[2] = {0, 0}; // largest count, rows
+        EGR_HIP(hipMemcpyAsync(host, status + 4, 16, hipMemcpyDeviceToHost, s));
+        EGR_HIP(hipStreamSynchronize(s)); // the one read-back: the number of rows sizes the sort and the last launch
+        host_rows_and_largest[0] = host[1], host_rows_and_largest[1] = host[0];
+        if (host[1] > max_rows) return egr_fail(g_voxel_error, fn, "more rows than max_rows: nothing was written");
+        a.n = host[1];
+        if (a.n == 0) return 0;
+        // only the n selected pairs are sorted; the workspace was sized for max_rows >= n, and a shortfall is refused, never overrun
+        size_t need = 0;
+        EGR_HIP(rocprim::radix_sort_pairs(nullptr, need, a.pair_keys[0], a.pair_keys[1], a.pair_slots[0], a.pair_slots[1], (size_t)a.n, 0, 63, s));
+        if (need > sort_room) return egr_fail(g_voxel_error, fn, "the workspace is smaller than egr_voxel_extract_workspace_bytes(device, max_rows)");
+        EGR_HIP(rocprim::radix_sort_pairs(sort_tmp, need, a.pair_keys[0], a.pair_keys[1], a.pair_slots[0], a.pair_slots[1], (size_t)a.n, 0, 63, s));
+        egr_launch(k_voxel_write, dim3((uint32_t)((a.n + VOXEL_THREADS - 1) / VOXEL_THREADS)), dim3(VOXEL_THREADS), s, a);
+        return 0;
+    });
 }

@@ -21,21 +21,12 @@
 #include <string>
 
 #include "../../include/egr_raytracer.h"
+#include "egr_host.hpp"
 
 namespace {
 
 constexpr int KNN_BOX = 1024; // points per box (simple-knn's BOX_SIZE)
 constexpr int BS = 256;
-
-struct KnnCheck {
-    hipError_t err;
-    const char *what;
-};
-#define KNN_HIP(call)                                  \
-    do {                                               \
-        hipError_t e_ = (call);                        \
-        if (e_ != hipSuccess) throw KnnCheck{e_, #call}; \
-    } while (0)
 
 __device__ __forceinline__ uint32_t ordered(float f) {
     uint32_t u = __float_as_uint(f);
@@ -165,49 +156,49 @@ __global__ void __launch_bounds__(64) k_knn_search(uint32_t n, uint32_t nboxes, 
 
 thread_local std::string g_knn_error;
 
+struct DeviceTemp { // a hipMalloc that ends with its block
+    void *p = nullptr;
+    ~DeviceTemp() {
+        if (p) (void)hipFree(p);
+    }
+};
+
 } // namespace
 
 extern "C" const char *egr_knn_last_error(void) { return g_knn_error.c_str(); }
 
 extern "C" int egr_knn_mean_dist2(int device, const float *points_xyz, uint32_t n, float *out_mean_dist2, void *hip_stream) {
+    const char *fn = "egr_knn_mean_dist2";
+    // ---- validation: before any HIP call
+    if (n == 0) return 0;
+    if (!points_xyz || !out_mean_dist2) return egr_fail(g_knn_error, fn, "null pointer: invalid argument");
     hipStream_t s = (hipStream_t)hip_stream;
-    void *tmp = nullptr, *sort_tmp = nullptr;
-    int rc = 0;
-    try {
-        KNN_HIP(hipSetDevice(device));
-        if (n == 0) return 0;
-        if (!points_xyz || !out_mean_dist2) throw KnnCheck{hipErrorInvalidValue, "null pointer"};
+    return egr_on_device(device, g_knn_error, fn, [&] {
+        DeviceTemp tmp, sort_tmp; // freed on every way out
         const uint32_t nboxes = (n + KNN_BOX - 1) / KNN_BOX;
         // one allocation: bounds[8] | keys_in | keys_out | vals_in | vals_out | sorted float4 | boxes
         auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         const size_t o_b = 0, o_ki = al(32), o_ko = o_ki + al(8 * (size_t)n), o_vi = o_ko + al(8 * (size_t)n), o_vo = o_vi + al(4 * (size_t)n),
                      o_sp = o_vo + al(4 * (size_t)n), o_bx = o_sp + al(16 * (size_t)n), total = o_bx + al(24 * (size_t)nboxes);
-        KNN_HIP(hipMalloc(&tmp, total));
-        char *base = (char *)tmp;
+        EGR_HIP(hipMalloc(&tmp.p, total));
+        char *base = (char *)tmp.p;
         uint32_t *bounds = (uint32_t *)(base + o_b);
         uint64_t *ki = (uint64_t *)(base + o_ki), *ko = (uint64_t *)(base + o_ko);
         uint32_t *vi = (uint32_t *)(base + o_vi), *vo = (uint32_t *)(base + o_vo);
         float4 *sp = (float4 *)(base + o_sp);
         float *boxes = (float *)(base + o_bx);
         const uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-        KNN_HIP(hipMemcpyAsync(bounds, init, sizeof(init), hipMemcpyHostToDevice, s));
+        EGR_HIP(hipMemcpyAsync(bounds, init, sizeof(init), hipMemcpyHostToDevice, s));
         const uint32_t blocks = (n + BS - 1) / BS;
-        hipLaunchKernelGGL(k_knn_bounds, dim3(std::min(blocks, 2048u)), dim3(BS), 0, s, n, points_xyz, bounds);
-        hipLaunchKernelGGL(k_knn_codes, dim3(blocks), dim3(BS), 0, s, n, points_xyz, bounds, ki, vi);
+        egr_launch(k_knn_bounds, dim3(std::min(blocks, 2048u)), dim3(BS), s, n, points_xyz, bounds);
+        egr_launch(k_knn_codes, dim3(blocks), dim3(BS), s, n, points_xyz, bounds, ki, vi);
         size_t bytes = 0;
-        KNN_HIP(rocprim::radix_sort_pairs(nullptr, bytes, ki, ko, vi, vo, (size_t)n, 0, 63, s));
-        KNN_HIP(hipMalloc(&sort_tmp, std::max<size_t>(bytes, 16)));
-        KNN_HIP(rocprim::radix_sort_pairs(sort_tmp, bytes, ki, ko, vi, vo, (size_t)n, 0, 63, s));
-        hipLaunchKernelGGL(k_knn_gather, dim3(blocks), dim3(BS), 0, s, n, points_xyz, vo, sp);
-        hipLaunchKernelGGL(k_knn_boxes, dim3(nboxes), dim3(BS), 0, s, n, sp, boxes);
-        hipLaunchKernelGGL(k_knn_search, dim3((n + 63) / 64), dim3(64), 0, s, n, nboxes, sp, boxes, out_mean_dist2);
-        KNN_HIP(hipGetLastError());
-        KNN_HIP(hipStreamSynchronize(s)); // temporaries are freed below
-    } catch (const KnnCheck &e) {
-        g_knn_error = std::string("libegr_hip: egr_knn_mean_dist2: ") + e.what + ": " + hipGetErrorString(e.err);
-        rc = 1;
-    }
-    if (sort_tmp) (void)hipFree(sort_tmp);
-    if (tmp) (void)hipFree(tmp);
-    return rc;
+        EGR_HIP(rocprim::radix_sort_pairs(nullptr, bytes, ki, ko, vi, vo, (size_t)n, 0, 63, s));
+        EGR_HIP(hipMalloc(&sort_tmp.p, std::max<size_t>(bytes, 16)));
+        EGR_HIP(rocprim::radix_sort_pairs(sort_tmp.p, bytes, ki, ko, vi, vo, (size_t)n, 0, 63, s));
+        egr_launch(k_knn_gather, dim3(blocks), dim3(BS), s, n, points_xyz, vo, sp);
+        egr_launch(k_knn_boxes, dim3(nboxes), dim3(BS), s, n, sp, boxes);
+        egr_launch(k_knn_search, dim3((n + 63) / 64), dim3(64), s, n, nboxes, sp, boxes, out_mean_dist2);
+        EGR_HIP(hipStreamSynchronize(s)); // the temporaries are freed on the way out
+    });
 }

@@ -20,6 +20,7 @@
 #include <string>
 
 #include "../../include/egr_raytracer.h"
+#include "egr_host.hpp"
 
 namespace {
 
@@ -163,16 +164,6 @@ __global__ void __launch_bounds__(256) k_prune_gather(GatherArgs a) {
 
 thread_local std::string g_prune_error;
 
-int fail(const char *fn, const std::string &what) {
-    g_prune_error = std::string("libegr_hip: ") + fn + ": " + what;
-    return 1;
-}
-
-bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
 } // namespace
 
 extern "C" const char *egr_prune_last_error(void) { return g_prune_error.c_str(); }
@@ -180,12 +171,13 @@ extern "C" const char *egr_prune_last_error(void) { return g_prune_error.c_str()
 extern "C" int egr_prune_select(int device, uint32_t n, const float *total_weight, float divisor, float min_weight, const float *points,
                                 const float *cam_centers, const float *cam_znear, uint32_t num_cams, const uint8_t *remove_mask, uint32_t *src_index,
                                 uint32_t *count, void *workspace, void *hip_stream) {
+    const char *fn = "egr_prune_select";
     // ---- validation: before any HIP call
-    if (!src_index || !count) return fail("egr_prune_select", "src_index and count are required outputs");
-    if (n > PRUNE_MAX_ROWS) return fail("egr_prune_select", "n exceeds 2^26 rows (the limit of the tree)");
-    if (points && num_cams != 0 && (!cam_centers || !cam_znear)) return fail("egr_prune_select", "num_cams > 0 needs cam_centers and cam_znear");
+    if (!src_index || !count) return egr_fail(g_prune_error, fn, "src_index and count are required outputs");
+    if (n > PRUNE_MAX_ROWS) return egr_fail(g_prune_error, fn, "n exceeds 2^26 rows (the limit of the tree)");
+    if (points && num_cams != 0 && (!cam_centers || !cam_znear)) return egr_fail(g_prune_error, fn, "num_cams > 0 needs cam_centers and cam_znear");
     if (n == 0) return 0;
-    if (!workspace || ((uintptr_t)workspace & 7u)) return fail("egr_prune_select", "an 8-byte aligned workspace of EGR_PRUNE_WORKSPACE_BYTES(n) is required");
+    if (!workspace || ((uintptr_t)workspace & 7u)) return egr_fail(g_prune_error, fn, "an 8-byte aligned workspace of EGR_PRUNE_WORKSPACE_BYTES(n) is required");
     SelectArgs a{};
     a.num_wg = (n + EGR_PRUNE_ROWS_PER_WG - 1) / EGR_PRUNE_ROWS_PER_WG;
     a.total_weight = total_weight, a.points = points, a.cam_centers = cam_centers, a.cam_znear = cam_znear, a.remove_mask = remove_mask;
@@ -194,55 +186,39 @@ extern "C" int egr_prune_select(int device, uint32_t n, const float *total_weigh
     a.divisor = divisor, a.min_weight = min_weight;
     a.n = n, a.num_cams = points ? num_cams : 0u;
     hipStream_t s = (hipStream_t)hip_stream;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_prune_flag, dim3(a.num_wg), dim3(PRUNE_THREADS), 0, s, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_prune_scan, dim3(1), dim3(PRUNE_SCAN_THREADS), 0, s, a);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_prune_scatter, dim3(a.num_wg), dim3(PRUNE_THREADS), 0, s, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail("egr_prune_select", hipGetErrorString(e));
-    return 0;
+    return egr_on_device(device, g_prune_error, fn, [&] {
+        egr_launch(k_prune_flag, dim3(a.num_wg), dim3(PRUNE_THREADS), s, a);
+        egr_launch(k_prune_scan, dim3(1), dim3(PRUNE_SCAN_THREADS), s, a);
+        egr_launch(k_prune_scatter, dim3(a.num_wg), dim3(PRUNE_THREADS), s, a);
+    });
 }
 
 extern "C" int egr_prune_gather(int device, const egr_prune_array *arrays, int num_arrays, uint32_t n, const uint32_t *src_index, uint32_t count,
                                 void *hip_stream) {
+    const char *fn = "egr_prune_gather";
     // ---- validation: before any HIP call
-    if (!arrays || num_arrays < 1 || num_arrays > EGR_MAX_PRUNE_ARRAYS) return fail("egr_prune_gather", "1..EGR_MAX_PRUNE_ARRAYS table entries are required");
-    if (!src_index) return fail("egr_prune_gather", "src_index is required");
-    if (n > PRUNE_MAX_ROWS || count > n) return fail("egr_prune_gather", "count <= n <= 2^26 rows is required");
+    if (!arrays || num_arrays < 1 || num_arrays > EGR_MAX_PRUNE_ARRAYS) return egr_fail(g_prune_error, fn, "1..EGR_MAX_PRUNE_ARRAYS table entries are required");
+    if (!src_index) return egr_fail(g_prune_error, fn, "src_index is required");
+    if (n > PRUNE_MAX_ROWS || count > n) return egr_fail(g_prune_error, fn, "count <= n <= 2^26 rows is required");
     GatherArgs a{};
     uint32_t wmax = 1;
     for (int k = 0; k < num_arrays; k++) {
-        if (!arrays[k].src || !arrays[k].dst || arrays[k].width == 0) return fail("egr_prune_gather", "table entry without src / dst, or with width 0");
+        if (!arrays[k].src || !arrays[k].dst || arrays[k].width == 0) return egr_fail(g_prune_error, fn, "table entry without src / dst, or with width 0");
         a.t[k] = arrays[k];
         wmax = std::max(wmax, arrays[k].width);
     }
     // out of place only: a parallel gather must never write what another thread still reads (no dst may touch any src or another dst)
+    // (an empty table still counts with its first row: count == 0 or n == 0 does not excuse src == dst)
+    EgrRange dst[EGR_MAX_PRUNE_ARRAYS], src[EGR_MAX_PRUNE_ARRAYS];
     for (int k = 0; k < num_arrays; k++) {
-        const size_t dbytes = (size_t)std::max(count, 1u) * arrays[k].width * 4;
-        for (int j = 0; j < num_arrays; j++) {
-            if (overlap(arrays[k].dst, dbytes, arrays[j].src, (size_t)std::max(n, 1u) * arrays[j].width * 4))
-                return fail("egr_prune_gather", "dst overlaps a src (src == dst or overlapping ranges): the gather runs out of place");
-            if (j != k && overlap(arrays[k].dst, dbytes, arrays[j].dst, (size_t)std::max(count, 1u) * arrays[j].width * 4))
-                return fail("egr_prune_gather", "two dst ranges overlap");
-        }
+        dst[k] = EgrRange{arrays[k].dst, (uint64_t)std::max(count, 1u) * arrays[k].width * 4};
+        src[k] = EgrRange{arrays[k].src, (uint64_t)std::max(n, 1u) * arrays[k].width * 4};
     }
+    if (const EgrClash clash = egr_find_clash(dst, num_arrays, src, num_arrays))
+        return egr_fail(g_prune_error, fn, clash.kind == EGR_CLASH_INPUT ? "dst overlaps a src (src == dst or overlapping ranges): the gather runs out of place" : "two dst ranges overlap");
     if (count == 0) return 0;
     a.src_index = src_index, a.count = count;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        const size_t total = (size_t)count * wmax;
-        const uint32_t bx = (uint32_t)std::min<size_t>((total + 255) / 256, 65535u * 16u);
-        hipLaunchKernelGGL(k_prune_gather, dim3(bx, (uint32_t)num_arrays), dim3(256), 0, (hipStream_t)hip_stream, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail("egr_prune_gather", hipGetErrorString(e));
-    return 0;
+    const size_t total = (size_t)count * wmax;
+    const uint32_t bx = (uint32_t)std::min<size_t>((total + 255) / 256, 65535u * 16u);
+    return egr_on_device(device, g_prune_error, fn, [&] { egr_launch(k_prune_gather, dim3(bx, (uint32_t)num_arrays), dim3(256), (hipStream_t)hip_stream, a); });
 }

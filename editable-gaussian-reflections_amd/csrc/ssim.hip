@@ -175,20 +175,10 @@ __global__ void __launch_bounds__(SSIM_THREADS) k_ssim_finish(SsimArgs a) {
     }
 }
 
-bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
-struct Span {
-    const void *p;
-    size_t bytes;
-};
-
 // The checks both entry points share, before any HIP call; then the two launches.
 int run(const char *fn, bool images, int device, uint32_t num_views, uint32_t height, uint32_t width, const float *final, const float *rgb, const float *const target[3],
         double *ssim_sum, double *ssim, void *workspace, void *hip_stream) {
-    auto fail = [&](const std::string &what) { return egr_eval_fail(fn, what); };
+    auto fail = [&](const std::string &what) { return egr_fail(g_eval_error, fn, what); };
     if (num_views == 0 || num_views > SSIM_MAX_VIEWS) return fail("num_views must be in 1..65535");
     if (height == 0 || width == 0) return fail("height and width must be >= 1");
     if (images) {
@@ -200,14 +190,10 @@ int run(const char *fn, bool images, int device, uint32_t num_views, uint32_t he
     const size_t tiles_x = ((size_t)width + TILE - 1) / TILE, tiles = EGR_SSIM_BLOCKS(height, width);
     if (tiles > 0x7FFFFFFFull) return fail("the image is too large");
     const size_t image = (size_t)num_views * height * width * 3 * sizeof(float), passes = images ? 1 : 3;
-    const Span in[5] = {{final, image}, {rgb, 3 * image}, {target[0], image}, {target[1], image}, {target[2], image}};
-    const Span out[3] = {{ssim_sum, (size_t)num_views * passes * 6 * 8}, {ssim, (size_t)num_views * passes * 2 * 8}, {workspace, EGR_SSIM_WORKSPACE_BYTES(num_views, height, width)}};
-    for (int o = 0; o < 3; o++) {
-        for (int i = 0; i < 5; i++)
-            if (overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes)) return fail("an output (ssim_sum, ssim, workspace) overlaps an input");
-        for (int q = o + 1; q < 3; q++)
-            if (overlap(out[o].p, out[o].bytes, out[q].p, out[q].bytes)) return fail("two outputs (ssim_sum, ssim, workspace) overlap");
-    }
+    const EgrRange in[5] = {{final, image}, {rgb, 3 * image}, {target[0], image}, {target[1], image}, {target[2], image}};
+    const EgrRange out[3] = {{ssim_sum, (uint64_t)num_views * passes * 6 * 8}, {ssim, (uint64_t)num_views * passes * 2 * 8}, {workspace, EGR_SSIM_WORKSPACE_BYTES(num_views, height, width)}};
+    if (const EgrClash clash = egr_find_clash(out, 3, in, 5))
+        return fail(clash.kind == EGR_CLASH_INPUT ? "an output (ssim_sum, ssim, workspace) overlaps an input" : "two outputs (ssim_sum, ssim, workspace) overlap");
     SsimArgs a{};
     a.final = final, a.rgb = rgb, a.target[0] = target[0], a.target[1] = target[1], a.target[2] = target[2];
     a.partial = (double *)workspace, a.sum = ssim_sum, a.mean = ssim;
@@ -216,18 +202,10 @@ int run(const char *fn, bool images, int device, uint32_t num_views, uint32_t he
     for (int k = 0; k < TAPS; k++) total += e[k] = std::exp(-(double)((k - REACH) * (k - REACH)) / (2.0 * 1.5 * 1.5));
     for (int k = 0; k < TAPS; k++) a.w[k] = e[k] / total;
     hipStream_t s = (hipStream_t)hip_stream;
-    hipError_t err = hipSetDevice(device);
-    if (err == hipSuccess) {
-        if (images) hipLaunchKernelGGL(k_ssim_partial<true>, dim3(a.tiles, num_views), dim3(SSIM_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(k_ssim_partial<false>, dim3(a.tiles, num_views), dim3(SSIM_THREADS), 0, s, a);
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(k_ssim_finish, dim3(num_views), dim3(SSIM_THREADS), 0, s, a);
-        err = hipGetLastError();
-    }
-    if (err != hipSuccess) return fail(hipGetErrorString(err));
-    return 0;
+    return egr_on_device(device, g_eval_error, fn, [&] {
+        egr_launch(images ? k_ssim_partial<true> : k_ssim_partial<false>, dim3(a.tiles, num_views), dim3(SSIM_THREADS), s, a);
+        egr_launch(k_ssim_finish, dim3(num_views), dim3(SSIM_THREADS), s, a);
+    });
 }
 
 } // namespace

@@ -16,6 +16,7 @@
 #include <string>
 
 #include "../../include/egr_raytracer.h"
+#include "egr_host.hpp"
 
 namespace {
 
@@ -59,19 +60,16 @@ extern "C" const char *egr_fused_step_last_error(void) { return g_step_error.c_s
 
 extern "C" int egr_fused_adam_step(int device, const egr_param_group *groups, int num_groups, uint32_t n, uint32_t step, double beta1, double beta2,
                                    double eps, void *hip_stream) {
-    if (!groups || num_groups < 1 || num_groups > EGR_MAX_PARAM_GROUPS || step < 1) {
-        g_step_error = "libegr_hip: egr_fused_adam_step: 1..EGR_MAX_PARAM_GROUPS groups and a 1-based step are required";
-        return 1;
-    }
+    const char *fn = "egr_fused_adam_step";
+    // ---- validation: before any HIP call
+    if (!groups || num_groups < 1 || num_groups > EGR_MAX_PARAM_GROUPS || step < 1) return egr_fail(g_step_error, fn, "1..EGR_MAX_PARAM_GROUPS groups and a 1-based step are required");
     if (n == 0) return 0;
     StepArgs a{};
     uint32_t wmax = 1;
     for (int k = 0; k < num_groups; k++) {
         a.g[k] = groups[k];
-        if (!groups[k].param || groups[k].width == 0 || (groups[k].exp_avg == nullptr) != (groups[k].exp_avg_sq == nullptr)) {
-            g_step_error = "libegr_hip: egr_fused_adam_step: group without parameter / width, or with only one Adam moment";
-            return 1;
-        }
+        if (!groups[k].param || groups[k].width == 0 || (groups[k].exp_avg == nullptr) != (groups[k].exp_avg_sq == nullptr))
+            return egr_fail(g_step_error, fn, "group without parameter / width, or with only one Adam moment");
         const double t = (double)(groups[k].step ? groups[k].step : step); // a group whose optimizer state was re-created counts from its own 1
         a.step_size[k] = (float)((double)groups[k].lr / (1.0 - std::pow(beta1, t)));
         a.bc2_sqrt[k] = (float)std::sqrt(1.0 - std::pow(beta2, t));
@@ -80,16 +78,7 @@ extern "C" int egr_fused_adam_step(int device, const egr_param_group *groups, in
     a.w1 = (float)(1.0 - beta1), a.beta2 = (float)beta2, a.w2 = (float)(1.0 - beta2);
     a.eps = (float)eps;
     a.n = n;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        const size_t total = (size_t)n * wmax;
-        const uint32_t bx = (uint32_t)std::min<size_t>((total + 255) / 256, 65535u * 16u);
-        hipLaunchKernelGGL(k_fused_step, dim3(bx, (uint32_t)num_groups), dim3(256), 0, (hipStream_t)hip_stream, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) {
-        g_step_error = std::string("libegr_hip: egr_fused_adam_step: ") + hipGetErrorString(e);
-        return 1;
-    }
-    return 0;
+    const size_t total = (size_t)n * wmax;
+    const uint32_t bx = (uint32_t)std::min<size_t>((total + 255) / 256, 65535u * 16u);
+    return egr_on_device(device, g_step_error, fn, [&] { egr_launch(k_fused_step, dim3(bx, (uint32_t)num_groups), dim3(256), (hipStream_t)hip_stream, a); });
 }

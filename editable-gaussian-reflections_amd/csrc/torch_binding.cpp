@@ -826,11 +826,78 @@ struct Raytracer : torch::CustomClassHolder {
     }
 };
 
+// ---- The context-free ops (torch.ops.egr.*, torch.ops.simple_knn.distCUDA2): tensors in, one library call each. Every op checks its tensor arguments through
+// tensor_arg (words_arg for the lists of 4-byte rows) and takes a c10::DeviceGuard for the tensors' device BEFORE it allocates an output or reads
+// current_stream(): the tensors need not live on the current device, and the library is handed the stream of the device it is told to run on.
+namespace {
+bool given(const c10::optional<Tensor> &t) { return t.has_value() && t->defined(); }
+// (a Tensor[] cannot hold None: there an undefined or empty tensor is an absent entry)
+c10::optional<Tensor> unless_empty(const Tensor &t) { return t.defined() && t.numel() ? c10::optional<Tensor>(t) : c10::nullopt; }
+
+// What a tensor argument must measure: a full shape (-1: any size in that dimension), at least so many rows of a trailing shape, or a number of elements in any shape.
+struct Shape {
+    std::vector<int64_t> dims;
+    int64_t min_rows = 0, numel = -1;
+    Shape(std::initializer_list<int64_t> d) : dims(d) {}
+    Shape(std::vector<int64_t> d) : dims(std::move(d)) {}
+    static Shape at_least(int64_t rows, std::vector<int64_t> trailing) {
+        trailing.insert(trailing.begin(), -1);
+        Shape s(std::move(trailing));
+        s.min_rows = rows;
+        return s;
+    }
+    static Shape elements(int64_t n) {
+        Shape s(std::vector<int64_t>{});
+        s.numel = n;
+        return s;
+    }
+    bool fits(const Tensor &t) const {
+        if (numel >= 0) return t.numel() == numel;
+        if (t.dim() != (int64_t)dims.size() || (min_rows > 0 && t.size(0) < min_rows)) return false;
+        for (size_t d = 0; d < dims.size(); d++)
+            if (dims[d] >= 0 && t.size((int64_t)d) != dims[d]) return false;
+        return true;
+    }
+    std::string text() const {
+        if (numel >= 0) return "of " + std::to_string(numel) + " elements";
+        std::string s = "[";
+        for (size_t d = 0; d < dims.size(); d++)
+            s += (d ? ", " : "") + (dims[d] >= 0 ? std::to_string(dims[d]) : d == 0 && min_rows > 0 ? ">= " + std::to_string(min_rows) : std::string("*"));
+        return s + "]";
+    }
+};
+
+// THE argument check: a tensor of T's dtype, contiguous, on `dev`, of the wanted shape -> its data pointer. An absent one (None, or undefined) -> NULL if it is
+// optional, an error if it is required. Errors carry the op's and the argument's name.
+template <class T> T *tensor_arg(const char *op, const std::string &name, const c10::optional<Tensor> &t, c10::Device dev, const Shape &want, bool required = true) {
+    if (!given(t)) {
+        TORCH_CHECK(!required, op, ": ", name, " is required");
+        return nullptr;
+    }
+    constexpr c10::ScalarType dtype = c10::CppTypeToScalarType<T>::value;
+    TORCH_CHECK(t->is_cuda() && t->device() == dev && t->scalar_type() == dtype && t->is_contiguous() && want.fits(*t), op, ": ", name, " must be a contiguous ", dtype, " tensor ",
+                want.text(), " on ", dev, ", got ", t->scalar_type(), " ", t->sizes(), t->is_contiguous() ? "" : " (not contiguous)", " on ", t->device());
+    return t->data_ptr<T>();
+}
+// An entry of the tensor lists of prune_gather and grow_append: n rows of 4-byte elements of any dtype, moved as bits.
+void *words_arg(const char *op, const char *list, size_t k, const Tensor &t, c10::Device dev, int64_t n) {
+    TORCH_CHECK(t.defined() && t.is_cuda() && t.device() == dev && t.is_contiguous() && t.element_size() == 4 && t.dim() >= 1 && t.size(0) == n, op, ": ", list, "[", k,
+                "] must be a contiguous tensor of 4-byte elements with ", n, " rows on ", dev, " (contiguous GPU tensors of 4-byte elements with the same leading size are required)");
+    return t.data_ptr();
+}
+// The device of an op: that of the tensor that leads its arguments.
+c10::Device gpu_of(const char *op, const char *name, const Tensor &t) {
+    TORCH_CHECK(t.defined() && t.is_cuda(), op, ": ", name, " must be a GPU tensor (there is no CPU path)");
+    return t.device();
+}
+} // namespace
+
 // simple_knn._C.distCUDA2 (gaussian_model.py:17): float CUDA(HIP) tensor [N,3] -> [N] mean squared distance to the 3 nearest
 // neighbours. Registered as torch.ops.simple_knn.distCUDA2; the package's simple_knn.py re-exports it under the reference's name.
-static torch::Tensor dist_hip2(const torch::Tensor &points) {
+static Tensor dist_hip2(const Tensor &points) {
     TORCH_CHECK(points.is_cuda(), "distCUDA2: points must live on the GPU (there is no CPU path)");
     TORCH_CHECK(points.dim() == 2 && points.size(1) == 3, "distCUDA2: expected an [N,3] tensor");
+    const c10::DeviceGuard guard(points.device());
     auto p = points.to(torch::kFloat32).contiguous();
     auto out = torch::zeros({p.size(0)}, p.options());
     const int rc = egr_knn_mean_dist2(p.get_device(), p.data_ptr<float>(), (uint32_t)p.size(0), out.data_ptr<float>(), current_stream());
@@ -839,36 +906,36 @@ static torch::Tensor dist_hip2(const torch::Tensor &points) {
 }
 // One launch for import + scale decay + Adam + clamps + zero_grad + export (csrc/step.hip). Tensor lists are parallel, one
 // entry per parameter group; an undefined / empty tensor means "absent" for grads, rt_params, rt_grads and the Adam moments.
-static void fused_adam_step(std::vector<torch::Tensor> params, std::vector<torch::Tensor> grads, std::vector<torch::Tensor> rt_params,
-                            std::vector<torch::Tensor> rt_grads, std::vector<torch::Tensor> exp_avg, std::vector<torch::Tensor> exp_avg_sq,
-                            std::vector<double> lrs, std::vector<double> clamp_min, std::vector<double> clamp_max, std::vector<double> log_decay,
+static void fused_adam_step(std::vector<Tensor> params, std::vector<Tensor> grads, std::vector<Tensor> rt_params, std::vector<Tensor> rt_grads, std::vector<Tensor> exp_avg,
+                            std::vector<Tensor> exp_avg_sq, std::vector<double> lrs, std::vector<double> clamp_min, std::vector<double> clamp_max, std::vector<double> log_decay,
                             int64_t step, double beta1, double beta2, double eps, std::vector<int64_t> group_steps) {
+    const char *op = "fused_adam_step";
     const size_t G = params.size();
     TORCH_CHECK(G >= 1 && G <= EGR_MAX_PARAM_GROUPS, "fused_adam_step: 1..8 parameter groups");
     TORCH_CHECK(grads.size() == G && rt_params.size() == G && rt_grads.size() == G && exp_avg.size() == G && exp_avg_sq.size() == G && lrs.size() == G &&
                     clamp_min.size() == G && clamp_max.size() == G && log_decay.size() == G,
                 "fused_adam_step: all lists need one entry per group");
     TORCH_CHECK(group_steps.empty() || group_steps.size() == G, "fused_adam_step: group_steps must be empty (every group uses `step`) or hold one count per group");
-    egr_param_group g[EGR_MAX_PARAM_GROUPS];
+    const c10::Device dev = gpu_of(op, "params[0]", params[0]);
+    const c10::DeviceGuard guard(dev);
+    TORCH_CHECK(params[0].dim() >= 1, "fused_adam_step: parameters must be contiguous float GPU tensors with the same leading size");
     const int64_t n = params[0].size(0);
-    auto ptr = [&](const torch::Tensor &t, const torch::Tensor &like, const char *what) -> float * {
-        if (!t.defined() || t.numel() == 0) return nullptr;
-        TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.numel() == like.numel(), "fused_adam_step: ", what,
-                    " must be a contiguous float GPU tensor of the parameter's size");
-        return t.data_ptr<float>();
-    };
+    egr_param_group g[EGR_MAX_PARAM_GROUPS];
     for (size_t k = 0; k < G; k++) {
-        TORCH_CHECK(params[k].is_cuda() && params[k].scalar_type() == torch::kFloat32 && params[k].is_contiguous() && params[k].size(0) == n,
-                    "fused_adam_step: parameters must be contiguous float GPU tensors with the same leading size");
-        g[k].param = params[k].data_ptr<float>();
-        g[k].grad = ptr(grads[k], params[k], "grad"), g[k].rt_param = ptr(rt_params[k], params[k], "rt_param");
-        g[k].rt_grad = ptr(rt_grads[k], params[k], "rt_grad");
-        g[k].exp_avg = ptr(exp_avg[k], params[k], "exp_avg"), g[k].exp_avg_sq = ptr(exp_avg_sq[k], params[k], "exp_avg_sq");
+        const std::string at = "[" + std::to_string(k) + "]";
+        const Shape size = Shape::elements(params[k].defined() ? params[k].numel() : 0); // (of the parameter: every other tensor of the group has it)
+        g[k].param = tensor_arg<float>(op, "params" + at, params[k], dev, size);
+        TORCH_CHECK(params[k].dim() >= 1 && params[k].size(0) == n, "fused_adam_step: parameters must be contiguous float GPU tensors with the same leading size");
+        g[k].grad = tensor_arg<float>(op, "grads" + at, unless_empty(grads[k]), dev, size, false);
+        g[k].rt_param = tensor_arg<float>(op, "rt_params" + at, unless_empty(rt_params[k]), dev, size, false);
+        g[k].rt_grad = tensor_arg<float>(op, "rt_grads" + at, unless_empty(rt_grads[k]), dev, size, false);
+        g[k].exp_avg = tensor_arg<float>(op, "exp_avg" + at, unless_empty(exp_avg[k]), dev, size, false);
+        g[k].exp_avg_sq = tensor_arg<float>(op, "exp_avg_sq" + at, unless_empty(exp_avg_sq[k]), dev, size, false);
         g[k].width = n ? (uint32_t)(params[k].numel() / n) : 1u;
         g[k].lr = (float)lrs[k], g[k].clamp_min = (float)clamp_min[k], g[k].clamp_max = (float)clamp_max[k], g[k].log_decay = (float)log_decay[k];
         g[k].step = group_steps.size() == G ? (uint32_t)group_steps[k] : 0u;
     }
-    const int rc = egr_fused_adam_step(params[0].get_device(), g, (int)G, (uint32_t)n, (uint32_t)step, beta1, beta2, eps, current_stream());
+    const int rc = egr_fused_adam_step(dev.index(), g, (int)G, (uint32_t)n, (uint32_t)step, beta1, beta2, eps, current_stream());
     TORCH_CHECK(rc == 0, egr_fused_step_last_error());
 }
 
@@ -877,45 +944,22 @@ static void fused_adam_step(std::vector<torch::Tensor> params, std::vector<torch
 // entries are the kept rows, ascending; count int32 [1]) on the device, asynchronously: reading `count` is the caller's one synchronisation.
 static std::tuple<Tensor, Tensor> prune_select(const c10::optional<Tensor> &total_weight, double divisor, double min_weight, const c10::optional<Tensor> &points,
                                                const c10::optional<Tensor> &cam_centers, const c10::optional<Tensor> &cam_znear, const c10::optional<Tensor> &remove_mask) {
-    auto given = [](const c10::optional<Tensor> &t) { return t.has_value() && t->defined(); };
-    int64_t n = -1;
-    c10::Device dev(torch::kCUDA);
-    auto rows = [&](const Tensor &t, const char *what) {
-        TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() >= 1, "prune_select: ", what, " must be a contiguous GPU tensor");
-        TORCH_CHECK(n < 0 || (t.size(0) == n && t.device() == dev), "prune_select: ", what, " has ", t.size(0), " rows on ", t.device(), ", expected ", n, " on ", dev);
-        n = t.size(0), dev = t.device();
-    };
-    const float *tw = nullptr, *pts = nullptr, *cc = nullptr, *cz = nullptr;
-    const uint8_t *mask = nullptr;
-    int64_t num_cams = 0;
-    if (given(total_weight)) {
-        rows(*total_weight, "total_weight");
-        TORCH_CHECK(total_weight->scalar_type() == torch::kFloat32 && total_weight->numel() == n, "prune_select: total_weight must be fp32 [N] or [N,1]");
-        tw = total_weight->data_ptr<float>();
-    }
-    if (given(points)) {
-        rows(*points, "points");
-        TORCH_CHECK(points->scalar_type() == torch::kFloat32 && points->dim() == 2 && points->size(1) == 3, "prune_select: points must be fp32 [N,3]");
-        pts = points->data_ptr<float>();
-    }
-    if (given(remove_mask)) {
-        rows(*remove_mask, "remove_mask");
-        TORCH_CHECK((remove_mask->scalar_type() == torch::kUInt8 || remove_mask->scalar_type() == torch::kBool) && remove_mask->numel() == n, "prune_select: remove_mask must be uint8 or bool [N]");
-        mask = reinterpret_cast<const uint8_t *>(remove_mask->data_ptr());
-    }
-    TORCH_CHECK(n >= 0, "prune_select: one of total_weight, points, remove_mask is required (it fixes the number of rows)");
-    TORCH_CHECK(given(cam_centers) == given(cam_znear), "prune_select: cam_centers and cam_znear go together");
-    if (given(cam_centers)) {
-        TORCH_CHECK(pts != nullptr, "prune_select: the camera criterion needs points");
-        num_cams = cam_znear->numel();
-        TORCH_CHECK(cam_centers->is_cuda() && cam_centers->device() == dev && cam_centers->scalar_type() == torch::kFloat32 && cam_centers->is_contiguous() && cam_centers->dim() == 2 &&
-                        cam_centers->size(0) == num_cams && cam_centers->size(1) == 3,
-                    "prune_select: cam_centers must be a contiguous fp32 [C,3] tensor on the points' device");
-        TORCH_CHECK(cam_znear->is_cuda() && cam_znear->device() == dev && cam_znear->scalar_type() == torch::kFloat32 && cam_znear->is_contiguous() && cam_znear->dim() == 1,
-                    "prune_select: cam_znear must be a contiguous fp32 [C] tensor on the points' device");
-        cc = cam_centers->data_ptr<float>(), cz = cam_znear->data_ptr<float>();
-    }
+    const char *op = "prune_select";
+    const Tensor *first = given(total_weight) ? &*total_weight : given(points) ? &*points : given(remove_mask) ? &*remove_mask : nullptr;
+    TORCH_CHECK(first, "prune_select: one of total_weight, points, remove_mask is required (it fixes the number of rows)");
+    const c10::Device dev = gpu_of(op, "the first criterion", *first);
+    const c10::DeviceGuard guard(dev);
+    TORCH_CHECK(first->dim() >= 1, "prune_select: the criteria are tensors with one row per gaussian");
+    const int64_t n = first->size(0);
     TORCH_CHECK(n <= (int64_t)0xFFFFFFFFll, "prune_select: too many rows");
+    const float *tw = tensor_arg<float>(op, "total_weight ([N] or [N,1])", total_weight, dev, Shape::elements(n), false);
+    const float *pts = tensor_arg<float>(op, "points", points, dev, {n, 3}, false);
+    const bool as_bool = given(remove_mask) && remove_mask->scalar_type() == torch::kBool; // (a bool is a byte that is 0 or 1)
+    const uint8_t *mask = tensor_arg<uint8_t>(op, "remove_mask (uint8 or bool)", as_bool ? c10::optional<Tensor>(remove_mask->view(torch::kUInt8)) : remove_mask, dev, Shape::elements(n), false);
+    TORCH_CHECK(given(cam_centers) == given(cam_znear), "prune_select: cam_centers and cam_znear go together");
+    TORCH_CHECK(!given(cam_centers) || given(points), "prune_select: the camera criterion needs points");
+    const int64_t num_cams = given(cam_znear) ? cam_znear->numel() : 0;
+    const float *cc = tensor_arg<float>(op, "cam_centers", cam_centers, dev, {num_cams, 3}, false), *cz = tensor_arg<float>(op, "cam_znear", cam_znear, dev, {num_cams}, false);
     const auto i32 = torch::dtype(torch::kInt32).device(dev);
     Tensor src_index = torch::empty({n}, i32), count = torch::zeros({1}, i32);
     if (n == 0) return {src_index, count}; // (no rows: count 0, nothing to launch)
@@ -930,27 +974,27 @@ static std::tuple<Tensor, Tensor> prune_select(const c10::optional<Tensor> &tota
 // int32) with the same leading size - as one launch per EGR_MAX_PRUNE_ARRAYS tensors over the same index list. The outputs are new tensors of the source's
 // dtype and trailing shape with `count` rows.
 static std::vector<Tensor> prune_gather(std::vector<Tensor> src, const Tensor &src_index, int64_t count) {
-    TORCH_CHECK(src_index.is_cuda() && src_index.scalar_type() == torch::kInt32 && src_index.is_contiguous() && src_index.dim() == 1, "prune_gather: src_index must be the int32 list of prune_select");
-    TORCH_CHECK(count >= 0 && count <= src_index.numel(), "prune_gather: count must be in 0..", src_index.numel());
+    const char *op = "prune_gather";
+    const c10::Device dev = gpu_of(op, "src_index", src_index);
+    const c10::DeviceGuard guard(dev);
+    const int64_t n = src_index.numel(); // (the tensors need the rows the index list was selected from)
+    const uint32_t *index = reinterpret_cast<const uint32_t *>(tensor_arg<int32_t>(op, "src_index (the list of prune_select)", src_index, dev, {n}));
+    TORCH_CHECK(count >= 0 && count <= n, "prune_gather: count must be in 0..", n);
     std::vector<Tensor> out;
-    if (src.empty()) return out;
-    const int64_t n = src[0].dim() >= 1 ? src[0].size(0) : -1;
-    TORCH_CHECK(n == src_index.numel(), "prune_gather: the tensors need the ", src_index.numel(), " rows the index list was selected from");
     std::vector<egr_prune_array> table;
-    for (const Tensor &t : src) {
-        TORCH_CHECK(t.is_cuda() && t.device() == src_index.device() && t.is_contiguous() && t.element_size() == 4 && t.dim() >= 1 && t.size(0) == n,
-                    "prune_gather: contiguous GPU tensors of 4-byte elements with the same leading size are required");
+    for (size_t k = 0; k < src.size(); k++) {
+        const Tensor &t = src[k];
+        const void *rows = words_arg(op, "src", k, t, dev, n);
         auto shape = t.sizes().vec();
         shape[0] = count;
         out.push_back(torch::empty(shape, t.options()));
         const int64_t width = n ? t.numel() / n : 1;
         if (width == 0) continue; // (a [N,0] tensor has no elements to move)
-        table.push_back(egr_prune_array{t.data_ptr(), out.back().data_ptr(), (uint32_t)width});
+        table.push_back(egr_prune_array{rows, out.back().data_ptr(), (uint32_t)width});
     }
     if (n == 0 || count == 0) return out; // (empty tensors have no storage to hand to the library)
     for (size_t k0 = 0; k0 < table.size(); k0 += EGR_MAX_PRUNE_ARRAYS) {
-        const int rc = egr_prune_gather(src_index.get_device(), table.data() + k0, (int)std::min<size_t>(EGR_MAX_PRUNE_ARRAYS, table.size() - k0), (uint32_t)n,
-                                        reinterpret_cast<const uint32_t *>(src_index.data_ptr<int32_t>()), (uint32_t)count, current_stream());
+        const int rc = egr_prune_gather(dev.index(), table.data() + k0, (int)std::min<size_t>(EGR_MAX_PRUNE_ARRAYS, table.size() - k0), (uint32_t)n, index, (uint32_t)count, current_stream());
         TORCH_CHECK(rc == 0, egr_prune_last_error());
     }
     return out;
@@ -962,7 +1006,7 @@ static Tensor grow_sample(int64_t first, int64_t n, int64_t seed, double radius,
     TORCH_CHECK(device.is_cuda(), "grow_sample: device must be a GPU (there is no CPU path), got ", device);
     TORCH_CHECK(n >= 0 && n <= ((int64_t)1 << 26), "grow_sample: n must be in 0..2^26 (the limit of the tree), got ", n);
     const c10::Device dev(torch::kCUDA, device.has_index() ? device.index() : c10::hip::current_device());
-    const c10::DeviceGuard guard(dev); // the output and current_stream() belong to `device`, which need not be the current one
+    const c10::DeviceGuard guard(dev);
     Tensor out = torch::empty({n, 3}, torch::dtype(torch::kFloat32).device(dev));
     if (n == 0) return out; // (an empty tensor has no storage to hand to the library)
     const int rc = egr_grow_sample(dev.index(), (uint64_t)first, (uint32_t)n, (uint64_t)seed, (float)radius, (float)clamp, out.data_ptr<float>(), current_stream());
@@ -973,6 +1017,7 @@ static Tensor grow_sample(int64_t first, int64_t n, int64_t seed, double radius,
 // same leading size n - as one launch per EGR_MAX_PRUNE_ARRAYS tensors. The m new rows of entry k are tail[k] (same dtype and trailing shape, m rows) or,
 // where tail[k] is None, the word fill_bits[k] in every element (an fp32's or int32's bits, -2^31 .. 2^32 - 1). The outputs are new tensors.
 static std::vector<Tensor> grow_append(std::vector<Tensor> src, const c10::List<c10::optional<Tensor>> &tail, std::vector<int64_t> fill_bits, int64_t m) {
+    const char *op = "grow_append";
     TORCH_CHECK(tail.size() == src.size() && fill_bits.size() == src.size(), "grow_append: src, tail and fill_bits must have one entry per tensor (", src.size(), ", ",
                 tail.size(), ", ", fill_bits.size(), ")");
     std::vector<Tensor> out;
@@ -980,27 +1025,24 @@ static std::vector<Tensor> grow_append(std::vector<Tensor> src, const c10::List<
     const int64_t n = src[0].dim() >= 1 ? src[0].size(0) : -1;
     TORCH_CHECK(n >= 0, "grow_append: tensors with a leading (row) dimension are required");
     TORCH_CHECK(m >= 0 && n + m <= ((int64_t)1 << 26), "grow_append: m must be >= 0 and n + m <= 2^26 rows (the limit of the tree), got n = ", n, ", m = ", m);
-    const c10::Device dev = src[0].device();
+    const c10::Device dev = gpu_of(op, "src[0]", src[0]);
     const c10::DeviceGuard guard(dev);
     std::vector<egr_grow_array> table;
     for (size_t k = 0; k < src.size(); k++) {
         const Tensor &t = src[k];
-        TORCH_CHECK(t.is_cuda() && t.device() == dev && t.is_contiguous() && t.element_size() == 4 && t.dim() >= 1 && t.size(0) == n,
-                    "grow_append: contiguous GPU tensors of 4-byte elements with the same leading size are required (src[", k, "])");
+        const void *rows = words_arg(op, "src", k, t, dev, n);
         TORCH_CHECK(fill_bits[k] >= -((int64_t)1 << 31) && fill_bits[k] < ((int64_t)1 << 32), "grow_append: fill_bits[", k, "] is not a 32-bit word");
         auto shape = t.sizes().vec();
         int64_t width = 1;
         for (size_t d = 1; d < shape.size(); d++) width *= shape[d];
         shape[0] = n + m;
-        egr_grow_array e{n ? t.data_ptr() : nullptr, nullptr, nullptr, (uint32_t)width, EGR_GROW_TAIL_FILL, (uint32_t)(uint64_t)fill_bits[k]};
+        egr_grow_array e{n ? rows : nullptr, nullptr, nullptr, (uint32_t)width, EGR_GROW_TAIL_FILL, (uint32_t)(uint64_t)fill_bits[k]};
         const c10::optional<Tensor> add = tail.get(k);
-        if (add.has_value() && add->defined()) {
-            auto want = shape;
-            want[0] = m;
-            TORCH_CHECK(add->is_cuda() && add->device() == dev && add->is_contiguous() && add->scalar_type() == t.scalar_type() && add->sizes().vec() == want,
-                        "grow_append: tail[", k, "] must be a contiguous ", t.scalar_type(), " tensor ", c10::IntArrayRef(want), " on ", dev, ", got ", add->scalar_type(), " ",
-                        add->sizes(), " on ", add->device());
-            e.tail = m ? add->data_ptr() : nullptr, e.tail_kind = EGR_GROW_TAIL_ROWS;
+        if (given(add)) {
+            const void *new_rows = words_arg(op, "tail", k, *add, dev, m);
+            TORCH_CHECK(add->scalar_type() == t.scalar_type() && add->sizes().slice(1) == t.sizes().slice(1), "grow_append: tail[", k, "] must have the dtype and the trailing shape of src[", k,
+                        "] (", t.scalar_type(), " ", t.sizes().slice(1), "), got ", add->scalar_type(), " ", add->sizes().slice(1));
+            e.tail = m ? new_rows : nullptr, e.tail_kind = EGR_GROW_TAIL_ROWS;
         }
         out.push_back(torch::empty(shape, t.options()));
         if (width == 0) continue; // (a [N,0] tensor has no elements to move)
@@ -1019,24 +1061,22 @@ static std::vector<Tensor> grow_append(std::vector<Tensor> src, const c10::List<
 // egr_edit_object records as bits (editing.py packs them); xyz fp32 [N,3] on the GPU; f0 [N,3], roughness [N,1], diffuse [N,3] only where an object has
 // that property range. Returns int32 [N] (bit k = row belongs to object k) on the current stream, no host synchronisation.
 static Tensor edit_select(const Tensor &xyz, const c10::optional<Tensor> &f0, const c10::optional<Tensor> &roughness, const c10::optional<Tensor> &diffuse, const Tensor &objects) {
-    TORCH_CHECK(xyz.is_cuda() && xyz.scalar_type() == torch::kFloat32 && xyz.is_contiguous() && xyz.dim() == 2 && xyz.size(1) == 3, "edit_select: xyz must be a contiguous fp32 [N,3] GPU tensor");
+    const char *op = "edit_select";
+    const c10::Device dev = gpu_of(op, "xyz", xyz);
+    const c10::DeviceGuard guard(dev);
+    const float *pxyz = tensor_arg<float>(op, "xyz", xyz, dev, {-1, 3});
     const int64_t n = xyz.size(0);
     TORCH_CHECK(n <= (int64_t)1 << 26, "edit_select: n exceeds 2^26 rows (the limit of the tree)");
     TORCH_CHECK(!objects.is_cuda() && objects.scalar_type() == torch::kInt32 && objects.is_contiguous() && objects.dim() == 2 &&
                     objects.size(1) == (int64_t)(sizeof(egr_edit_object) / 4),
                 "edit_select: objects must be a contiguous CPU int32 [K,", sizeof(egr_edit_object) / 4, "] tensor (egr_edit_object records)");
     TORCH_CHECK(objects.size(0) <= EGR_MAX_EDIT_OBJECTS, "edit_select: at most ", EGR_MAX_EDIT_OBJECTS, " objects");
-    auto ptr = [&](const c10::optional<Tensor> &t, int64_t width, const char *what) -> const float * {
-        if (!t.has_value() || !t->defined()) return nullptr;
-        TORCH_CHECK(t->is_cuda() && t->device() == xyz.device() && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->numel() == n * width,
-                    "edit_select: ", what, " must be a contiguous fp32 [N,", width, "] tensor on xyz's device");
-        return t->data_ptr<float>();
-    };
-    const float *pf0 = ptr(f0, 3, "f0"), *pr = ptr(roughness, 1, "roughness"), *pd = ptr(diffuse, 3, "diffuse");
-    Tensor mask = torch::empty({n}, torch::dtype(torch::kInt32).device(xyz.device()));
+    const float *pf0 = tensor_arg<float>(op, "f0 ([N,3])", f0, dev, Shape::elements(n * 3), false), *pr = tensor_arg<float>(op, "roughness ([N,1])", roughness, dev, Shape::elements(n), false);
+    const float *pd = tensor_arg<float>(op, "diffuse ([N,3])", diffuse, dev, Shape::elements(n * 3), false);
+    Tensor mask = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
     if (n == 0) return mask; // (no rows: nothing to launch)
-    const int rc = egr_edit_select(xyz.get_device(), (uint32_t)n, xyz.data_ptr<float>(), pf0, pr, pd, reinterpret_cast<const egr_edit_object *>(objects.data_ptr<int32_t>()),
-                                   (uint32_t)objects.size(0), reinterpret_cast<uint32_t *>(mask.data_ptr<int32_t>()), current_stream());
+    const int rc = egr_edit_select(dev.index(), (uint32_t)n, pxyz, pf0, pr, pd, reinterpret_cast<const egr_edit_object *>(objects.data_ptr<int32_t>()), (uint32_t)objects.size(0),
+                                   reinterpret_cast<uint32_t *>(mask.data_ptr<int32_t>()), current_stream());
     TORCH_CHECK(rc == 0, egr_edit_last_error());
     return mask;
 }
@@ -1044,83 +1084,81 @@ static Tensor edit_select(const Tensor &xyz, const c10::optional<Tensor> &f0, co
 // scale [N,3], rotation [N,4], mean [N,3], opacity [N,1], rgb [N,3], normal [N,3], roughness [N,1], f0 [N,3]; dst[k] may be src[k] itself. `mask`: the int32 [N]
 // tensor of edit_select; `records`: a GPU int32 tensor [K, 43] holding K egr_edit_record records as bits. Current stream, no host synchronisation.
 static void edit_apply(std::vector<Tensor> src, std::vector<Tensor> dst, const Tensor &mask, const Tensor &records) {
+    const char *op = "edit_apply";
     static const int64_t width[8] = {3, 4, 3, 1, 3, 3, 1, 3};
     TORCH_CHECK(src.size() == 8 && dst.size() == 8, "edit_apply: src and dst are eight tensors each (scale, rotation, mean, opacity, rgb, normal, roughness, f0)");
+    const c10::Device dev = gpu_of(op, "src[0]", src[0]);
+    const c10::DeviceGuard guard(dev);
     TORCH_CHECK(src[0].dim() >= 1, "edit_apply: tensors with rows are required");
     const int64_t n = src[0].size(0);
     TORCH_CHECK(n <= (int64_t)1 << 26, "edit_apply: n exceeds 2^26 rows (the limit of the tree)");
-    const auto dev = src[0].device();
     egr_edit_arrays s{}, d{};
     float **sp = &s.scale, **dp = &d.scale;
     for (int k = 0; k < 8; k++) {
-        for (const Tensor *t : {&src[k], &dst[k]})
-            TORCH_CHECK(t->is_cuda() && t->device() == dev && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->dim() >= 1 && t->size(0) == n && t->numel() == n * width[k],
-                        "edit_apply: tensor ", k, " must be a contiguous fp32 [N,", width[k], "] GPU tensor");
-        sp[k] = src[k].data_ptr<float>(), dp[k] = dst[k].data_ptr<float>();
+        const std::string at = "[" + std::to_string(k) + "] ([N," + std::to_string(width[k]) + "])";
+        sp[k] = tensor_arg<float>(op, "src" + at, src[k], dev, Shape::elements(n * width[k])), dp[k] = tensor_arg<float>(op, "dst" + at, dst[k], dev, Shape::elements(n * width[k]));
+        TORCH_CHECK(src[k].dim() >= 1 && src[k].size(0) == n && dst[k].dim() >= 1 && dst[k].size(0) == n, "edit_apply: tensor ", k, " must be a contiguous fp32 [N,", width[k], "] GPU tensor");
     }
-    TORCH_CHECK(records.is_cuda() && records.device() == dev && records.scalar_type() == torch::kInt32 && records.is_contiguous() && records.dim() == 2 &&
-                    records.size(1) == (int64_t)(sizeof(egr_edit_record) / 4) && records.size(0) <= EGR_MAX_EDIT_OBJECTS,
-                "edit_apply: records must be a contiguous GPU int32 [K <= 32,", sizeof(egr_edit_record) / 4, "] tensor (egr_edit_record records)");
-    TORCH_CHECK(mask.is_cuda() && mask.device() == dev && mask.scalar_type() == torch::kInt32 && mask.is_contiguous() && mask.dim() == 1 && mask.size(0) == n,
-                "edit_apply: mask must be the int32 [N] tensor of edit_select");
+    const int32_t *rec = tensor_arg<int32_t>(op, "records (K <= 32 egr_edit_record records)", records, dev, {-1, (int64_t)(sizeof(egr_edit_record) / 4)});
+    const int64_t K = records.size(0);
+    TORCH_CHECK(K <= EGR_MAX_EDIT_OBJECTS, "edit_apply: at most ", EGR_MAX_EDIT_OBJECTS, " records");
+    const int32_t *bits = tensor_arg<int32_t>(op, "mask (the tensor of edit_select)", mask, dev, {n});
     if (n == 0) return; // (empty tensors have no storage to hand to the library)
-    const int rc = egr_edit_apply(dev.index(), (uint32_t)n, &s, &d, reinterpret_cast<const uint32_t *>(mask.data_ptr<int32_t>()),
-                                  records.size(0) ? reinterpret_cast<const egr_edit_record *>(records.data_ptr<int32_t>()) : nullptr, (uint32_t)records.size(0), current_stream());
+    const int rc = egr_edit_apply(dev.index(), (uint32_t)n, &s, &d, reinterpret_cast<const uint32_t *>(bits), K ? reinterpret_cast<const egr_edit_record *>(rec) : nullptr, (uint32_t)K, current_stream());
     TORCH_CHECK(rc == 0, egr_edit_last_error());
 }
 
-// Fused evaluation metrics (egr_eval_metrics, csrc/eval.hip): final [V,H,W,3], rgb [V,3,H,W,3] (None when both of its targets are) and the channel-major targets
-// [V,3,H,W] (None: the pass is skipped and reports NaN) as contiguous fp32 GPU tensors. Returns (sse fp64 [V,3,3], psnr fp64 [V,3,2], display fp32 [V,3,2,3,H,W] -
+// What eval_metrics and eval_ssim take: final [V,H,W,3], rgb [V,3,H,W,3] (None when both of its targets are) and the channel-major targets [V,3,H,W] (None: the pass
+// is skipped and reports NaN) as contiguous fp32 tensors on one GPU. The checks of both ops, the sizes they derive and the pointers they pass on.
+struct EvalInputs {
+    c10::Device dev;
+    int64_t V, H, W;
+    const float *final, *rgb, *target_final, *target_diffuse, *target_specular;
+};
+static EvalInputs eval_inputs(const char *op, const Tensor &final, const c10::optional<Tensor> &rgb, const c10::optional<Tensor> &target_final,
+                              const c10::optional<Tensor> &target_diffuse, const c10::optional<Tensor> &target_specular) {
+    EvalInputs a{gpu_of(op, "final", final), 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    a.final = tensor_arg<float>(op, "final ([V,H,W,3])", final, a.dev, {-1, -1, -1, 3});
+    a.V = final.size(0), a.H = final.size(1), a.W = final.size(2);
+    TORCH_CHECK(a.V >= 1 && a.H >= 1 && a.W >= 1 && a.H <= 0x7FFFFFFF && a.W <= 0x7FFFFFFF, op, ": at least one view and one pixel are required");
+    a.rgb = tensor_arg<float>(op, "rgb", rgb, a.dev, {a.V, EGR_NUM_STEPS, a.H, a.W, 3}, false);
+    a.target_final = tensor_arg<float>(op, "target_final", target_final, a.dev, {a.V, 3, a.H, a.W}, false);
+    a.target_diffuse = tensor_arg<float>(op, "target_diffuse", target_diffuse, a.dev, {a.V, 3, a.H, a.W}, false);
+    a.target_specular = tensor_arg<float>(op, "target_specular", target_specular, a.dev, {a.V, 3, a.H, a.W}, false);
+    return a;
+}
+
+// Fused evaluation metrics (egr_eval_metrics, csrc/eval.hip) on the tensors of eval_inputs. Returns (sse fp64 [V,3,3], psnr fp64 [V,3,2], display fp32 [V,3,2,3,H,W] -
 // or an empty tensor without want_display; a skipped pass reads NaN there) on the device, two launches on the current stream, no host synchronisation.
 static std::tuple<Tensor, Tensor, Tensor> eval_metrics(const Tensor &final, const c10::optional<Tensor> &rgb, const c10::optional<Tensor> &target_final,
                                                        const c10::optional<Tensor> &target_diffuse, const c10::optional<Tensor> &target_specular, bool want_display) {
-    TORCH_CHECK(final.is_cuda() && final.scalar_type() == torch::kFloat32 && final.is_contiguous() && final.dim() == 4 && final.size(3) == 3, "eval_metrics: final must be a contiguous fp32 [V,H,W,3] GPU tensor");
-    const int64_t V = final.size(0), H = final.size(1), W = final.size(2);
-    TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && H <= 0x7FFFFFFF && W <= 0x7FFFFFFF, "eval_metrics: at least one view and one pixel are required");
-    const auto dev = final.device();
-    const c10::DeviceGuard guard(dev); // the outputs, the workspace and current_stream() belong to final's device, which need not be the current one
-    auto ptr = [&](const c10::optional<Tensor> &t, std::vector<int64_t> want, const char *what) -> const float * {
-        if (!t.has_value() || !t->defined()) return nullptr;
-        TORCH_CHECK(t->is_cuda() && t->device() == dev && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->sizes() == torch::IntArrayRef(want), "eval_metrics: ", what,
-                    " must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " on final's device, got ", t->sizes());
-        return t->data_ptr<float>();
-    };
-    const float *prgb = ptr(rgb, {V, EGR_NUM_STEPS, H, W, 3}, "rgb");
-    const float *tf = ptr(target_final, {V, 3, H, W}, "target_final"), *td = ptr(target_diffuse, {V, 3, H, W}, "target_diffuse"), *ts = ptr(target_specular, {V, 3, H, W}, "target_specular");
-    const auto f64 = torch::dtype(torch::kFloat64).device(dev);
+    const EvalInputs a = eval_inputs("eval_metrics", final, rgb, target_final, target_diffuse, target_specular);
+    const c10::DeviceGuard guard(a.dev);
+    const int64_t V = a.V, H = a.H, W = a.W;
+    const auto f64 = torch::dtype(torch::kFloat64).device(a.dev);
     Tensor sse = torch::empty({V, 3, 3}, f64), psnr = torch::empty({V, 3, 2}, f64);
     Tensor display = torch::empty({0}, final.options());
-    if (want_display) display = (tf && td && ts) ? torch::empty({V, 3, 2, 3, H, W}, final.options()) : torch::full({V, 3, 2, 3, H, W}, NAN, final.options());
+    if (want_display)
+        display = (a.target_final && a.target_diffuse && a.target_specular) ? torch::empty({V, 3, 2, 3, H, W}, final.options()) : torch::full({V, 3, 2, 3, H, W}, NAN, final.options());
     Tensor workspace = torch::empty({(int64_t)(EGR_EVAL_WORKSPACE_BYTES(V, H, W) / 8)}, f64); // (freed stream-ordered by the caching allocator)
-    const int rc = egr_eval_metrics(dev.index(), (uint32_t)V, (uint32_t)H, (uint32_t)W, final.data_ptr<float>(), prgb, tf, td, ts, sse.data_ptr<double>(), psnr.data_ptr<double>(),
-                                    want_display ? display.data_ptr<float>() : nullptr, workspace.data_ptr(), current_stream());
+    const int rc = egr_eval_metrics(a.dev.index(), (uint32_t)V, (uint32_t)H, (uint32_t)W, a.final, a.rgb, a.target_final, a.target_diffuse, a.target_specular, sse.data_ptr<double>(),
+                                    psnr.data_ptr<double>(), want_display ? display.data_ptr<float>() : nullptr, workspace.data_ptr(), current_stream());
     TORCH_CHECK(rc == 0, egr_eval_last_error());
     return {sse, psnr, display};
 }
 
-// Fused SSIM (egr_eval_ssim, csrc/ssim.hip) on the tensors of eval_metrics, with its checks. Returns (ssim_sum fp64 [V,3,3,2]: the sums of the SSIM map per pass and
-// channel over all pixels and over the interior, ssim fp64 [V,3,2]: the two means per pass; a skipped pass reads NaN) on the device, two launches on the current
-// stream, no host synchronisation.
+// Fused SSIM (egr_eval_ssim, csrc/ssim.hip) on the tensors of eval_inputs. Returns (ssim_sum fp64 [V,3,3,2]: the sums of the SSIM map per pass and channel over all
+// pixels and over the interior, ssim fp64 [V,3,2]: the two means per pass; a skipped pass reads NaN) on the device, two launches on the current stream, no host
+// synchronisation.
 static std::tuple<Tensor, Tensor> eval_ssim(const Tensor &final, const c10::optional<Tensor> &rgb, const c10::optional<Tensor> &target_final,
                                             const c10::optional<Tensor> &target_diffuse, const c10::optional<Tensor> &target_specular) {
-    TORCH_CHECK(final.is_cuda() && final.scalar_type() == torch::kFloat32 && final.is_contiguous() && final.dim() == 4 && final.size(3) == 3, "eval_ssim: final must be a contiguous fp32 [V,H,W,3] GPU tensor");
-    const int64_t V = final.size(0), H = final.size(1), W = final.size(2);
-    TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && H <= 0x7FFFFFFF && W <= 0x7FFFFFFF, "eval_ssim: at least one view and one pixel are required");
-    const auto dev = final.device();
-    const c10::DeviceGuard guard(dev); // the outputs, the workspace and current_stream() belong to final's device, which need not be the current one
-    auto ptr = [&](const c10::optional<Tensor> &t, std::vector<int64_t> want, const char *what) -> const float * {
-        if (!t.has_value() || !t->defined()) return nullptr;
-        TORCH_CHECK(t->is_cuda() && t->device() == dev && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->sizes() == torch::IntArrayRef(want), "eval_ssim: ", what,
-                    " must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " on final's device, got ", t->sizes());
-        return t->data_ptr<float>();
-    };
-    const float *prgb = ptr(rgb, {V, EGR_NUM_STEPS, H, W, 3}, "rgb");
-    const float *tf = ptr(target_final, {V, 3, H, W}, "target_final"), *td = ptr(target_diffuse, {V, 3, H, W}, "target_diffuse"), *ts = ptr(target_specular, {V, 3, H, W}, "target_specular");
-    const auto f64 = torch::dtype(torch::kFloat64).device(dev);
-    Tensor sum = torch::empty({V, 3, 3, 2}, f64), mean = torch::empty({V, 3, 2}, f64);
-    Tensor workspace = torch::empty({(int64_t)(EGR_SSIM_WORKSPACE_BYTES(V, H, W) / 8)}, f64); // (freed stream-ordered by the caching allocator)
-    const int rc = egr_eval_ssim(dev.index(), (uint32_t)V, (uint32_t)H, (uint32_t)W, final.data_ptr<float>(), prgb, tf, td, ts, sum.data_ptr<double>(), mean.data_ptr<double>(),
-                                 workspace.data_ptr(), current_stream());
+    const EvalInputs a = eval_inputs("eval_ssim", final, rgb, target_final, target_diffuse, target_specular);
+    const c10::DeviceGuard guard(a.dev);
+    const auto f64 = torch::dtype(torch::kFloat64).device(a.dev);
+    Tensor sum = torch::empty({a.V, 3, 3, 2}, f64), mean = torch::empty({a.V, 3, 2}, f64);
+    Tensor workspace = torch::empty({(int64_t)(EGR_SSIM_WORKSPACE_BYTES(a.V, a.H, a.W) / 8)}, f64); // (freed stream-ordered by the caching allocator)
+    const int rc = egr_eval_ssim(a.dev.index(), (uint32_t)a.V, (uint32_t)a.H, (uint32_t)a.W, a.final, a.rgb, a.target_final, a.target_diffuse, a.target_specular, sum.data_ptr<double>(),
+                                 mean.data_ptr<double>(), workspace.data_ptr(), current_stream());
     TORCH_CHECK(rc == 0, egr_eval_last_error());
     return {sum, mean};
 }
@@ -1128,18 +1166,17 @@ static std::tuple<Tensor, Tensor> eval_ssim(const Tensor &final, const c10::opti
 // The same kernel on display images the caller already has (egr_ssim_images): pred, gt contiguous fp32 [V,3,H,W] on one GPU, used as they are. Returns
 // (ssim_sum fp64 [V,3,2], ssim fp64 [V,2]) on the device.
 static std::tuple<Tensor, Tensor> ssim_images(const Tensor &pred, const Tensor &gt) {
-    TORCH_CHECK(pred.is_cuda() && pred.scalar_type() == torch::kFloat32 && pred.is_contiguous() && pred.dim() == 4 && pred.size(1) == 3, "ssim_images: pred must be a contiguous fp32 [V,3,H,W] GPU tensor");
-    TORCH_CHECK(gt.is_cuda() && gt.device() == pred.device() && gt.scalar_type() == torch::kFloat32 && gt.is_contiguous() && gt.sizes() == pred.sizes(),
-                "ssim_images: gt must be a contiguous fp32 tensor ", pred.sizes(), " on pred's device, got ", gt.sizes());
-    const int64_t V = pred.size(0), H = pred.size(2), W = pred.size(3);
-    TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && H <= 0x7FFFFFFF && W <= 0x7FFFFFFF, "ssim_images: at least one view and one pixel are required");
-    const auto dev = pred.device();
+    const char *op = "ssim_images";
+    const c10::Device dev = gpu_of(op, "pred", pred);
     const c10::DeviceGuard guard(dev);
+    const float *p = tensor_arg<float>(op, "pred ([V,3,H,W])", pred, dev, {-1, 3, -1, -1});
+    const int64_t V = pred.size(0), H = pred.size(2), W = pred.size(3);
+    const float *g = tensor_arg<float>(op, "gt", gt, dev, {V, 3, H, W});
+    TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && H <= 0x7FFFFFFF && W <= 0x7FFFFFFF, "ssim_images: at least one view and one pixel are required");
     const auto f64 = torch::dtype(torch::kFloat64).device(dev);
     Tensor sum = torch::empty({V, 3, 2}, f64), mean = torch::empty({V, 2}, f64);
     Tensor workspace = torch::empty({(int64_t)(EGR_SSIM_WORKSPACE_BYTES(V, H, W) / 8)}, f64);
-    const int rc = egr_ssim_images(dev.index(), (uint32_t)V, (uint32_t)H, (uint32_t)W, pred.data_ptr<float>(), gt.data_ptr<float>(), sum.data_ptr<double>(), mean.data_ptr<double>(),
-                                   workspace.data_ptr(), current_stream());
+    const int rc = egr_ssim_images(dev.index(), (uint32_t)V, (uint32_t)H, (uint32_t)W, p, g, sum.data_ptr<double>(), mean.data_ptr<double>(), workspace.data_ptr(), current_stream());
     TORCH_CHECK(rc == 0, egr_eval_last_error());
     return {sum, mean};
 }
@@ -1154,6 +1191,7 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor> eval_frames(const c10::optiona
                                                               const c10::optional<Tensor> &t_final, const c10::optional<Tensor> &t_diffuse, const c10::optional<Tensor> &t_specular,
                                                               const c10::optional<Tensor> &t_depth, const c10::optional<Tensor> &t_normal, const c10::optional<Tensor> &t_roughness,
                                                               const c10::optional<Tensor> &t_f0, int64_t kinds, int64_t rounding, int64_t depth_mode, bool side_by_side) {
+    const char *op = "eval_frames";
     struct In { const c10::optional<Tensor> *t; const char *name; bool pixel_major; int64_t channels; };
     const In in[13] = {{&final, "final", true, 3}, {&rgb, "rgb", true, 3}, {&depth, "depth", true, 1}, {&normal, "normal", true, 3}, {&roughness, "roughness", true, 1}, {&f0, "f0", true, 3},
                        {&t_final, "t_final", false, 3}, {&t_diffuse, "t_diffuse", false, 3}, {&t_specular, "t_specular", false, 3}, {&t_depth, "t_depth", false, 1},
@@ -1161,7 +1199,7 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor> eval_frames(const c10::optiona
     const Tensor *first = nullptr;
     int64_t V = 0, H = 0, W = 0;
     for (int i = 0; i < 13 && !first; i++) {
-        if (!in[i].t->has_value() || !(*in[i].t)->defined()) continue;
+        if (!given(*in[i].t)) continue;
         first = &**in[i].t;
         const int64_t want_dim = i == 0 || !in[i].pixel_major ? 4 : 5;
         TORCH_CHECK(first->dim() == want_dim, "eval_frames: ", in[i].name, " must have ", want_dim, " dimensions, got ", first->sizes());
@@ -1170,18 +1208,11 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor> eval_frames(const c10::optiona
     TORCH_CHECK(first && first->is_cuda(), "eval_frames: at least one GPU tensor is required");
     TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && H <= 0x7FFFFFFF && W <= 0x7FFFFFFF, "eval_frames: at least one view and one pixel are required");
     TORCH_CHECK(kinds >= 0 && kinds <= 0xFFFFFFFFll && rounding >= 0 && rounding <= 0xFFFFFFFFll && depth_mode >= 0 && depth_mode <= 0xFFFFFFFFll, "eval_frames: kinds, rounding and depth_mode are the header's unsigned constants");
-    const auto dev = first->device();
-    const c10::DeviceGuard guard(dev); // the outputs, the workspace and current_stream() belong to the inputs' device, which need not be the current one
+    const c10::Device dev = first->device();
+    const c10::DeviceGuard guard(dev);
     const float *p[13];
-    for (int i = 0; i < 13; i++) {
-        p[i] = nullptr;
-        if (!in[i].t->has_value() || !(*in[i].t)->defined()) continue;
-        const Tensor &t = **in[i].t;
-        const std::vector<int64_t> want = i == 0 ? std::vector<int64_t>{V, H, W, 3} : in[i].pixel_major ? std::vector<int64_t>{V, EGR_NUM_STEPS, H, W, in[i].channels} : std::vector<int64_t>{V, in[i].channels, H, W};
-        TORCH_CHECK(t.is_cuda() && t.device() == dev && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.sizes() == torch::IntArrayRef(want), "eval_frames: ", in[i].name,
-                    " must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " on one GPU, got ", t.sizes());
-        p[i] = t.data_ptr<float>();
-    }
+    for (int i = 0; i < 13; i++)
+        p[i] = tensor_arg<float>(op, in[i].name, *in[i].t, dev, i == 0 ? Shape{V, H, W, 3} : in[i].pixel_major ? Shape{V, EGR_NUM_STEPS, H, W, in[i].channels} : Shape{V, in[i].channels, H, W}, false);
     const auto opt = [&](torch::ScalarType ty) { return torch::dtype(ty).device(dev); };
     Tensor frames = side_by_side ? torch::empty({V, EGR_FRAMES_KINDS, H, 2 * W, 3}, opt(torch::kUInt8)) : torch::empty({V, EGR_FRAMES_KINDS, 2, H, W, 3}, opt(torch::kUInt8));
     Tensor sse8 = torch::empty({V, EGR_FRAMES_KINDS, 3}, opt(torch::kInt64)), psnr8 = torch::empty({V, EGR_FRAMES_KINDS, 2}, opt(torch::kFloat64));
@@ -1203,61 +1234,54 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor> eval_frames(const c10::optiona
 // status int64 [8] (zeroed). voxel_accumulate adds V views in one launch: c2w fp64 [V,3,3], origin fp64 [V,3], view_size fp64 [V] (the caller's host fp64 camera
 // set-up, uploaded), depth fp32 [V,H,W], colour fp32 or uint8 [V,H,W,3] (uint8 with the 256-entry fp32 table), positions_out fp64 [V,H,W,3] or None.
 // Current stream, no host synchronisation.
-static void voxel_table_check(const char *fn, const Tensor &keys, const Tensor &acc, const Tensor &status) {
-    TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64 && keys.is_contiguous() && keys.dim() == 1, fn, ": keys must be a contiguous int64 [cap] GPU tensor");
-    TORCH_CHECK(acc.is_cuda() && acc.device() == keys.device() && acc.scalar_type() == torch::kInt64 && acc.is_contiguous() && acc.dim() == 2 && acc.size(0) == keys.size(0) && acc.size(1) == 4,
-                fn, ": acc must be a contiguous int64 [cap,4] tensor on the device of keys");
-    TORCH_CHECK(status.is_cuda() && status.device() == keys.device() && status.scalar_type() == torch::kInt64 && status.is_contiguous() && status.numel() == EGR_VOXEL_STATUS_WORDS,
-                fn, ": status must be a contiguous int64 [", EGR_VOXEL_STATUS_WORDS, "] tensor on the device of keys");
+struct VoxelTable {
+    c10::Device dev;
+    int64_t *keys, *acc, *status;
+    uint64_t cap;
+};
+static VoxelTable voxel_table(const char *op, const Tensor &keys, const Tensor &acc, const Tensor &status) {
+    TORCH_CHECK(keys.defined() && keys.is_cuda(), op, ": keys must be a contiguous int64 [cap] GPU tensor"); // (a CPU tensor is refused, not dereferenced)
+    VoxelTable t{keys.device(), nullptr, nullptr, nullptr, 0};
+    t.keys = tensor_arg<int64_t>(op, "keys ([cap])", keys, t.dev, {-1});
+    t.cap = (uint64_t)keys.size(0);
+    t.acc = tensor_arg<int64_t>(op, "acc", acc, t.dev, {keys.size(0), 4});
+    t.status = tensor_arg<int64_t>(op, "status", status, t.dev, Shape::elements(EGR_VOXEL_STATUS_WORDS));
+    return t;
 }
 static void voxel_accumulate(const Tensor &keys, const Tensor &acc, const Tensor &status, const Tensor &c2w, const Tensor &origin, const Tensor &view_size, const Tensor &depth,
                              const Tensor &colour, const c10::optional<Tensor> &colour_table, double voxel_scale, double colour_max, const c10::optional<Tensor> &positions_out) {
-    voxel_table_check("voxel_accumulate", keys, acc, status);
-    const auto dev = keys.device();
+    const char *op = "voxel_accumulate";
+    const VoxelTable T = voxel_table(op, keys, acc, status);
+    const c10::Device dev = T.dev;
     const c10::DeviceGuard guard(dev);
-    TORCH_CHECK(depth.is_cuda() && depth.device() == dev && depth.scalar_type() == torch::kFloat32 && depth.is_contiguous() && depth.dim() == 3, "voxel_accumulate: depth must be a contiguous fp32 [V,H,W] tensor on the table's device");
+    const float *pdepth = tensor_arg<float>(op, "depth ([V,H,W])", depth, dev, {-1, -1, -1});
     const int64_t V = depth.size(0), H = depth.size(1), W = depth.size(2);
     TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && V <= 65535 && H <= (1 << 20) && W <= (1 << 20), "voxel_accumulate: at least one view and one pixel are required");
-    auto f64 = [&](const Tensor &t, std::vector<int64_t> want, const char *what) -> const double * {
-        TORCH_CHECK(t.is_cuda() && t.device() == dev && t.scalar_type() == torch::kFloat64 && t.is_contiguous() && t.sizes() == torch::IntArrayRef(want), "voxel_accumulate: ", what,
-                    " must be a contiguous fp64 tensor ", torch::IntArrayRef(want), " on the table's device, got ", t.sizes());
-        return t.data_ptr<double>();
-    };
-    const double *pc2w = f64(c2w, {V, 3, 3}, "c2w"), *porigin = f64(origin, {V, 3}, "origin"), *pview = f64(view_size, {V}, "view_size");
-    const bool u8 = colour.scalar_type() == torch::kUInt8;
-    TORCH_CHECK(colour.is_cuda() && colour.device() == dev && (u8 || colour.scalar_type() == torch::kFloat32) && colour.is_contiguous() && colour.sizes() == torch::IntArrayRef({V, H, W, 3}),
-                "voxel_accumulate: colour must be a contiguous fp32 or uint8 [V,H,W,3] tensor on the table's device");
-    const float *table = nullptr;
-    if (u8) {
-        TORCH_CHECK(colour_table.has_value() && colour_table->defined() && colour_table->is_cuda() && colour_table->device() == dev && colour_table->scalar_type() == torch::kFloat32 &&
-                        colour_table->is_contiguous() && colour_table->numel() == 256,
-                    "voxel_accumulate: uint8 colours need colour_table, a contiguous fp32 [256] tensor on the table's device");
-        table = colour_table->data_ptr<float>();
-    }
-    double *pos = nullptr;
-    if (positions_out.has_value() && positions_out->defined()) pos = const_cast<double *>(f64(*positions_out, {V, H, W, 3}, "positions_out"));
-    const int rc = egr_voxel_accumulate(dev.index(), keys.data_ptr<int64_t>(), acc.data_ptr<int64_t>(), status.data_ptr<int64_t>(), (uint64_t)keys.size(0), (uint32_t)V, (uint32_t)H,
-                                        (uint32_t)W, pc2w, porigin, pview, depth.data_ptr<float>(), u8 ? nullptr : colour.data_ptr<float>(), u8 ? colour.data_ptr<uint8_t>() : nullptr,
-                                        table, voxel_scale, colour_max, pos, current_stream());
+    const double *pc2w = tensor_arg<double>(op, "c2w", c2w, dev, {V, 3, 3}), *porigin = tensor_arg<double>(op, "origin", origin, dev, {V, 3}), *pview = tensor_arg<double>(op, "view_size", view_size, dev, {V});
+    const bool u8 = colour.defined() && colour.scalar_type() == torch::kUInt8;
+    const uint8_t *colour8 = u8 ? tensor_arg<uint8_t>(op, "colour", colour, dev, {V, H, W, 3}) : nullptr;
+    const float *colour32 = u8 ? nullptr : tensor_arg<float>(op, "colour (fp32 or uint8)", colour, dev, {V, H, W, 3});
+    const float *table = u8 ? tensor_arg<float>(op, "colour_table (uint8 colours need it)", colour_table, dev, Shape::elements(256)) : nullptr;
+    double *pos = tensor_arg<double>(op, "positions_out", positions_out, dev, {V, H, W, 3}, false);
+    const int rc = egr_voxel_accumulate(dev.index(), T.keys, T.acc, T.status, T.cap, (uint32_t)V, (uint32_t)H, (uint32_t)W, pc2w, porigin, pview, pdepth, colour32, colour8, table, voxel_scale,
+                                        colour_max, pos, current_stream());
     TORCH_CHECK(rc == 0, egr_voxel_last_error());
 }
 // Growth: every occupied slot of (src_keys, src_acc) is inserted into the initialised table (keys, acc); the slots it claims are added to status[0].
 static void voxel_rehash(const Tensor &keys, const Tensor &acc, const Tensor &status, const Tensor &src_keys, const Tensor &src_acc) {
-    voxel_table_check("voxel_rehash", keys, acc, status);
-    voxel_table_check("voxel_rehash", src_keys, src_acc, status);
-    TORCH_CHECK(src_keys.device() == keys.device(), "voxel_rehash: both tables must be on one device");
-    const c10::DeviceGuard guard(keys.device());
-    const int rc = egr_voxel_rehash(keys.device().index(), keys.data_ptr<int64_t>(), acc.data_ptr<int64_t>(), status.data_ptr<int64_t>(), (uint64_t)keys.size(0), src_keys.data_ptr<int64_t>(),
-                                    src_acc.data_ptr<int64_t>(), (uint64_t)src_keys.size(0), current_stream());
+    const VoxelTable T = voxel_table("voxel_rehash", keys, acc, status), S = voxel_table("voxel_rehash", src_keys, src_acc, status);
+    TORCH_CHECK(S.dev == T.dev, "voxel_rehash: both tables must be on one device");
+    const c10::DeviceGuard guard(T.dev);
+    const int rc = egr_voxel_rehash(T.dev.index(), T.keys, T.acc, T.status, T.cap, S.keys, S.acc, S.cap, current_stream());
     TORCH_CHECK(rc == 0, egr_voxel_last_error());
 }
 // The voxels with count >= min_count in the order of torch.unique(dim=0): (coords int32 [n,3], points fp32 [n,3], colors fp32 [n,3], counts int32 [n], the largest
 // count of the table). max_rows bounds n (the table's occupied slots always do). ONE host synchronisation: the read-back of n.
 static std::tuple<Tensor, Tensor, Tensor, Tensor, int64_t> voxel_extract(const Tensor &keys, const Tensor &acc, const Tensor &status, int64_t min_count, double voxel_scale, int64_t max_rows) {
-    voxel_table_check("voxel_extract", keys, acc, status);
+    const VoxelTable T = voxel_table("voxel_extract", keys, acc, status);
     TORCH_CHECK(min_count >= 0 && min_count <= 0xFFFFFFFFll, "voxel_extract: min_count must be in 0..2^32-1");
-    TORCH_CHECK(max_rows >= 1 && max_rows <= keys.size(0), "voxel_extract: max_rows must be in 1..cap");
-    const auto dev = keys.device();
+    TORCH_CHECK(max_rows >= 1 && max_rows <= (int64_t)T.cap, "voxel_extract: max_rows must be in 1..cap");
+    const c10::Device dev = T.dev;
     const c10::DeviceGuard guard(dev);
     const auto i32 = torch::dtype(torch::kInt32).device(dev), f32 = torch::dtype(torch::kFloat32).device(dev);
     Tensor coords = torch::empty({max_rows, 3}, i32), points = torch::empty({max_rows, 3}, f32), colors = torch::empty({max_rows, 3}, f32), counts = torch::empty({max_rows}, i32);
@@ -1265,9 +1289,8 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor, int64_t> voxel_extract(const T
     TORCH_CHECK(bytes != 0, egr_voxel_last_error());
     Tensor workspace = torch::empty({(int64_t)((bytes + 15) / 16) * 2}, torch::dtype(torch::kInt64).device(dev)); // (the caching allocator aligns to 512 bytes)
     uint64_t host[2] = {0, 0};
-    const int rc = egr_voxel_extract(dev.index(), keys.data_ptr<int64_t>(), acc.data_ptr<int64_t>(), status.data_ptr<int64_t>(), (uint64_t)keys.size(0), (uint32_t)min_count, voxel_scale,
-                                     (uint64_t)max_rows, coords.data_ptr<int32_t>(), points.data_ptr<float>(), colors.data_ptr<float>(), counts.data_ptr<int32_t>(), host,
-                                     workspace.data_ptr(), (size_t)workspace.numel() * 8, current_stream());
+    const int rc = egr_voxel_extract(dev.index(), T.keys, T.acc, T.status, T.cap, (uint32_t)min_count, voxel_scale, (uint64_t)max_rows, coords.data_ptr<int32_t>(), points.data_ptr<float>(),
+                                     colors.data_ptr<float>(), counts.data_ptr<int32_t>(), host, workspace.data_ptr(), (size_t)workspace.numel() * 8, current_stream());
     TORCH_CHECK(rc == 0, egr_voxel_last_error());
     const int64_t n = (int64_t)host[0];
     return {coords.narrow(0, 0, n), points.narrow(0, 0, n), colors.narrow(0, 0, n), counts.narrow(0, 0, n), (int64_t)host[1]};
@@ -1278,45 +1301,34 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor, int64_t> voxel_extract(const T
 // table of a uint8 source, None for fp32; planes[kind]: the store's contiguous half [slots,C,H,W]; depth_range: contiguous fp32 [slots,2]. One entry per kind each.
 static void viewset_ingest(const c10::List<c10::optional<Tensor>> &sources, const c10::List<c10::optional<Tensor>> &tables, std::vector<Tensor> planes, const Tensor &depth_range,
                            int64_t first_slot) {
+    const char *op = "viewset_ingest";
     TORCH_CHECK(sources.size() == EGR_VIEWSET_KINDS && tables.size() == EGR_VIEWSET_KINDS && planes.size() == EGR_VIEWSET_KINDS,
                 "viewset_ingest: sources, tables and planes must have one entry per kind (", EGR_VIEWSET_KINDS, ")");
-    TORCH_CHECK(depth_range.is_cuda() && depth_range.scalar_type() == torch::kFloat32 && depth_range.is_contiguous() && depth_range.dim() == 2 && depth_range.size(1) == 2,
-                "viewset_ingest: depth_range must be a contiguous fp32 [slots,2] GPU tensor");
-    const c10::Device dev = depth_range.device();
+    const c10::Device dev = gpu_of(op, "depth_range", depth_range);
     const c10::DeviceGuard guard(dev);
+    float *range = tensor_arg<float>(op, "depth_range ([slots,2])", depth_range, dev, {-1, 2});
     const int64_t slots = depth_range.size(0);
     TORCH_CHECK(first_slot >= 0 && first_slot <= slots, "viewset_ingest: first_slot must be in 0..slots, got ", first_slot);
     egr_viewset_source table[EGR_VIEWSET_KINDS] = {};
-    int64_t V = -1, Hs = 0, Ws = 0, H = -1, W = -1;
+    int64_t V = -1, Hs = -1, Ws = -1, H = -1, W = -1; // (-1: any, until the first tensor that has it fixes it for the rest)
     for (size_t k = 0; k < EGR_VIEWSET_KINDS; k++) {
-        const Tensor &p = planes[k];
+        const std::string at = "[" + std::to_string(k) + "]";
         const int64_t C = (k == EGR_VIEWSET_DEPTH || k == 5) ? 1 : 3;
-        TORCH_CHECK(p.is_cuda() && p.device() == dev && p.scalar_type() == torch::kFloat16 && p.is_contiguous() && p.dim() == 4 && p.size(0) == slots && p.size(1) == C,
-                    "viewset_ingest: planes[", k, "] must be a contiguous half [", slots, ",", C, ",H,W] tensor on the store's device, got ", p.sizes());
-        if (H < 0) H = p.size(2), W = p.size(3);
-        TORCH_CHECK(p.size(2) == H && p.size(3) == W, "viewset_ingest: the planes of every kind must share one image size");
-        const c10::optional<Tensor> s = sources.get(k), t = tables.get(k);
-        const bool has_table = t.has_value() && t->defined();
-        if (has_table) {
-            TORCH_CHECK(t->is_cuda() && t->device() == dev && t->scalar_type() == torch::kFloat16 && t->is_contiguous() && t->numel() == 256,
-                        "viewset_ingest: tables[", k, "] must be a contiguous half [256] tensor on the store's device");
-            table[k].table = t->data_ptr();
-        }
-        if (!(s.has_value() && s->defined())) {
-            table[k].table = nullptr; // (the table of an absent kind is ignored)
-            continue;
-        }
-        TORCH_CHECK(s->is_cuda() && s->device() == dev && s->is_contiguous() && s->dim() == 4 && (s->scalar_type() == torch::kUInt8 || s->scalar_type() == torch::kFloat32),
-                    "viewset_ingest: sources[", k, "] must be a contiguous uint8 or fp32 [V,Hs,Ws,Cs] tensor on the store's device");
-        if (V < 0) V = s->size(0), Hs = s->size(1), Ws = s->size(2);
-        TORCH_CHECK(s->size(0) == V && s->size(1) == Hs && s->size(2) == Ws, "viewset_ingest: the sources of one call must share [V,Hs,Ws] (sources[", k, "] is ", s->sizes(), ")");
-        table[k].data = s->data_ptr(), table[k].planes = p.data_ptr(), table[k].channels = (uint32_t)s->size(3);
-        table[k].dtype = s->scalar_type() == torch::kUInt8 ? EGR_VIEWSET_U8 : EGR_VIEWSET_F32;
+        void *store = tensor_arg<at::Half>(op, "planes" + at + " (the planes of every kind share one image size)", planes[k], dev, {slots, C, H, W});
+        H = planes[k].size(2), W = planes[k].size(3);
+        const c10::optional<Tensor> s = sources.get(k);
+        const void *lookup = tensor_arg<at::Half>(op, "tables" + at, tables.get(k), dev, Shape::elements(256), false);
+        if (!given(s)) continue; // (the table of an absent kind is ignored)
+        const bool u8 = s->scalar_type() == torch::kUInt8;
+        const std::string name = "sources" + at + " (uint8 or fp32; the sources of one call share [V,Hs,Ws])";
+        table[k].data = u8 ? (const void *)tensor_arg<uint8_t>(op, name, s, dev, {V, Hs, Ws, -1}) : (const void *)tensor_arg<float>(op, name, s, dev, {V, Hs, Ws, -1});
+        V = s->size(0), Hs = s->size(1), Ws = s->size(2);
+        table[k].table = lookup, table[k].planes = store, table[k].channels = (uint32_t)s->size(3);
+        table[k].dtype = u8 ? EGR_VIEWSET_U8 : EGR_VIEWSET_F32;
     }
     TORCH_CHECK(V >= 1, "viewset_ingest: at least one kind with at least one view is required");
     TORCH_CHECK(Hs > 0 && Ws > 0 && H > 0 && W > 0 && std::max(std::max(V, Hs), std::max(std::max(Ws, H), W)) <= 65535, "viewset_ingest: V and the image sizes must be in 1..65535");
-    const int rc = egr_viewset_ingest(dev.index(), table, (uint32_t)V, (uint32_t)Hs, (uint32_t)Ws, (uint32_t)H, (uint32_t)W, (uint32_t)first_slot, (uint32_t)slots,
-                                      depth_range.data_ptr<float>(), current_stream());
+    const int rc = egr_viewset_ingest(dev.index(), table, (uint32_t)V, (uint32_t)Hs, (uint32_t)Ws, (uint32_t)H, (uint32_t)W, (uint32_t)first_slot, (uint32_t)slots, range, current_stream());
     TORCH_CHECK(rc == 0, egr_viewset_last_error());
 }
 // The training views in fp16, part 2 (egr_viewset_gather): rows v < len(indices) of the fp32 outputs = the stored views indices[v], exactly float(half), and their
@@ -1325,37 +1337,27 @@ static void viewset_ingest(const c10::List<c10::optional<Tensor>> &sources, cons
 // out_R / out_centers / out_fovy: contiguous fp32 with >= V rows. Only the first V rows of an output are written.
 static void viewset_gather(std::vector<Tensor> planes, const Tensor &R, const Tensor &centers, const Tensor &fovy, int64_t num_filled, std::vector<int64_t> indices,
                            const c10::List<c10::optional<Tensor>> &out, const Tensor &out_R, const Tensor &out_centers, const Tensor &out_fovy) {
+    const char *op = "viewset_gather";
     TORCH_CHECK(planes.size() == EGR_VIEWSET_KINDS && out.size() == EGR_VIEWSET_KINDS, "viewset_gather: planes and out must have one entry per kind (", EGR_VIEWSET_KINDS, ")");
     const int64_t V = (int64_t)indices.size();
     TORCH_CHECK(V >= 1, "viewset_gather: at least one index is required");
-    TORCH_CHECK(fovy.is_cuda() && fovy.dim() == 1, "viewset_gather: fovy must be an fp32 [slots] GPU tensor");
-    const c10::Device dev = fovy.device();
+    const c10::Device dev = gpu_of(op, "fovy", fovy);
     const c10::DeviceGuard guard(dev);
-    const int64_t slots = fovy.size(0);
-    TORCH_CHECK(num_filled >= 0 && num_filled <= slots, "viewset_gather: num_filled must be in 0..slots");
-    auto f32 = [&](const Tensor &t, std::vector<int64_t> tail, int64_t rows, bool exact, const char *what) {
-        bool ok = t.is_cuda() && t.device() == dev && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.dim() == (int64_t)tail.size() + 1 &&
-                  (exact ? t.size(0) == rows : t.size(0) >= rows);
-        for (size_t d = 0; ok && d < tail.size(); d++) ok = t.size((int64_t)d + 1) == tail[d];
-        TORCH_CHECK(ok, "viewset_gather: ", what, " must be a contiguous fp32 tensor with ", exact ? "" : "at least ", rows, " rows of ", c10::IntArrayRef(tail), " on the store's device, got ",
-                    t.sizes());
-        return t.data_ptr<float>();
-    };
     egr_viewset_store store = {};
     egr_viewset_batch batch = {};
-    store.R = f32(R, {3, 3}, slots, true, "R"), store.centers = f32(centers, {3}, slots, true, "centers"), store.fovy = f32(fovy, {}, slots, true, "fovy");
-    batch.R = f32(out_R, {3, 3}, V, false, "out_R"), batch.centers = f32(out_centers, {3}, V, false, "out_centers"), batch.fovy = f32(out_fovy, {}, V, false, "out_fovy");
-    int64_t H = -1, W = -1;
+    store.fovy = tensor_arg<float>(op, "fovy ([slots])", fovy, dev, {-1});
+    const int64_t slots = fovy.size(0);
+    TORCH_CHECK(num_filled >= 0 && num_filled <= slots, "viewset_gather: num_filled must be in 0..slots");
+    store.R = tensor_arg<float>(op, "R", R, dev, {slots, 3, 3}), store.centers = tensor_arg<float>(op, "centers", centers, dev, {slots, 3});
+    batch.R = tensor_arg<float>(op, "out_R", out_R, dev, Shape::at_least(V, {3, 3})), batch.centers = tensor_arg<float>(op, "out_centers", out_centers, dev, Shape::at_least(V, {3}));
+    batch.fovy = tensor_arg<float>(op, "out_fovy", out_fovy, dev, Shape::at_least(V, {}));
+    int64_t H = -1, W = -1; // (-1: any, until the first kind fixes it for the rest)
     for (size_t k = 0; k < EGR_VIEWSET_KINDS; k++) {
-        const Tensor &p = planes[k];
+        const std::string at = "[" + std::to_string(k) + "]";
         const int64_t C = (k == EGR_VIEWSET_DEPTH || k == 5) ? 1 : 3;
-        TORCH_CHECK(p.is_cuda() && p.device() == dev && p.scalar_type() == torch::kFloat16 && p.is_contiguous() && p.dim() == 4 && p.size(0) == slots && p.size(1) == C,
-                    "viewset_gather: planes[", k, "] must be a contiguous half [", slots, ",", C, ",H,W] tensor on the store's device, got ", p.sizes());
-        if (H < 0) H = p.size(2), W = p.size(3);
-        TORCH_CHECK(p.size(2) == H && p.size(3) == W, "viewset_gather: the planes of every kind must share one image size");
-        store.planes[k] = p.data_ptr();
-        const c10::optional<Tensor> o = out.get(k);
-        if (o.has_value() && o->defined()) batch.targets[k] = f32(*o, {C, H, W}, V, false, "out[kind]");
+        store.planes[k] = tensor_arg<at::Half>(op, "planes" + at + " (the planes of every kind share one image size)", planes[k], dev, {slots, C, H, W});
+        H = planes[k].size(2), W = planes[k].size(3);
+        batch.targets[k] = tensor_arg<float>(op, "out" + at, out.get(k), dev, Shape::at_least(V, {C, H, W}), false);
     }
     TORCH_CHECK(H > 0 && W > 0 && H <= 65535 && W <= 65535 && slots <= 0xFFFFFFFFll, "viewset_gather: image sizes must be in 1..65535");
     store.num_slots = (uint32_t)slots, store.num_filled = (uint32_t)num_filled, store.height = (uint32_t)H, store.width = (uint32_t)W;
@@ -1369,8 +1371,9 @@ static void viewset_gather(std::vector<Tensor> planes, const Tensor &R, const Te
 }
 
 // unit-test hook (egr_debug_lean_arith): (a / b, sqrt(a)) as the hot kernels' division and square root compute them
-static std::tuple<torch::Tensor, torch::Tensor> debug_lean_arith(const torch::Tensor &a, const torch::Tensor &b) {
-    TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.numel() == b.numel(), "debug_lean_arith: two GPU tensors of one size expected");
+static std::tuple<Tensor, Tensor> debug_lean_arith(const Tensor &a, const Tensor &b) {
+    TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.device() == b.device() && a.numel() == b.numel(), "debug_lean_arith: two tensors of one size on one GPU expected");
+    const c10::DeviceGuard guard(a.device());
     auto x = a.to(torch::kFloat32).contiguous(), y = b.to(torch::kFloat32).contiguous();
     auto q = torch::zeros_like(x), r = torch::zeros_like(x);
     TORCH_CHECK(egr_debug_lean_arith(x.get_device(), x.data_ptr<float>(), y.data_ptr<float>(), q.data_ptr<float>(), r.data_ptr<float>(), (uint32_t)x.numel(), current_stream()) == 0, "debug_lean_arith failed");

@@ -16,6 +16,7 @@
 #include <string>
 
 #include "../../include/egr_raytracer.h"
+#include "egr_host.hpp"
 
 namespace {
 
@@ -274,22 +275,6 @@ __global__ void __launch_bounds__(VS_THREADS) k_viewset_gather(GatherArgs a) {
 
 thread_local std::string g_viewset_error;
 
-int fail(const char *fn, const std::string &what) {
-    g_viewset_error = std::string("libegr_hip: ") + fn + ": " + what;
-    return 1;
-}
-
-struct Range {
-    const void *p;
-    size_t bytes;
-};
-
-// (an empty range touches nothing)
-bool overlap(const Range &a, const Range &b) {
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a.bytes != 0 && b.bytes != 0 && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
 const char *const KIND_NAMES[EGR_VIEWSET_KINDS] = {"render", "diffuse", "specular", "depth", "normal", "roughness", "f0"};
 
 } // namespace
@@ -300,113 +285,97 @@ extern "C" int egr_viewset_ingest(int device, const egr_viewset_source *sources,
                                   uint32_t width, uint32_t first_slot, uint32_t num_slots, float *depth_range, void *hip_stream) {
     const char *fn = "egr_viewset_ingest";
     // ---- validation: before any HIP call
-    if (!sources) return fail(fn, "the table of sources is required");
-    if (!depth_range) return fail(fn, "depth_range is a required output");
-    if (num_views == 0 || num_views > VS_MAX_SIDE) return fail(fn, "num_views must be in 1..65535 per call");
+    if (!sources) return egr_fail(g_viewset_error, fn, "the table of sources is required");
+    if (!depth_range) return egr_fail(g_viewset_error, fn, "depth_range is a required output");
+    if (num_views == 0 || num_views > VS_MAX_SIDE) return egr_fail(g_viewset_error, fn, "num_views must be in 1..65535 per call");
     if (src_height == 0 || src_width == 0 || height == 0 || width == 0 || src_height > VS_MAX_SIDE || src_width > VS_MAX_SIDE || height > VS_MAX_SIDE || width > VS_MAX_SIDE)
-        return fail(fn, "image sizes must be in 1..65535");
+        return egr_fail(g_viewset_error, fn, "image sizes must be in 1..65535");
     if (src_height != height) {
         const uint32_t want = (uint32_t)((double)height * ((double)src_width / (double)src_height)); // _resize_image_tensor's int(resolution * aspect_ratio)
-        if (width != want) return fail(fn, "size mismatch: a resized source must give the store's width, int(height * (src_width / src_height)) = " + std::to_string(want));
+        if (width != want) return egr_fail(g_viewset_error, fn, "size mismatch: a resized source must give the store's width, int(height * (src_width / src_height)) = " + std::to_string(want));
         const uint64_t wh = (src_height + height - 1) / height + 1, ww = (src_width + width - 1) / width + 1;
-        if (wh * ww > VS_MAX_WINDOW) return fail(fn, "an averaging window of more than 2^24 elements");
+        if (wh * ww > VS_MAX_WINDOW) return egr_fail(g_viewset_error, fn, "an averaging window of more than 2^24 elements");
     } else if (src_width != width) {
-        return fail(fn, "size mismatch: a source of the store's height must have the store's width");
+        return egr_fail(g_viewset_error, fn, "size mismatch: a source of the store's height must have the store's width");
     }
-    if ((uint64_t)first_slot + num_views > num_slots) return fail(fn, "first_slot + num_views exceeds num_slots");
+    if ((uint64_t)first_slot + num_views > num_slots) return egr_fail(g_viewset_error, fn, "first_slot + num_views exceeds num_slots");
     IngestArgs a{};
-    Range in[2 * EGR_VIEWSET_KINDS], out[EGR_VIEWSET_KINDS + 1];
+    EgrRange in[2 * EGR_VIEWSET_KINDS], out[EGR_VIEWSET_KINDS + 1];
     int nin = 0, nout = 0;
     const size_t HW = (size_t)height * width, HWs = (size_t)src_height * src_width;
     for (uint32_t k = 0; k < EGR_VIEWSET_KINDS; k++) {
         const egr_viewset_source &S = sources[k];
         if (!S.data) continue;
         const std::string name = KIND_NAMES[k];
-        if (S.channels != 1 && S.channels != 3) return fail(fn, name + ": channels must be 1 or 3");
-        if (S.channels == 1 && kind_channels(k) == 3) return fail(fn, name + ": a colour kind needs 3 channels");
-        if (S.dtype != EGR_VIEWSET_U8 && S.dtype != EGR_VIEWSET_F32) return fail(fn, name + ": unknown dtype (EGR_VIEWSET_U8 or EGR_VIEWSET_F32)");
-        if (S.dtype == EGR_VIEWSET_U8 && k == EGR_VIEWSET_DEPTH) return fail(fn, "uint8 depth is refused (the reference asserts the same)");
-        if (S.dtype == EGR_VIEWSET_U8 && !S.table) return fail(fn, name + ": a uint8 source needs its table of 256 halfs");
-        if (S.dtype == EGR_VIEWSET_F32 && S.table) return fail(fn, name + ": a table was given for an fp32 source");
-        if (!S.planes) return fail(fn, name + ": present data without planes");
-        if (S.dtype == EGR_VIEWSET_F32 && ((uintptr_t)S.data & 3u)) return fail(fn, name + ": an fp32 source must be 4-byte aligned");
-        if (((uintptr_t)S.planes & 1u) || (S.table && ((uintptr_t)S.table & 1u))) return fail(fn, name + ": planes and table must be 2-byte aligned");
-        in[nin++] = Range{S.data, (size_t)num_views * HWs * S.channels * (S.dtype == EGR_VIEWSET_U8 ? 1 : 4)};
-        if (S.table) in[nin++] = Range{S.table, 512};
-        out[nout++] = Range{(const uint16_t *)S.planes + (size_t)first_slot * kind_channels(k) * HW, (size_t)num_views * kind_channels(k) * HW * 2};
+        if (S.channels != 1 && S.channels != 3) return egr_fail(g_viewset_error, fn, name + ": channels must be 1 or 3");
+        if (S.channels == 1 && kind_channels(k) == 3) return egr_fail(g_viewset_error, fn, name + ": a colour kind needs 3 channels");
+        if (S.dtype != EGR_VIEWSET_U8 && S.dtype != EGR_VIEWSET_F32) return egr_fail(g_viewset_error, fn, name + ": unknown dtype (EGR_VIEWSET_U8 or EGR_VIEWSET_F32)");
+        if (S.dtype == EGR_VIEWSET_U8 && k == EGR_VIEWSET_DEPTH) return egr_fail(g_viewset_error, fn, "uint8 depth is refused (the reference asserts the same)");
+        if (S.dtype == EGR_VIEWSET_U8 && !S.table) return egr_fail(g_viewset_error, fn, name + ": a uint8 source needs its table of 256 halfs");
+        if (S.dtype == EGR_VIEWSET_F32 && S.table) return egr_fail(g_viewset_error, fn, name + ": a table was given for an fp32 source");
+        if (!S.planes) return egr_fail(g_viewset_error, fn, name + ": present data without planes");
+        if (S.dtype == EGR_VIEWSET_F32 && ((uintptr_t)S.data & 3u)) return egr_fail(g_viewset_error, fn, name + ": an fp32 source must be 4-byte aligned");
+        if (((uintptr_t)S.planes & 1u) || (S.table && ((uintptr_t)S.table & 1u))) return egr_fail(g_viewset_error, fn, name + ": planes and table must be 2-byte aligned");
+        in[nin++] = EgrRange{S.data, (size_t)num_views * HWs * S.channels * (S.dtype == EGR_VIEWSET_U8 ? 1 : 4)};
+        if (S.table) in[nin++] = EgrRange{S.table, 512};
+        out[nout++] = EgrRange{(const uint16_t *)S.planes + (size_t)first_slot * kind_channels(k) * HW, (size_t)num_views * kind_channels(k) * HW * 2};
         a.s[k] = S;
     }
-    if (nout == 0) return fail(fn, "every kind is absent");
-    out[nout++] = Range{depth_range + (size_t)first_slot * 2, (size_t)num_views * 8};
-    for (int i = 0; i < nout; i++) {
-        for (int j = 0; j < nin; j++)
-            if (overlap(out[i], in[j])) return fail(fn, "an output (planes or depth_range rows) overlaps an input (data or table)");
-        for (int j = i + 1; j < nout; j++)
-            if (overlap(out[i], out[j])) return fail(fn, "two outputs overlap");
-    }
+    if (nout == 0) return egr_fail(g_viewset_error, fn, "every kind is absent");
+    out[nout++] = EgrRange{depth_range + (size_t)first_slot * 2, (size_t)num_views * 8};
+    if (const EgrClash clash = egr_find_clash(out, nout, in, nin))
+        return egr_fail(g_viewset_error, fn, clash.kind == EGR_CLASH_INPUT ? "an output (planes or depth_range rows) overlaps an input (data or table)" : "two outputs overlap");
     a.V = num_views, a.Hs = src_height, a.Ws = src_width, a.H = height, a.W = width, a.first_slot = first_slot, a.range = depth_range;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess && a.s[EGR_VIEWSET_DEPTH].data) {
-        hipLaunchKernelGGL(k_viewset_range_init, dim3((2 * num_views + 63) / 64), dim3(64), 0, (hipStream_t)hip_stream, depth_range, first_slot, num_views);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
+    hipStream_t s = (hipStream_t)hip_stream;
+    return egr_on_device(device, g_viewset_error, fn, [&] {
+        if (a.s[EGR_VIEWSET_DEPTH].data) egr_launch(k_viewset_range_init, dim3((2 * num_views + 63) / 64), dim3(64), s, depth_range, first_slot, num_views);
         const size_t quads = (HW + VS_QUAD - 1) / VS_QUAD;
-        hipLaunchKernelGGL(k_viewset_ingest, dim3((uint32_t)((quads + VS_THREADS - 1) / VS_THREADS), EGR_VIEWSET_KINDS, num_views), dim3(VS_THREADS), 0, (hipStream_t)hip_stream, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail(fn, hipGetErrorString(e));
-    return 0;
+        egr_launch(k_viewset_ingest, dim3((uint32_t)((quads + VS_THREADS - 1) / VS_THREADS), EGR_VIEWSET_KINDS, num_views), dim3(VS_THREADS), s, a);
+    });
 }
 
 extern "C" int egr_viewset_gather(int device, const egr_viewset_store *store, const uint32_t *indices, uint32_t num_views, const egr_viewset_batch *out,
                                   void *hip_stream) {
     const char *fn = "egr_viewset_gather";
     // ---- validation: before any HIP call
-    if (!store || !out || !indices) return fail(fn, "store, indices and out are required");
-    if (num_views == 0) return fail(fn, "num_views is 0");
-    if (store->height == 0 || store->width == 0 || store->height > VS_MAX_SIDE || store->width > VS_MAX_SIDE) return fail(fn, "image sizes must be in 1..65535");
-    if (store->num_filled > store->num_slots) return fail(fn, "num_filled exceeds num_slots");
+    if (!store || !out || !indices) return egr_fail(g_viewset_error, fn, "store, indices and out are required");
+    if (num_views == 0) return egr_fail(g_viewset_error, fn, "num_views is 0");
+    if (store->height == 0 || store->width == 0 || store->height > VS_MAX_SIDE || store->width > VS_MAX_SIDE) return egr_fail(g_viewset_error, fn, "image sizes must be in 1..65535");
+    if (store->num_filled > store->num_slots) return egr_fail(g_viewset_error, fn, "num_filled exceeds num_slots");
     for (uint32_t v = 0; v < num_views; v++)
-        if (indices[v] >= store->num_filled) return fail(fn, "index " + std::to_string(indices[v]) + " (entry " + std::to_string(v) + ") is out of range: " + std::to_string(store->num_filled) + " slots are filled");
+        if (indices[v] >= store->num_filled) return egr_fail(g_viewset_error, fn, "index " + std::to_string(indices[v]) + " (entry " + std::to_string(v) + ") is out of range: " + std::to_string(store->num_filled) + " slots are filled");
     const size_t HW = (size_t)store->height * store->width;
-    Range in[EGR_VIEWSET_KINDS + 3], o[EGR_VIEWSET_KINDS + 3];
+    EgrRange in[EGR_VIEWSET_KINDS + 3], o[EGR_VIEWSET_KINDS + 3];
     int nin = 0, nout = 0;
     uint32_t cmax = 0;
     for (uint32_t k = 0; k < EGR_VIEWSET_KINDS; k++) {
         if (!out->targets[k]) continue;
-        if (!store->planes[k]) return fail(fn, std::string(KIND_NAMES[k]) + ": wanted, but the store has no planes of it");
-        if (((uintptr_t)out->targets[k] & 3u) || ((uintptr_t)store->planes[k] & 1u)) return fail(fn, std::string(KIND_NAMES[k]) + ": misaligned planes or output");
-        in[nin++] = Range{store->planes[k], (size_t)store->num_slots * kind_channels(k) * HW * 2};
-        o[nout++] = Range{out->targets[k], (size_t)num_views * kind_channels(k) * HW * 4};
+        if (!store->planes[k]) return egr_fail(g_viewset_error, fn, std::string(KIND_NAMES[k]) + ": wanted, but the store has no planes of it");
+        if (((uintptr_t)out->targets[k] & 3u) || ((uintptr_t)store->planes[k] & 1u)) return egr_fail(g_viewset_error, fn, std::string(KIND_NAMES[k]) + ": misaligned planes or output");
+        in[nin++] = EgrRange{store->planes[k], (size_t)store->num_slots * kind_channels(k) * HW * 2};
+        o[nout++] = EgrRange{out->targets[k], (size_t)num_views * kind_channels(k) * HW * 4};
         cmax = cmax > kind_channels(k) ? cmax : kind_channels(k);
     }
     const struct { float *dst; const float *src; uint32_t width; const char *name; } rows[3] = {{out->R, store->R, 9, "R"}, {out->centers, store->centers, 3, "centers"}, {out->fovy, store->fovy, 1, "fovy"}};
     for (const auto &r : rows) {
         if (!r.dst) continue;
-        if (!r.src) return fail(fn, std::string(r.name) + ": wanted, but the store has no such array");
-        if (((uintptr_t)r.dst & 3u) || ((uintptr_t)r.src & 3u)) return fail(fn, std::string(r.name) + ": misaligned array");
-        in[nin++] = Range{r.src, (size_t)store->num_slots * r.width * 4};
-        o[nout++] = Range{r.dst, (size_t)num_views * r.width * 4};
+        if (!r.src) return egr_fail(g_viewset_error, fn, std::string(r.name) + ": wanted, but the store has no such array");
+        if (((uintptr_t)r.dst & 3u) || ((uintptr_t)r.src & 3u)) return egr_fail(g_viewset_error, fn, std::string(r.name) + ": misaligned array");
+        in[nin++] = EgrRange{r.src, (size_t)store->num_slots * r.width * 4};
+        o[nout++] = EgrRange{r.dst, (size_t)num_views * r.width * 4};
     }
-    if (nout == 0) return fail(fn, "nothing is wanted: every output is NULL");
-    for (int i = 0; i < nout; i++) {
-        for (int j = 0; j < nin; j++)
-            if (overlap(o[i], in[j])) return fail(fn, "an output overlaps the store (an input)");
-        for (int j = i + 1; j < nout; j++)
-            if (overlap(o[i], o[j])) return fail(fn, "two outputs overlap");
-    }
-    hipError_t e = hipSetDevice(device);
-    for (uint32_t v0 = 0; e == hipSuccess && v0 < num_views; v0 += EGR_VIEWSET_MAX_GATHER) {
-        GatherArgs a{};
-        for (uint32_t k = 0; k < EGR_VIEWSET_KINDS; k++) a.planes[k] = (const uint16_t *)store->planes[k], a.out[k] = out->targets[k];
-        a.R = store->R, a.centers = store->centers, a.fovy = store->fovy, a.out_R = out->R, a.out_centers = out->centers, a.out_fovy = out->fovy;
-        a.V = num_views - v0 < EGR_VIEWSET_MAX_GATHER ? num_views - v0 : EGR_VIEWSET_MAX_GATHER, a.first = v0, a.HW = HW;
-        for (uint32_t v = 0; v < a.V; v++) a.idx[v] = indices[v0 + v];
-        const size_t octs = cmax ? ((size_t)cmax * HW + VS_OCT - 1) / VS_OCT : 1;
-        hipLaunchKernelGGL(k_viewset_gather, dim3((uint32_t)((octs + VS_THREADS - 1) / VS_THREADS), EGR_VIEWSET_KINDS, a.V), dim3(VS_THREADS), 0, (hipStream_t)hip_stream, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail(fn, hipGetErrorString(e));
-    return 0;
+    if (nout == 0) return egr_fail(g_viewset_error, fn, "nothing is wanted: every output is NULL");
+    if (const EgrClash clash = egr_find_clash(o, nout, in, nin))
+        return egr_fail(g_viewset_error, fn, clash.kind == EGR_CLASH_INPUT ? "an output overlaps the store (an input)" : "two outputs overlap");
+    return egr_on_device(device, g_viewset_error, fn, [&] {
+        for (uint32_t v0 = 0; v0 < num_views; v0 += EGR_VIEWSET_MAX_GATHER) {
+            GatherArgs a{};
+            for (uint32_t k = 0; k < EGR_VIEWSET_KINDS; k++) a.planes[k] = (const uint16_t *)store->planes[k], a.out[k] = out->targets[k];
+            a.R = store->R, a.centers = store->centers, a.fovy = store->fovy, a.out_R = out->R, a.out_centers = out->centers, a.out_fovy = out->fovy;
+            a.V = num_views - v0 < EGR_VIEWSET_MAX_GATHER ? num_views - v0 : EGR_VIEWSET_MAX_GATHER, a.first = v0, a.HW = HW;
+            for (uint32_t v = 0; v < a.V; v++) a.idx[v] = indices[v0 + v];
+            const size_t octs = cmax ? ((size_t)cmax * HW + VS_OCT - 1) / VS_OCT : 1;
+            egr_launch(k_viewset_gather, dim3((uint32_t)((octs + VS_THREADS - 1) / VS_THREADS), EGR_VIEWSET_KINDS, a.V), dim3(VS_THREADS), (hipStream_t)hip_stream, a);
+        }
+    });
 }

@@ -393,7 +393,8 @@ int egr_debug_set_pixel_mask(egr_context *ctx, const uint8_t *device_mask);
  * are the correctly rounded ones whenever 2^-100 <= |b| <= 2^100, |a / b| is a normal number or 0, and a is 0 or a normal number >= 2^-100 for the root
  * (tests/test_hip_parity.py holds them to `/` and sqrtf bit for bit over that domain); outside it - b = 0, b = inf, a = inf, denormal radicands - they return NaN
  * or a result that is off in the last bits where IEEE gives inf / 0 / a denormal: a degenerate gaussian (all-zero quaternion, |W d| out of range) then drops out of
- * a ray's list through the NaN comparisons instead of contributing an inf. Asynchronous on the stream. */
+ * a ray's list through the NaN comparisons instead of contributing an inf. Asynchronous on the stream. Context-free (CONTEXT-FREE FUNCTIONS below), but
+ * without an error string: a test hook, it reports through its return value alone. */
 int egr_debug_lean_arith(int device, const float *a, const float *b, float *quot, float *root, uint32_t n, void *hip_stream);
 /* BVH self-check: every leaf box equals its instance box, every internal box is the union of its children,
  * every visible instance is reachable exactly once. Returns 0 if consistent. Host-side; synchronises. */
@@ -421,6 +422,17 @@ int egr_debug_get_tree(egr_context *ctx, uint64_t *keys, uint32_t *gid_of_pos, u
 
 const char *egr_last_error(egr_context *ctx);
 const char *egr_version(void);
+
+/* ---- CONTEXT-FREE FUNCTIONS: everything below (and egr_debug_lean_arith above) takes `int device, ..., void *hip_stream` and no egr_context. They share:
+ *   device      the HIP device of EVERY device pointer of the call and of hip_stream. It need not be the calling thread's current device, and the thread's
+ *               current device is the same after the call as before it, on success and on failure. (The egr_context functions keep the same promise for
+ *               their context's device.)
+ *   validation  arguments are checked BEFORE any HIP call: a refused call has touched neither the device nor the runtime, and runs on a machine without a GPU.
+ *               Where a call must be out of place, a NULL or empty range touches nothing.
+ *   errors      a non-zero return; the module's egr_<module>_last_error() then holds "libegr_hip: <function>: <why>" - the text of the failed check or the
+ *               HIP error string - per module (a failure in one never shows in another's) and per thread. The pointer is valid until the thread's next
+ *               failure in that module.
+ *   launches    asynchronous on hip_stream unless the function says that it synchronises. */
 
 /* ---- `simple_knn._C.distCUDA2` (editable_gauss_refl/scene/gaussian_model.py:17, called at :197-201 and
  * :246-250 to initialise the scales). out[i] = mean of the squared distances from point i to its 3 nearest OTHER points
