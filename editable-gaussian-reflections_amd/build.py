@@ -1,6 +1,6 @@
 """In-tree build of the two native artefacts (no cmake, no JIT cache):
 
-  libegr_hip.so    hipcc --offload-arch=gfx950   csrc/{trace,bvh,api,knn,step,denoise,prune,grow,edit,eval,ssim,frames,initcloud,viewset}.hip   the C-ABI product (include/egr_raytracer.h)
+  libegr_hip.so    hipcc --offload-arch=gfx950   csrc/{trace,bvh,api,knn,step,denoise,prune,grow,edit,eval,ssim,frames,initcloud,viewset,priors}.hip   the C-ABI product (include/egr_raytracer.h)
   libraytracer.so  g++ against the installed torch  csrc/torch_binding.cpp                 TORCH_LIBRARY(raytracer) shim
 
 The PRODUCT lives in build/. A build with any of the five build-time settings (VARIANT_SETTINGS: the diagnostic switches of csrc/egr_diag.hpp and
@@ -35,7 +35,7 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp
 # numeric constants with an #ifndef default in csrc/ - are set for a sweep through EGR_EXTRA_FLAGS="-DEGR_GPOP=4"; the alternative code paths that rounds 1-5 switched
 # between at build time are settled and gone: profiles/HISTORY.md has their measurements)
 VARIANT_SETTINGS = ("EGR_TRAVERSAL_STATS", "EGR_TASK_TIMES", "EGR_DEBUG_LIST", "EGR_DEBUG_PIXEL", "EGR_EXTRA_FLAGS")
-HIP_SOURCES = ["trace.hip", "bvh.hip", "api.hip", "knn.hip", "step.hip", "denoise.hip", "prune.hip", "grow.hip", "edit.hip", "eval.hip", "ssim.hip", "frames.hip", "initcloud.hip", "viewset.hip"]
+HIP_SOURCES = ["trace.hip", "bvh.hip", "api.hip", "knn.hip", "step.hip", "denoise.hip", "prune.hip", "grow.hip", "edit.hip", "eval.hip", "ssim.hip", "frames.hip", "initcloud.hip", "viewset.hip", "priors.hip"]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))) + [os.path.join(ROOT, "include", "egr_raytracer.h")]  # every object depends on all of them
 _POOL = ThreadPoolExecutor(8)  # compilers at once, over all builds of this process (trace.hip alone takes longer than the rest together; not sized by the CPU count)
 

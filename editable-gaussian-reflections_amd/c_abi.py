@@ -245,6 +245,56 @@ def viewset_gather(planes, R, centers, fovy, num_slots, num_filled, height, widt
     _check(L.egr_viewset_gather(device, C.byref(store), idx, len(indices), C.byref(batch), C.c_void_p(stream)), L.egr_viewset_last_error)
 
 
+# prior views (csrc/priors.hip): the arguments of egr_prior_pairs, egr_prior_fit and egr_prior_finish, field for field
+EGR_PRIOR_CAM_FLOATS, EGR_PRIOR_MAX_SAMPLE = 25, 1024
+EGR_PRIOR_RANSAC, EGR_PRIOR_LSTSQ = 0, 1
+_U32P, _I32P = C.POINTER(C.c_uint32), C.POINTER(C.c_int32)  # HOST arrays, read during the call
+egr_prior_pairs_args = _struct("egr_prior_pairs_args", [(k, C.c_uint32) for k in ("num_views", "height", "width", "depth_channels")] + [
+    ("cams", _F), ("points", _F), ("offsets", _U32P), ("offsets_dev", C.c_void_p), ("depth", _F), ("sparse", _F), ("pairs_x", _F), ("pairs_y", _F), ("count", C.c_void_p),
+    ("dropped", C.c_void_p)])
+egr_prior_fit_args = _struct("egr_prior_fit_args", [(k, C.c_uint32) for k in ("num_views", "pair_stride", "num_iters", "sample_stride", "method", "reserved")] + [
+    ("pairs_x", _F), ("pairs_y", _F), ("views", _U32P), ("views_dev", C.c_void_p), ("samples", _I32P), ("samples_dev", C.c_void_p), ("hyp_error", C.c_void_p), ("hyp_model", _F),
+    ("ab", _F), ("best_iteration", C.c_void_p), ("best_error", C.c_void_p), ("inliers", _U8)])
+egr_prior_finish_args = _struct("egr_prior_finish_args", [(k, C.c_uint32) for k in ("num_views", "height", "width", "depth_channels")] + [
+    ("cams", _F), ("ab", _F), ("depth", _F), ("normal", _F), ("metalness", _F), ("distance", _F), ("normal_out", _F), ("f0", _F)])
+
+
+def _host_array(ctype, values):
+    """A host array of `ctype` for a HOST argument, or NULL for None."""
+    if values is None:
+        return None
+    values = [int(x) for x in values]
+    return (ctype * max(len(values), 1))(*values)
+
+
+def prior_pairs(num_views, height, width, cams, points, offsets, offsets_dev, depth, sparse, pairs_x, pairs_y, count, dropped, depth_channels=1, device=0, stream=0):
+    """egr_prior_pairs on integer device addresses (include/egr_raytracer.h has the shapes; None = NULL). `offsets`: the V + 1 host integers; `offsets_dev`: the
+    address of their device copy (uint32)."""
+    L = lib()
+    a = egr_prior_pairs_args(num_views=num_views, height=height, width=width, depth_channels=depth_channels, cams=cams, points=points, offsets=_host_array(C.c_uint32, offsets),
+                             offsets_dev=offsets_dev, depth=depth, sparse=sparse, pairs_x=pairs_x, pairs_y=pairs_y, count=count, dropped=dropped)
+    _check(L.egr_prior_pairs(device, C.byref(a), C.c_void_p(stream)), L.egr_prior_last_error)
+
+
+def prior_fit(num_views, pair_stride, pairs_x, pairs_y, views, views_dev, ab, best_iteration, best_error, samples=None, samples_dev=None, num_iters=0, sample_stride=0,
+              hyp_error=None, hyp_model=None, inliers=None, method=EGR_PRIOR_RANSAC, device=0, stream=0):
+    """egr_prior_fit on integer device addresses. `views`: the flat host integers [V][4] (count, sample_size, top_k, 0); `samples`: the flat host integers
+    [V][num_iters][sample_stride]; `views_dev`, `samples_dev`: the addresses of their device copies."""
+    L = lib()
+    a = egr_prior_fit_args(num_views=num_views, pair_stride=pair_stride, num_iters=num_iters, sample_stride=sample_stride, method=method, pairs_x=pairs_x, pairs_y=pairs_y,
+                           views=_host_array(C.c_uint32, views), views_dev=views_dev, samples=_host_array(C.c_int32, samples), samples_dev=samples_dev, hyp_error=hyp_error,
+                           hyp_model=hyp_model, ab=ab, best_iteration=best_iteration, best_error=best_error, inliers=inliers)
+    _check(L.egr_prior_fit(device, C.byref(a), C.c_void_p(stream)), L.egr_prior_last_error)
+
+
+def prior_finish(num_views, height, width, cams, ab, depth, normal, distance, normal_out, metalness=None, f0=None, depth_channels=1, device=0, stream=0):
+    """egr_prior_finish on integer device addresses (None = NULL)."""
+    L = lib()
+    a = egr_prior_finish_args(num_views=num_views, height=height, width=width, depth_channels=depth_channels, cams=cams, ab=ab, depth=depth, normal=normal, metalness=metalness,
+                              distance=distance, normal_out=normal_out, f0=f0)
+    _check(L.egr_prior_finish(device, C.byref(a), C.c_void_p(stream)), L.egr_prior_last_error)
+
+
 _lib = None
 
 
@@ -329,6 +379,12 @@ def lib(path=None):
         L.egr_viewset_gather.argtypes = [C.c_int, C.POINTER(egr_viewset_store), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(egr_viewset_batch), P]
         L.egr_viewset_last_error.argtypes = []
         L.egr_viewset_last_error.restype = C.c_char_p
+        # prior views (csrc/priors.hip): device, args, stream each
+        L.egr_prior_pairs.argtypes = [C.c_int, C.POINTER(egr_prior_pairs_args), P]
+        L.egr_prior_fit.argtypes = [C.c_int, C.POINTER(egr_prior_fit_args), P]
+        L.egr_prior_finish.argtypes = [C.c_int, C.POINTER(egr_prior_finish_args), P]
+        L.egr_prior_last_error.argtypes = []
+        L.egr_prior_last_error.restype = C.c_char_p
         L.egr_last_error.argtypes = [P]
         L.egr_last_error.restype = C.c_char_p
         L.egr_version.restype = C.c_char_p

@@ -1370,6 +1370,109 @@ static void viewset_gather(std::vector<Tensor> planes, const Tensor &R, const Te
     TORCH_CHECK(rc == 0, egr_viewset_last_error());
 }
 
+// Prior views, part 1 (egr_prior_pairs, csrc/priors.hip): the sparse depth maps of V views and their (predicted, sparse) pairs in row-major order. cams: fp32
+// [V,25] (priors.py: camera_rows); points: fp32 [M,3], the views' world-space points one after the other; offsets: V + 1 host integers ascending from 0 to M;
+// depth: fp32 [V,H,W,1|3]. Returns sparse fp32 [V,H,W] (+inf = empty), pairs_x / pairs_y fp32 [V,H*W], count / dropped int32 [V]. Current stream; the offsets are
+// uploaded, nothing is read back.
+static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> prior_pairs(const Tensor &cams, const Tensor &points, std::vector<int64_t> offsets, const Tensor &depth) {
+    const char *op = "prior_pairs";
+    const c10::Device dev = gpu_of(op, "depth", depth);
+    const c10::DeviceGuard guard(dev);
+    egr_prior_pairs_args a = {};
+    a.depth = tensor_arg<float>(op, "depth ([V,H,W,1|3])", depth, dev, {-1, -1, -1, -1});
+    const int64_t V = depth.size(0), H = depth.size(1), W = depth.size(2);
+    TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && std::max(V, std::max(H, W)) <= 65535, "prior_pairs: V and the image sizes must be in 1..65535");
+    a.cams = tensor_arg<float>(op, "cams", cams, dev, {V, EGR_PRIOR_CAM_FLOATS});
+    a.points = tensor_arg<float>(op, "points ([M,3])", points, dev, {-1, 3});
+    TORCH_CHECK((int64_t)offsets.size() == V + 1, "prior_pairs: offsets must have V + 1 = ", V + 1, " entries, got ", offsets.size());
+    std::vector<int32_t> host(offsets.size());
+    for (size_t i = 0; i < offsets.size(); i++) {
+        TORCH_CHECK(offsets[i] >= 0 && offsets[i] <= points.size(0), "prior_pairs: offsets[", i, "] = ", offsets[i], " is outside the ", points.size(0), " points");
+        host[i] = (int32_t)(uint32_t)offsets[i];
+    }
+    TORCH_CHECK(points.size(0) <= 0xFFFFFFFFll && offsets.back() == points.size(0), "prior_pairs: offsets must end at the number of points");
+    const Tensor offsets_dev = torch::from_blob(host.data(), {V + 1}, torch::kInt32).to(dev);
+    const auto f32 = torch::dtype(torch::kFloat32).device(dev), i32 = torch::dtype(torch::kInt32).device(dev);
+    Tensor sparse = torch::empty({V, H, W}, f32), pairs_x = torch::empty({V, H * W}, f32), pairs_y = torch::empty({V, H * W}, f32), count = torch::empty({V}, i32), dropped = torch::empty({V}, i32);
+    a.num_views = (uint32_t)V, a.height = (uint32_t)H, a.width = (uint32_t)W, a.depth_channels = (uint32_t)depth.size(3);
+    a.offsets = (const uint32_t *)host.data(), a.offsets_dev = (const uint32_t *)offsets_dev.data_ptr<int32_t>();
+    a.sparse = sparse.data_ptr<float>(), a.pairs_x = pairs_x.data_ptr<float>(), a.pairs_y = pairs_y.data_ptr<float>();
+    a.count = (uint32_t *)count.data_ptr<int32_t>(), a.dropped = (uint32_t *)dropped.data_ptr<int32_t>();
+    const int rc = egr_prior_pairs(dev.index(), &a, current_stream());
+    TORCH_CHECK(rc == 0, egr_prior_last_error());
+    return {sparse, pairs_x, pairs_y, count, dropped};
+}
+// Prior views, part 2 (egr_prior_fit): y = a x + b per view over the first counts[v] pairs of pairs_x / pairs_y [V,stride]. method 0 (RANSAC): samples is a CPU
+// int32 [V,num_iters,S] table of pair indices (row (v, it) uses its first sample_sizes[v]); top_ks[v] residuals score and refit. method 1: the least-squares fit
+// of all pairs (samples None). Returns ab fp32 [V,2], best_iteration int32 [V], best_error fp64 [V], hyp_error fp64 [V,num_iters], hyp_model fp32 [V,num_iters,4]
+// (w, b, threshold, bits of the ties taken) and the inlier mask uint8 [V,stride] (zeros beyond a view's count; [V,0] unless want_mask). Current stream; the
+// table and the sizes are uploaded, nothing is read back.
+static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> prior_fit(const Tensor &pairs_x, const Tensor &pairs_y, std::vector<int64_t> counts, std::vector<int64_t> sample_sizes,
+                                                                            std::vector<int64_t> top_ks, const c10::optional<Tensor> &samples, int64_t method, bool want_mask) {
+    const char *op = "prior_fit";
+    const c10::Device dev = gpu_of(op, "pairs_x", pairs_x);
+    const c10::DeviceGuard guard(dev);
+    egr_prior_fit_args a = {};
+    a.pairs_x = tensor_arg<float>(op, "pairs_x ([V,stride])", pairs_x, dev, {-1, -1});
+    const int64_t V = pairs_x.size(0), stride = pairs_x.size(1);
+    a.pairs_y = tensor_arg<float>(op, "pairs_y", pairs_y, dev, {V, stride});
+    TORCH_CHECK(V >= 1 && V <= 65535 && stride >= 1 && stride <= 65535ll * 65535ll, "prior_fit: V must be in 1..65535 and the stride in 1..65535^2");
+    TORCH_CHECK(method == EGR_PRIOR_RANSAC || method == EGR_PRIOR_LSTSQ, "prior_fit: method must be 0 (RANSAC) or 1 (least squares), got ", method);
+    TORCH_CHECK((int64_t)counts.size() == V && (int64_t)sample_sizes.size() == V && (int64_t)top_ks.size() == V, "prior_fit: counts, sample_sizes and top_ks must have one entry per view (", V, ")");
+    std::vector<int32_t> views((size_t)V * 4, 0);
+    for (int64_t v = 0; v < V; v++) {
+        const int64_t e[3] = {counts[(size_t)v], sample_sizes[(size_t)v], top_ks[(size_t)v]};
+        for (int j = 0; j < 3; j++) {
+            TORCH_CHECK(e[j] >= 0 && e[j] <= 0xFFFFFFFFll, "prior_fit: view ", v, ": counts, sample_sizes and top_ks must be in 0..2^32-1");
+            views[(size_t)v * 4 + j] = (int32_t)(uint32_t)e[j];
+        }
+    }
+    int64_t iters = 0, S = 0;
+    Tensor samples_dev;
+    if (method == EGR_PRIOR_RANSAC) {
+        TORCH_CHECK(given(samples) && samples->device().is_cpu() && samples->scalar_type() == torch::kInt32 && samples->is_contiguous() && samples->dim() == 3 && samples->size(0) == V,
+                    "prior_fit: samples must be a contiguous CPU int32 tensor [V,num_iters,S] (the table is checked on the host, where it was made)");
+        iters = samples->size(1), S = samples->size(2);
+        TORCH_CHECK(iters >= 1 && iters <= 65535 && S >= 1 && S <= EGR_PRIOR_MAX_SAMPLE, "prior_fit: num_iters must be in 1..65535 and the table's width in 1..", EGR_PRIOR_MAX_SAMPLE);
+        samples_dev = samples->to(dev);
+        a.samples = samples->data_ptr<int32_t>(), a.samples_dev = samples_dev.data_ptr<int32_t>();
+    }
+    const Tensor views_dev = torch::from_blob(views.data(), {V, 4}, torch::kInt32).to(dev);
+    const auto f32 = torch::dtype(torch::kFloat32).device(dev), f64 = torch::dtype(torch::kFloat64).device(dev), i32 = torch::dtype(torch::kInt32).device(dev);
+    Tensor ab = torch::empty({V, 2}, f32), best_iteration = torch::empty({V}, i32), best_error = torch::empty({V}, f64), hyp_error = torch::empty({V, iters}, f64),
+           hyp_model = torch::empty({V, iters, 4}, f32), inliers = torch::zeros({V, want_mask ? stride : 0}, torch::dtype(torch::kUInt8).device(dev));
+    a.num_views = (uint32_t)V, a.pair_stride = (uint32_t)stride, a.num_iters = (uint32_t)iters, a.sample_stride = (uint32_t)S, a.method = (uint32_t)method;
+    a.views = (const uint32_t *)views.data(), a.views_dev = (const uint32_t *)views_dev.data_ptr<int32_t>();
+    a.hyp_error = iters ? hyp_error.data_ptr<double>() : nullptr, a.hyp_model = iters ? hyp_model.data_ptr<float>() : nullptr;
+    a.ab = ab.data_ptr<float>(), a.best_iteration = best_iteration.data_ptr<int32_t>(), a.best_error = best_error.data_ptr<double>();
+    a.inliers = want_mask ? inliers.data_ptr<uint8_t>() : nullptr;
+    const int rc = egr_prior_fit(dev.index(), &a, current_stream());
+    TORCH_CHECK(rc == 0, egr_prior_last_error());
+    return {ab, best_iteration, best_error, hyp_error, hyp_model, inliers};
+}
+// Prior views, part 3 (egr_prior_finish): one pass over V views - the distance image of depth * a + b with (a, b) = ab[v] read on the device, the world normals
+// and f0 from metalness. depth fp32 [V,H,W,1|3], normal fp32 [V,H,W,3] (camera space), metalness fp32 [V,H,W] or [V,H,W,1] or None. Returns distance [V,H,W,1],
+// normals [V,H,W,3], f0 [V,H,W,3] ([0] without metalness): new tensors, the dataset's pixel-major layout. Current stream, no synchronisation.
+static std::tuple<Tensor, Tensor, Tensor> prior_finish(const Tensor &cams, const Tensor &ab, const Tensor &depth, const Tensor &normal, const c10::optional<Tensor> &metalness) {
+    const char *op = "prior_finish";
+    const c10::Device dev = gpu_of(op, "depth", depth);
+    const c10::DeviceGuard guard(dev);
+    egr_prior_finish_args a = {};
+    a.depth = tensor_arg<float>(op, "depth ([V,H,W,1|3])", depth, dev, {-1, -1, -1, -1});
+    const int64_t V = depth.size(0), H = depth.size(1), W = depth.size(2);
+    TORCH_CHECK(V >= 1 && H >= 1 && W >= 1 && std::max(V, std::max(H, W)) <= 65535, "prior_finish: V and the image sizes must be in 1..65535");
+    a.cams = tensor_arg<float>(op, "cams", cams, dev, {V, EGR_PRIOR_CAM_FLOATS}), a.ab = tensor_arg<float>(op, "ab", ab, dev, {V, 2});
+    a.normal = tensor_arg<float>(op, "normal", normal, dev, {V, H, W, 3});
+    a.metalness = tensor_arg<float>(op, "metalness ([V,H,W] or [V,H,W,1])", metalness, dev, Shape::elements(V * H * W), false);
+    const auto f32 = torch::dtype(torch::kFloat32).device(dev);
+    Tensor distance = torch::empty({V, H, W, 1}, f32), world = torch::empty({V, H, W, 3}, f32), f0 = a.metalness ? torch::empty({V, H, W, 3}, f32) : torch::empty({0}, f32);
+    a.num_views = (uint32_t)V, a.height = (uint32_t)H, a.width = (uint32_t)W, a.depth_channels = (uint32_t)depth.size(3);
+    a.distance = distance.data_ptr<float>(), a.normal_out = world.data_ptr<float>(), a.f0 = a.metalness ? f0.data_ptr<float>() : nullptr;
+    const int rc = egr_prior_finish(dev.index(), &a, current_stream());
+    TORCH_CHECK(rc == 0, egr_prior_last_error());
+    return {distance, world, f0};
+}
+
 // unit-test hook (egr_debug_lean_arith): (a / b, sqrt(a)) as the hot kernels' division and square root compute them
 static std::tuple<Tensor, Tensor> debug_lean_arith(const Tensor &a, const Tensor &b) {
     TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.device() == b.device() && a.numel() == b.numel(), "debug_lean_arith: two tensors of one size on one GPU expected");
@@ -1414,6 +1517,11 @@ TORCH_LIBRARY(egr, m) {
     m.def("viewset_gather(Tensor[] planes, Tensor R, Tensor centers, Tensor fovy, int num_filled, int[] indices, Tensor?[] out, Tensor out_R, Tensor out_centers, "
           "Tensor out_fovy) -> ()",
           &viewset_gather);
+    m.def("prior_pairs(Tensor cams, Tensor points, int[] offsets, Tensor depth) -> (Tensor sparse, Tensor pairs_x, Tensor pairs_y, Tensor count, Tensor dropped)", &prior_pairs);
+    m.def("prior_fit(Tensor pairs_x, Tensor pairs_y, int[] counts, int[] sample_sizes, int[] top_ks, Tensor? samples, int method=0, bool want_mask=False) -> "
+          "(Tensor ab, Tensor best_iteration, Tensor best_error, Tensor hyp_error, Tensor hyp_model, Tensor inliers)",
+          &prior_fit);
+    m.def("prior_finish(Tensor cams, Tensor ab, Tensor depth, Tensor normal, Tensor? metalness) -> (Tensor distance, Tensor normal_world, Tensor f0)", &prior_finish);
 }
 
 TORCH_LIBRARY(raytracer, m) {

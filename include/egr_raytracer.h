@@ -949,6 +949,119 @@ int egr_viewset_gather(int device, const egr_viewset_store *store, const uint32_
                        void *hip_stream);
 const char *egr_viewset_last_error(void);
 
+/* ---- prior views (additive symbols of library version 0.8, egr_version() is unchanged): what dataset/blender_prior_dataset.py:94-126 and
+ * dataset/colmap_prior_dataset.py:124-146 do per view on the CPU before a network-predicted G-buffer can be trained on - the sparse SfM depth map
+ * (utils/depth_utils.py:101-182), the robust affine fit of the predicted depth to it (ransac_linear_fit, :208-278), depth -> distance along the pixel's ray
+ * (:66-98), camera normals -> world (:7-16) and f0 from metalness - for a chunk of V views sharing height x width, in three calls (csrc/priors.hip;
+ * tests/priors_restatement.py is the same arithmetic in numpy). Context-free: the library allocates nothing, every call is asynchronous on the stream, and
+ * arguments are validated BEFORE any HIP call (non-zero return, egr_prior_last_error() says why, nothing was touched). Arrays marked HOST are read during the
+ * call by the validation; the array of the same name with _dev is the caller's device copy of the same values, which the kernels read (they clamp what they read
+ * from it to the validated sizes, so a copy that differs gives wrong numbers, never an access outside the arrays).
+ *
+ * cams [V][EGR_PRIOR_CAM_FLOATS] fp32, device: per view the 3x4 world-to-camera matrix (row-major: rows of [R^T | T] of the record), then fx, fy, cx, cy - the
+ * Python-float expressions W / (2 tan(fovx / 2)), H / (2 tan(fovy / 2)), W / 2, H / 2 rounded to fp32 on the host - then the record's R (3x3 row-major), which
+ * takes camera normals to the world.
+ *
+ * egr_prior_pairs (steps 1 and 2):
+ *   project   every point p of view v (points[offsets[v] .. offsets[v + 1]], world space): c = ((m0 x + m1 y) + m2 z) + m3 per row in fp32; kept if c.z > 0;
+ *             u = rint(c.x * fx / c.z + cx), v = rint(c.y * fy / c.z + cy) with every product, quotient and sum rounded once (no contraction) and halves
+ *             rounded to even, as torch.round; kept if 0 <= u < width and 0 <= v < height (-0.5 is column 0, width - 0.5 is outside). The kept c.z goes into
+ *             sparse [V][height][width], which the call first fills with +inf, by a 32-bit atomic minimum on the bit pattern: the NEAREST point of a pixel
+ *             wins, whatever the order of the points (upstream's unstable argsort keeps an arbitrary one). +inf stays where no point fell: +inf = EMPTY.
+ *   pairs     per view, the pixels that hold a point in ROW-MAJOR order (the order of upstream's boolean-mask indexing): pairs_x[v][i] = depth[v][pixel]
+ *             [channel 0] (the predicted depth), pairs_y[v][i] = sparse[v][pixel], count[v] pairs. A pair whose x is not finite is DROPPED and counted in
+ *             dropped[v] (upstream would poison its lstsq). One workgroup and one scan per view: no global counter, the order is exact.
+ * Refused: NULL args or a NULL cams, offsets, offsets_dev, depth or output, points NULL with offsets[V] > 0, num_views, height or width outside 1..65535,
+ * depth_channels other than 1 or 3, offsets[0] != 0 or offsets that do not ascend, an output that overlaps an input or another output.
+ *
+ * egr_prior_fit (steps 3 and 4), on pair lists pairs_x / pairs_y [V][pair_stride] of which view v uses the first views[v][0]:
+ *   views     HOST [V][4] uint32: count, sample_size S, top_k, 0. Upstream's S = min(max(2, ceil(0.1 N)), 50) and top_k = max(1, ceil(0.1 N)) are Python-float
+ *             expressions and stay with the caller. A view with count < 2 cannot be fitted: it gets a = 1, b = 0, best_iteration = -1, best_error = NaN.
+ *   samples   HOST [V][num_iters][sample_stride] int32: row (v, it) holds the S pair indices of hypothesis `it` (upstream: random.sample(range(N), S)).
+ *   hypotheses (method EGR_PRIOR_RANSAC; grid num_iters x V, one workgroup each) y = w x + b through the S sampled pairs in fp64 by centred normal
+ *             equations, summed in sample order: w = Sxy / Sxx, b = my - w mx; with Sxx == 0 the minimum-norm solution (w, b) = my (mx, 1) / (mx^2 + 1), as
+ *             lstsq gives for a rank-deficient system. w, b are rounded to fp32. Residuals r_i = |y_i - (w x_i + b)| in fp32 with separate roundings,
+ *             recomputed in every pass, never stored. threshold = the top_k-th smallest r, by a 4-pass 8-bit radix select on the bit patterns (monotone for
+ *             |.|, +inf and NaN above every number) with a 256-bin histogram in LDS. error = the fp64 sum of r^2 over the top_k smallest = sum over r <
+ *             threshold in a fixed order, without atomics, + (top_k - count_less) threshold^2: ties at the threshold do not change it.
+ *             hyp_error[v][it] = error; hyp_model[v][it] = (w, b, threshold, the bits of top_k - count_less).
+ *   select    (one workgroup per view) best = the smallest error, the lowest iteration among equals (upstream's strict <); a NaN error never wins against a
+ *             number. Inliers = every pair with r < threshold plus the FIRST top_k - count_less pairs with r == threshold in pair order (the tie rule: a
+ *             definition of this library). (a, b) = the fp64 fit to the inliers, with the same rule for Sxx == 0, rounded to fp32 into ab[v]. best_iteration
+ *             [v], best_error[v]; inliers[v][i] (uint8, i < count, NULL = not wanted).
+ *   EGR_PRIOR_LSTSQ (upstream's commented-out linear_least_squares_1d) skips the hypotheses: every pair is an inlier, best_iteration = -1, best_error = NaN;
+ *             samples, samples_dev, hyp_error and hyp_model are not read or written, num_iters and sample_stride are ignored.
+ * Refused: NULL args, pairs, views, views_dev, ab, best_iteration or best_error; for EGR_PRIOR_RANSAC NULL samples, samples_dev, hyp_error or hyp_model,
+ * num_iters outside 1..65535, sample_stride outside 1..EGR_PRIOR_MAX_SAMPLE; num_views outside 1..65535, pair_stride outside 1..65535^2, an unknown method, a
+ * count above pair_stride, for a view with count >= 2 a sample_size outside 2..min(count, sample_stride) or a top_k outside 1..count, a sample index < 0 or >=
+ * its view's count, an output that overlaps an input or another output.
+ *
+ * egr_prior_finish (step 5), one streaming pass, out of place: per pixel (row v, column u) of view i with a, b = ab[i] read from DEVICE memory (no read-back
+ * after the fit):
+ *   distance  Z = depth[channel 0] * a + b; X = (u - cx) * Z / fx; Y = (v - cy) * Z / fy; distance = sqrtf((X X + Y Y) + Z Z): fp32, every operation rounded once.
+ *   normals   n = -n; n = n / sqrtf((nx nx + ny ny) + nz nz); out = R n (rows of R, ((r0 nx + r1 ny) + r2 nz)). A zero normal gives NaN, as upstream.
+ *   f0        0.04f * (1 - m) + m, three times (metalness NULL: f0 is not written and may be NULL).
+ * distance [V][H][W][1], normal_out [V][H][W][3], f0 [V][H][W][3]: fp32, pixel-major, the dataset's layout. Refused: NULL args, cams, ab, depth, normal,
+ * distance or normal_out, metalness without f0, sizes outside 1..65535, depth_channels other than 1 or 3, an output that overlaps an input or another output. */
+#define EGR_PRIOR_CAM_FLOATS 25
+#define EGR_PRIOR_RANSAC 0u
+#define EGR_PRIOR_LSTSQ 1u
+#define EGR_PRIOR_MAX_SAMPLE 1024 /* pair indices per hypothesis */
+typedef struct egr_prior_pairs_args {
+    uint32_t num_views;
+    uint32_t height;
+    uint32_t width;
+    uint32_t depth_channels;     /* 1 or 3: channel 0 is read                                  */
+    const float *cams;           /* device [V][EGR_PRIOR_CAM_FLOATS]                            */
+    const float *points;         /* device [offsets[V]][3], world space                         */
+    const uint32_t *offsets;     /* HOST [V + 1], ascending from 0                              */
+    const uint32_t *offsets_dev; /* device copy of offsets                                      */
+    const float *depth;          /* device [V][H][W][depth_channels], the predicted depth       */
+    float *sparse;               /* out, device [V][H][W]: nearest point depth, +inf = empty    */
+    float *pairs_x;              /* out, device [V][H * W]                                      */
+    float *pairs_y;              /* out, device [V][H * W]                                      */
+    uint32_t *count;             /* out, device [V]                                             */
+    uint32_t *dropped;           /* out, device [V]                                             */
+} egr_prior_pairs_args;
+typedef struct egr_prior_fit_args {
+    uint32_t num_views;
+    uint32_t pair_stride;   /* elements between the pair lists of two views (H * W after egr_prior_pairs) */
+    uint32_t num_iters;
+    uint32_t sample_stride; /* columns of the sample table                                     */
+    uint32_t method;        /* EGR_PRIOR_RANSAC or EGR_PRIOR_LSTSQ                             */
+    uint32_t reserved;
+    const float *pairs_x;        /* device [V][pair_stride]                                     */
+    const float *pairs_y;        /* device [V][pair_stride]                                     */
+    const uint32_t *views;       /* HOST [V][4]: count, sample_size, top_k, 0                   */
+    const uint32_t *views_dev;   /* device copy of views                                        */
+    const int32_t *samples;      /* HOST [V][num_iters][sample_stride]                          */
+    const int32_t *samples_dev;  /* device copy of samples                                      */
+    double *hyp_error;           /* out, device [V][num_iters]                                  */
+    float *hyp_model;            /* out, device [V][num_iters][4]: w, b, threshold, ties taken  */
+    float *ab;                   /* out, device [V][2]                                          */
+    int32_t *best_iteration;     /* out, device [V]                                             */
+    double *best_error;          /* out, device [V]                                             */
+    uint8_t *inliers;            /* out, device [V][pair_stride]; NULL = not wanted             */
+} egr_prior_fit_args;
+typedef struct egr_prior_finish_args {
+    uint32_t num_views;
+    uint32_t height;
+    uint32_t width;
+    uint32_t depth_channels; /* 1 or 3: channel 0 is read                                       */
+    const float *cams;       /* device [V][EGR_PRIOR_CAM_FLOATS]                                */
+    const float *ab;         /* device [V][2]                                                   */
+    const float *depth;      /* device [V][H][W][depth_channels]                                */
+    const float *normal;     /* device [V][H][W][3], camera space                               */
+    const float *metalness;  /* device [V][H][W]; NULL = no f0                                  */
+    float *distance;         /* out, device [V][H][W][1]                                        */
+    float *normal_out;       /* out, device [V][H][W][3], world space                           */
+    float *f0;               /* out, device [V][H][W][3]                                        */
+} egr_prior_finish_args;
+int egr_prior_pairs(int device, const egr_prior_pairs_args *args, void *hip_stream);
+int egr_prior_fit(int device, const egr_prior_fit_args *args, void *hip_stream);
+int egr_prior_finish(int device, const egr_prior_finish_args *args, void *hip_stream);
+const char *egr_prior_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif
