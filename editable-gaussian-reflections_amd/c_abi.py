@@ -49,6 +49,7 @@ egr_train_batch = _struct("egr_train_batch", [("num_views", C.c_uint32), ("rotat
 egr_object_mask_query = _struct("egr_object_mask_query", [("rotation_c2w_dataset", _F), ("camera_center", _F), ("vertical_fov_radians", _F), ("znear", C.c_float),
                                                           ("zfar", C.c_float), ("row_bits", C.c_void_p), ("bits", C.POINTER(C.c_uint8)), ("num_bits", C.c_uint32),
                                                           ("masks", _F), ("hit", C.c_void_p), ("top", C.c_void_p)])
+EGR_CAMERA_ROTATION_ON_HOST, EGR_CAMERA_CENTER_ON_HOST = 1, 2  # egr_set_camera_from_dataset_ex: that pointer is host memory, read before the call returns
 EGR_MAX_PRUNE_ARRAYS = 32
 EGR_PRUNE_ROWS_PER_WG = 1024
 egr_prune_array = _struct("egr_prune_array", [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_uint32)])
@@ -327,6 +328,7 @@ def lib(path=None):
         L.egr_debug_set_pixel_mask.argtypes = [P, P]
         L.egr_set_targets_chw.argtypes = [P, P, P, P, P, P, P, P]
         L.egr_set_camera_from_dataset.argtypes = [P, P, P, C.c_float, C.c_float, C.c_float, P]
+        L.egr_set_camera_from_dataset_ex.argtypes = [P, P, P, C.c_float, C.c_float, C.c_float, C.c_uint, P]  # ... flags (EGR_CAMERA_*_ON_HOST: that pointer is host memory), stream
         L.egr_tile_owner.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
         L.egr_tile_owner.restype = C.c_int
         L.egr_set_strands.argtypes = [P, C.c_int]

@@ -17,6 +17,7 @@ void egr_export_step_hits(egr_context *c, int32_t *host_out, hipStream_t s); // 
 void egr_export_hit_hash(egr_context *c, uint64_t *host_out, hipStream_t s); // trace.hip
 void egr_upload_targets(egr_context *c, const float *const chw[6], hipStream_t s); // trace.hip
 void egr_set_camera_launch(egr_context *c, const float *R, const float *centre, float fov, float znear, float zfar, hipStream_t s); // trace.hip
+void egr_set_camera_values_launch(egr_context *c, const float *R, bool R_on_host, const float *centre, bool centre_on_host, float fov, float znear, float zfar, hipStream_t s); // trace.hip
 
 void egr_stamp_begin(egr_context *c, const char *name, hipStream_t s) {
     if (!c->timing) return;
@@ -362,6 +363,20 @@ int egr_set_batch_frames(egr_context *c, int frames) {
 int egr_set_camera_from_dataset(egr_context *c, const float *rotation_c2w_dataset, const float *camera_center, float vertical_fov_radians, float znear, float zfar, void *stream) {
     if (!c || !c->bound || !rotation_c2w_dataset || !camera_center) return 1;
     return guarded(c, [&] { egr_set_camera_launch(c, rotation_c2w_dataset, camera_center, vertical_fov_radians, znear, zfar, (hipStream_t)stream); });
+}
+
+int egr_set_camera_from_dataset_ex(egr_context *c, const float *rotation_c2w_dataset, const float *camera_center, float vertical_fov_radians, float znear, float zfar, unsigned flags,
+                                   void *stream) {
+    if (!c || !c->bound || !rotation_c2w_dataset || !camera_center) return 1;
+    if (flags & ~(EGR_CAMERA_ROTATION_ON_HOST | EGR_CAMERA_CENTER_ON_HOST)) {
+        c->last_error = "libegr_hip: egr_set_camera_from_dataset_ex: unknown flag";
+        return 1;
+    }
+    if (flags == 0u) return egr_set_camera_from_dataset(c, rotation_c2w_dataset, camera_center, vertical_fov_radians, znear, zfar, stream);
+    return guarded(c, [&] {
+        egr_set_camera_values_launch(c, rotation_c2w_dataset, (flags & EGR_CAMERA_ROTATION_ON_HOST) != 0u, camera_center, (flags & EGR_CAMERA_CENTER_ON_HOST) != 0u, vertical_fov_radians, znear,
+                                     zfar, (hipStream_t)stream);
+    });
 }
 
 int egr_set_targets_chw(egr_context *c, const float *diffuse, const float *specular, const float *depth, const float *normal, const float *roughness, const float *f0, void *stream) {

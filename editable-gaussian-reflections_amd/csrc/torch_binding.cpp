@@ -500,11 +500,15 @@ struct Raytracer : torch::CustomClassHolder {
     }
     // pose + scalars of a view in one launch (egr_set_camera_from_dataset): R = the dataset's c2w rotation [3,3], centre = camera_center [3], fp32 CUDA tensors
     void set_camera(Tensor R, Tensor centre, double fov, double znear, double zfar) {
-        // (the reference's copy_ calls - gaussian_raytracer.py:98-100 - take tensors of any device: a CPU tensor is moved to this tracer's device first)
+        // (the reference's copy_ calls - gaussian_raytracer.py:98-100 - take tensors of any device. A tensor of another GPU is moved to this tracer's device; a CPU
+        // tensor - a dataset's numpy pose - is converted on the host and its values go to the launch BY VALUE: the upload of a pageable tensor would wait for
+        // the stream, once per training iteration)
         TORCH_CHECK(R.dim() == 2 && R.size(0) == 3 && R.size(1) == 3 && centre.numel() == 3, "set_camera: tensors [3,3] and [3] expected");
         const auto dev = framebuffer_data->output_rgb.device();
-        Tensor r = R.to(dev, torch::kFloat32).contiguous(), cc = centre.to(dev, torch::kFloat32).contiguous();
-        check(egr_set_camera_from_dataset(ctx, r.data_ptr<float>(), cc.data_ptr<float>(), (float)fov, (float)znear, (float)zfar, current_stream()), "set_camera");
+        const auto here = [&](const Tensor &t) { return t.is_cpu() ? t.to(torch::kFloat32).contiguous() : t.to(dev, torch::kFloat32).contiguous(); };
+        Tensor r = here(R), cc = here(centre);
+        const unsigned flags = (r.is_cpu() ? EGR_CAMERA_ROTATION_ON_HOST : 0u) | (cc.is_cpu() ? EGR_CAMERA_CENTER_ON_HOST : 0u);
+        check(egr_set_camera_from_dataset_ex(ctx, r.data_ptr<float>(), cc.data_ptr<float>(), (float)fov, (float)znear, (float)zfar, flags, current_stream()), "set_camera");
     }
     static constexpr struct { const char *name; int64_t channels; } TARGETS[6] = {{"diffuse", 3}, {"specular", 3}, {"depth", 1}, {"normal", 3}, {"roughness", 1}, {"f0", 3}}; // (the order of the C ABI's six target pointers)
     // the six target images of a training view, channel-major ([C,H,W] contiguous fp32 CUDA tensors; an undefined / empty tensor = absent = zeros), written into

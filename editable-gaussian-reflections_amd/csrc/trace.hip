@@ -1467,6 +1467,23 @@ __global__ void k_set_camera(egr_camera cam, const float *__restrict__ R, const 
     if (t < 3) const_cast<float *>(cam.origin)[t] = centre[t];
     if (t == 0) *const_cast<float *>(cam.vertical_fov_radians) = fov, *const_cast<float *>(cam.znear) = znear, *const_cast<float *>(cam.zfar) = zfar;
 }
+// ... with R and / or centre in HOST memory (a dataset's numpy pose): the twelve floats travel by value as a kernel argument - no upload, no wait, and the
+// caller's arrays are free again when the launch call returns. A null device pointer = that part comes from `host`. The same stores as k_set_camera.
+struct CameraPoseValues {
+    float R[9], centre[3];
+};
+__global__ void k_set_camera_values(egr_camera cam, CameraPoseValues host, const float *__restrict__ R_dev, const float *__restrict__ centre_dev, float fov, float znear, float zfar) {
+    const int t = threadIdx.x;
+    if (t < 9) {
+        const int r = t / 3, c = t % 3;
+        const float x = R_dev ? R_dev[t] : host.R[t];
+        const float rb = c == 0 ? x : -x;
+        const_cast<float *>(cam.rotation_c2w)[t] = rb;
+        const_cast<float *>(cam.rotation_w2c)[3 * c + r] = rb;
+    }
+    if (t < 3) const_cast<float *>(cam.origin)[t] = centre_dev ? centre_dev[t] : host.centre[t];
+    if (t == 0) *const_cast<float *>(cam.vertical_fov_radians) = fov, *const_cast<float *>(cam.znear) = znear, *const_cast<float *>(cam.zfar) = zfar;
+}
 
 // Target upload (the caller's six `buf.copy_(val.moveaxis(0, -1))` of gaussian_raytracer.py:109-137 as ONE launch): CHW images -> the framebuffer's HWC
 // target buffers, for the pixels of THIS rank's tiles only (a rank of an 8-way partition reads and writes an eighth of the 116 MB a whole
@@ -1982,6 +1999,15 @@ void egr_export_hit_hash(egr_context *c, uint64_t *host_out, hipStream_t s) { ex
 
 void egr_set_camera_launch(egr_context *c, const float *R, const float *centre, float fov, float znear, float zfar, hipStream_t s) {
     hipLaunchKernelGGL(k_set_camera, dim3(1), dim3(64), 0, s, c->cam, R, centre, fov, znear, zfar);
+}
+// R / centre in host memory (R_on_host / centre_on_host): read HERE, before the launch call returns, and handed over by value
+void egr_set_camera_values_launch(egr_context *c, const float *R, bool R_on_host, const float *centre, bool centre_on_host, float fov, float znear, float zfar, hipStream_t s) {
+    CameraPoseValues host{};
+    if (R_on_host)
+        for (int i = 0; i < 9; i++) host.R[i] = R[i];
+    if (centre_on_host)
+        for (int i = 0; i < 3; i++) host.centre[i] = centre[i];
+    hipLaunchKernelGGL(k_set_camera_values, dim3(1), dim3(64), 0, s, c->cam, host, R_on_host ? nullptr : R, centre_on_host ? nullptr : centre, fov, znear, zfar);
 }
 
 void egr_upload_targets(egr_context *c, const float *const chw[6], hipStream_t s) {

@@ -248,7 +248,8 @@ class GaussianRaytracer:
         grads = torch.is_grad_enabled()
         refit = grads or force_update_bvh  # (then the export below is part of the refit's pass)
         with torch.no_grad():
-            R = torch.from_numpy(viewpoint_camera.R).cuda().float() if isinstance(viewpoint_camera.R, np.ndarray) else viewpoint_camera.R.cuda()
+            # (a numpy or CPU pose stays on the host: set_camera hands its twelve floats to the launch by value, where an upload would wait for the stream)
+            R = torch.from_numpy(viewpoint_camera.R) if isinstance(viewpoint_camera.R, np.ndarray) else viewpoint_camera.R
             # gaussian_raytracer.py:94-100 (R_c2w_blender = blender_rotation(R); znear / zfar / fov fill_; set_pose(camera_center, R_c2w_blender)) as ONE launch
             self.cuda_module.set_camera(R, viewpoint_camera.camera_center, float(viewpoint_camera.FoVy), float(os.getenv("ZNEAR", znear)), float(os.getenv("ZFAR", zfar)))
             if not refit:

@@ -188,6 +188,13 @@ int egr_raytrace_targets(egr_context *ctx, int grads_enabled, const egr_gaussian
  * the origin, and the three scalars. Asynchronous on the stream. */
 int egr_set_camera_from_dataset(egr_context *ctx, const float *rotation_c2w_dataset, const float *camera_center, float vertical_fov_radians, float znear,
                                 float zfar, void *hip_stream);
+/* The same with flags: EGR_CAMERA_ROTATION_ON_HOST / EGR_CAMERA_CENTER_ON_HOST say that the pointer is HOST memory (a dataset keeps R as a numpy array). Such
+ * values are read before the call returns and travel to the ONE launch by value: no upload, no wait for the stream, and the caller's array is free again at
+ * once. The bound camera struct holds the same bits as after the device-pointer call. Unknown flags are refused (non-zero, egr_last_error). */
+#define EGR_CAMERA_ROTATION_ON_HOST 1u
+#define EGR_CAMERA_CENTER_ON_HOST 2u
+int egr_set_camera_from_dataset_ex(egr_context *ctx, const float *rotation_c2w_dataset, const float *camera_center, float vertical_fov_radians, float znear,
+                                   float zfar, unsigned flags, void *hip_stream);
 
 /* Target upload (replaces the caller's six `framebuffer.target_*.copy_(image.moveaxis(0, -1))` of renderer/gaussian_raytracer.py:109-137, which
  * stay valid): device pointers to channel-major fp32 images ([3][H][W] diffuse, specular, normal, f0; [1][H][W] depth, roughness), NULL = the
