@@ -144,8 +144,9 @@
             // each) where the packet walk of rounds 1-3 had every lane test its own ray against every slot of one node (8 x 31
             // instructions per node, one dependent scalar-cache round trip per node). The walk pops up to eight nodes per iteration
             // from a wave-wide LDS stack, inner hits go back onto it, leaf hits into the leaf buffer; the buffered leaves are then
-            // evaluated one after the other by ONE instance of the candidate test (records through the scalar cache, the next leaf's
-            // record requested before the current one is worked off), every lane for its own ray. The test is conservative (interval
+            // evaluated by ONE instance of the candidate test, every lane for its own ray and only against the leaves its ray can meet (a
+            // per-ray sphere pre-test, records staged in LDS: below; exact statistics: every leaf, records through the scalar cache, the
+            // next leaf's record requested before the current one is worked off). The test is conservative (interval
             // arithmetic on the box's projections + half a cell of slack): it may enter a box no ray hits, never the reverse.
             const unsigned long long okm = __ballot(ray_ok);
             if (okm != 0ull) {
@@ -261,6 +262,8 @@
                         // the loop below reads it back with one broadcast LDS read instead of twelve VALU instructions in every lane. The ray table is
                         // free during a primary step (only pair walks publish rays) and holds the 192 vectors a round can have.
                         static_assert(EGR_WAVE + 8 * EGR_FPOP * EGR_WIDTH <= 3 * EGR_WAVE, "the ray table holds one float4 per buffered leaf");
+                        static_assert(3 * EGR_WAVE + 5 * EGR_WAVE <= EGR_LBUF, "the leaf buffer holds five more words per leaf of a 64-leaf chunk behind its 192 leaf indices");
+                        if constexpr (CUBE) { // exact statistics count an `outside` pair (test_candidate returns 1): every lane tests every buffered leaf
                         float4 *const llo = &rayp[0][0];
                         for (uint32_t base = 0u; base < nl; base += (uint32_t)EGR_WAVE) {
                             const uint32_t li = base + (uint32_t)lane;
@@ -293,6 +296,87 @@
                             // exec mask, and has to wait for the whole load before the body's first instruction - the prefetch hid nothing)
                             asm volatile("" ::"s"(n0.w), "s"(n1.w), "s"(n2.w), "s"(n3.x), "s"(n3.y));
 #endif
+                        }
+                        } else {
+                        // Default launches: a pair whose response point lies outside the ellipsoid returns 0 or 3 - never counted, never appended - and with
+                        // gaussians about two tiles across three quarters of a tile's (ray, leaf) pairs are just that, found out only after most of
+                        // candidate_geometry_from, in every lane, for every leaf. So, in chunks of 64 buffered leaves and lane = ray throughout:
+                        // 0. STAGING, one lane per leaf: what the candidate test reads of the leaf's record (rows of W, opacity, sigma factor), the
+                        //    object-space origin (see above) and the padded sphere go to LDS - the ray table holds the rows with the origin in their
+                        //    fourth components, the leaf buffer behind its 192 indices the other five words. The records are fetched ONCE per tile,
+                        //    coalesced by leaf; a gather per lane from global memory in the loop of step 2 made an iteration 2.6 times as expensive
+                        //    as the scalar fetch it replaced and the kernel slower (profiles/HISTORY.md, profiles/r19/).
+                        // 1. the PRE-TEST (trace.hip: ray_misses_sphere): every leaf of the chunk in turn, wave-uniform, its sphere read with a broadcast
+                        //    LDS read, a dozen VALU instructions; a lane keeps bit i of a two-dword mask for every leaf its ray can meet. A rejected
+                        //    pair is one the candidate test would have returned 0 or 3 for.
+                        // 2. the SURVIVOR LOOP: every lane walks ITS OWN kept leaves in ascending buffer order - the order it met them in when every
+                        //    lane tested every leaf, so its list, its counters and the factors of full_Td come out entry for entry as they did - and
+                        //    different lanes work on different leaves in one iteration: the loop runs for the longest mask of any lane, not for the
+                        //    number of leaves (per chunk: a mask over the whole round would need the round's records in LDS, 10.7 KB per wave). A lane
+                        //    reads its record from LDS by slot; the next slot is taken off the mask and its reads are under way while the current
+                        //    record is worked off. Still ONE instance of the candidate test (see above).
+                        constexpr int NW = EGR_WAVE / 32;
+                        uint32_t *const lx = lbuf + 3 * EGR_WAVE; // five words per leaf of the chunk: opacity, sigma factor, a / rad
+                        const float rd2 = dot(rd, rd);
+                        for (uint32_t cbase = 0u; cbase < nl; cbase += (uint32_t)EGR_WAVE) {
+                        const uint32_t cn = min(nl - cbase, (uint32_t)EGR_WAVE);
+                        if ((uint32_t)lane < cn) { // STAGING, one lane per leaf of the chunk: the record as the candidate test reads it, the object-space origin, the sphere
+                            const uint32_t leaf = lbuf[cbase + (uint32_t)lane];
+                            const float4 g0 = v.inst_w[4 * (size_t)leaf], g1 = v.inst_w[4 * (size_t)leaf + 1], g2 = v.inst_w[4 * (size_t)leaf + 2], g3 = v.inst_w[4 * (size_t)leaf + 3];
+                            const f3 lo_ = object_origin(g0, g1, g2, cam_o);
+                            const f3 an = staged_sphere(v.bsph[leaf], g0, g1, g2, lo_, cam_o);
+                            rayp[lane][0] = make_float4(g0.x, g0.y, g0.z, lo_.x), rayp[lane][1] = make_float4(g1.x, g1.y, g1.z, lo_.y), rayp[lane][2] = make_float4(g2.x, g2.y, g2.z, lo_.z);
+                            lx[5 * lane] = f2u(g3.z), lx[5 * lane + 1] = f2u(g3.w), lx[5 * lane + 2] = f2u(an.x), lx[5 * lane + 3] = f2u(an.y), lx[5 * lane + 4] = f2u(an.z);
+                        }
+                        wave_sync();
+                        uint32_t mk[NW]; // (indexed by unrolled constants only: a dynamic index would send it to scratch)
+#pragma unroll
+                        for (int w = 0; w < NW; w++) {
+                            uint32_t m = 0u;
+                            if (32u * (uint32_t)w < cn) {
+                                const uint32_t nb = min(cn - 32u * (uint32_t)w, 32u);
+#pragma unroll 4 // (four leaves' LDS reads in flight)
+                                for (uint32_t j = 0; j < nb; j++) {
+                                    const uint32_t i = 32u * (uint32_t)w + j;
+                                    const f3 an = mk3(u2f(lx[5u * i + 2u]), u2f(lx[5u * i + 3u]), u2f(lx[5u * i + 4u]));
+                                    m |= (ray_misses_sphere(an, rd, rd2) ? 0u : 1u) << j;
+                                }
+                            }
+                            mk[w] = ray_ok ? m : 0u;
+                        }
+                        constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;
+                        auto pop = [&]() -> uint32_t { // this lane's lowest kept slot, taken off its mask (selects, no indexing); NO_SLOT when none is left
+                            uint32_t word = 0u, base = 0u;
+#pragma unroll
+                            for (int w = NW - 1; w >= 0; w--) {
+                                const bool h = mk[w] != 0u;
+                                word = h ? mk[w] : word, base = h ? 32u * (uint32_t)w : base;
+                            }
+                            const uint32_t rest = word & (word - 1u);
+#pragma unroll
+                            for (int w = 0; w < NW; w++) mk[w] = base == 32u * (uint32_t)w ? rest : mk[w]; // (no word left: base 0, and word 0 stays 0)
+                            return base + (uint32_t)__ffs((int)word) - 1u;                                    // (no word left: 0 + 0 - 1 = NO_SLOT)
+                        };
+                        uint32_t s_n = pop(); // the slot worked off next; a lane without one parks on the chunk's last slot and idles
+                        uint32_t sc = min(s_n, cn - 1u);
+                        uint32_t leaf_n = lbuf[cbase + sc];
+                        float4 n0 = rayp[sc][0], n1 = rayp[sc][1], n2 = rayp[sc][2]; // (rows of W, the origin in their fourth components)
+                        float q0 = u2f(lx[5u * sc]), q1 = u2f(lx[5u * sc + 1u]);
+#pragma unroll 1
+                        while (__ballot(s_n != NO_SLOT) != 0ull) {
+                            const bool have = s_n != NO_SLOT;
+                            const uint32_t p = leaf_n;
+                            const float4 w0 = n0, w1 = n1, w2 = n2, a2 = make_float4(0.0f, 0.0f, q0, q1); // (opacity, sigma factor: what the candidate test reads of the live quarter)
+                            const f3 lo_pre = mk3(n0.w, n1.w, n2.w);
+                            s_n = pop(), sc = min(s_n, cn - 1u); // the next record's LDS reads are under way during the test below
+                            leaf_n = lbuf[cbase + sc];
+                            n0 = rayp[sc][0], n1 = rayp[sc][1], n2 = rayp[sc][2];
+                            q0 = u2f(lx[5u * sc]), q1 = u2f(lx[5u * sc + 1u]);
+                            EGR_STATS(st_leafhits += have ? 1u : 0u, st_outer += (lane == 0);)
+                            if (have) evaluate(p, w0, w1, w2, a2, lo_pre);
+                        }
+                        wave_sync(); // every lane has read its last record: the next chunk's staging overwrites them
+                        }
                         }
                         }
                         nl = 0u;

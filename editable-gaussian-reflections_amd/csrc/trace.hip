@@ -421,6 +421,37 @@ EGR_DI int test_candidate(const FwdConst &fc, int step, int seg, float near_plan
     return 2;
 }
 
+// Per-ray pre-test of primary tiles (forward_task.inc), before a (ray, gaussian) pair is evaluated at all: the ray against the gaussian's bounding sphere
+// (bvh.hip: bsph). staged_sphere runs once per buffered leaf and returns a / rad, the vector from the camera to the centre in units of the PADDED radius;
+// ray_misses_sphere runs per (ray, leaf): the line o + t d misses the sphere iff |a x d|^2 > rad^2 |d|^2, i.e. |(a / rad) x d|^2 > |d|^2.
+// What a rejection must imply is that test_candidate returns 0 or 3 for the pair (never counted, never appended), i.e. that `outside` as
+// candidate_geometry_from computes it in fp32 is true. In exact arithmetic |u| >= (distance of the line from the centre) / s_max, s_max the largest
+// semi-axis, so a line that misses the sphere of radius s_max (1 + m) has |u| >= 1 + m. The fp32 |u| differs from that by
+//   (a) the rounding of lo = W o + w, a cancellation: <= 3 x 2^-24 (|o|_1 + |centre|_1) in WORLD units on every axis, whatever the scale;
+//   (b) the direction dhat = W d / |W d|: every component of W d is rounded to 2^-23 |d| / s_a, against |W d| >= |d| / s_max: an angle of
+//       sqrt(3) 2^-23 k, k = s_max / s_min, which moves u = lo - (lo . dhat) dhat by up to |lo| times that;
+//   (c) the roundings of tl, of dhat's length and of the three fma of u: about 6 x 2^-24 |lo|.
+// Hence m = 0.005 + 1e-6 |lo|_1 (k + 1) (four to five times (b) + (c)), and 1e-6 (|o|_1 + |centre|_1) is added to the radius for (a). The fixed 0.5 %
+// alone would stop covering (b) + (c), about 2e-7 |lo| (k + 2), at |lo| (k + 2) of about 2e4: a round gaussian 1e4 of its radii from the camera - a 1e-4
+// gaussian at distance 50 is fifty times beyond that, so the pad scales with |lo|. The pre-test's own arithmetic (a = centre - o, the cross product)
+// is covered by 2e-6 |a|_1, as in the leaf filter. Only finite evidence rejects: a NaN or an inf on either side keeps the pair.
+EGR_DI f3 staged_sphere(const float4 &sp, const float4 &w0, const float4 &w1, const float4 &w2, const f3 &lo, const f3 &o) {
+    const f3 a = mk3(sp.x - o.x, sp.y - o.y, sp.z - o.z);
+    const float smax = sqrtf(fmaxf(sp.w, 0.0f));                                                                              // (padded by k_instances)
+    const float inv_smin = sqrtf(fmaxf(fmaxf(dot(mk3(w0.x, w0.y, w0.z), mk3(w0.x, w0.y, w0.z)), dot(mk3(w1.x, w1.y, w1.z), mk3(w1.x, w1.y, w1.z))),
+                                       dot(mk3(w2.x, w2.y, w2.z), mk3(w2.x, w2.y, w2.z)))); // rows of W = columns of R over the scales
+    const float lo1 = fabsf(lo.x) + fabsf(lo.y) + fabsf(lo.z);
+    const float rad = smax * (1.005f + 1e-6f * lo1 * (smax * inv_smin + 1.0f)) + 2e-6f * (fabsf(a.x) + fabsf(a.y) + fabsf(a.z)) +
+                      1e-6f * (fabsf(o.x) + fabsf(o.y) + fabsf(o.z) + fabsf(sp.x) + fabsf(sp.y) + fabsf(sp.z));
+    const float ir = sp.w >= 0.0f ? 1.0f / rad : u2f(0x7FC00000u); // (an unusable gaussian: NaN, every pair is kept and the candidate test rejects it as before)
+    return mk3(a.x * ir, a.y * ir, a.z * ir);
+}
+EGR_DI bool ray_misses_sphere(const f3 &an, const f3 &d, float d2) { // an: staged_sphere; d2 = |d|^2
+    const f3 c = cross(an, d);
+    const float c2 = dot(c, c);
+    return c2 > d2 && c2 < __builtin_inff();
+}
+
 // One evaluation batch worked off: lane = one (ray, gaussian) pair whose 64-B record (w0..w2 = rows of W, w3 = live quarter) has arrived. The candidate
 // test, then an accepted candidate takes a slot of its ray's list through the ray's LDS counter (the run in the wave's scratch, beyond cand_cap ONE
 // extension block per ray). Shared by the pair walk of bounce tiles and by the primary tiles' leaf evaluation (forward_task.inc).
