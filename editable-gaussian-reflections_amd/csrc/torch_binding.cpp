@@ -29,6 +29,68 @@ inline at::TensorOptions I32() { return torch::dtype(torch::kInt32).device(torch
 inline at::TensorOptions B8() { return torch::dtype(torch::kBool).device(torch::kCUDA); }
 inline void *current_stream() { return (void *)c10::hip::getCurrentHIPStream().stream(); }
 template <class T> T *ptr(const Tensor &t) { return reinterpret_cast<T *>(t.data_ptr()); }
+
+// ---- The argument checks of both halves of this file: the Raytracer's methods and the context-free ops
+bool given(const c10::optional<Tensor> &t) { return t.has_value() && t->defined(); }
+// (a Tensor[] cannot hold None: there an undefined or empty tensor is an absent entry)
+c10::optional<Tensor> unless_empty(const Tensor &t) { return t.defined() && t.numel() ? c10::optional<Tensor>(t) : c10::nullopt; }
+
+// What a tensor argument must measure: a full shape (-1: any size in that dimension), at least so many rows of a trailing shape, or a number of elements in any shape.
+struct Shape {
+    std::vector<int64_t> dims;
+    int64_t min_rows = 0, numel = -1;
+    Shape(std::initializer_list<int64_t> d) : dims(d) {}
+    Shape(std::vector<int64_t> d) : dims(std::move(d)) {}
+    static Shape at_least(int64_t rows, std::vector<int64_t> trailing) {
+        trailing.insert(trailing.begin(), -1);
+        Shape s(std::move(trailing));
+        s.min_rows = rows;
+        return s;
+    }
+    static Shape elements(int64_t n) {
+        Shape s(std::vector<int64_t>{});
+        s.numel = n;
+        return s;
+    }
+    bool fits(const Tensor &t) const {
+        if (numel >= 0) return t.numel() == numel;
+        if (t.dim() != (int64_t)dims.size() || (min_rows > 0 && t.size(0) < min_rows)) return false;
+        for (size_t d = 0; d < dims.size(); d++)
+            if (dims[d] >= 0 && t.size((int64_t)d) != dims[d]) return false;
+        return true;
+    }
+    std::string text() const {
+        if (numel >= 0) return "of " + std::to_string(numel) + " elements";
+        std::string s = "[";
+        for (size_t d = 0; d < dims.size(); d++)
+            s += (d ? ", " : "") + (dims[d] >= 0 ? std::to_string(dims[d]) : d == 0 && min_rows > 0 ? ">= " + std::to_string(min_rows) : std::string("*"));
+        return s + "]";
+    }
+};
+
+// THE argument check: a tensor of T's dtype, contiguous, on `dev`, of the wanted shape -> its data pointer. An absent one (None, or undefined) -> NULL if it is
+// optional, an error if it is required. Errors carry the op's and the argument's name.
+template <class T> T *tensor_arg(const char *op, const std::string &name, const c10::optional<Tensor> &t, c10::Device dev, const Shape &want, bool required = true) {
+    if (!given(t)) {
+        TORCH_CHECK(!required, op, ": ", name, " is required");
+        return nullptr;
+    }
+    constexpr c10::ScalarType dtype = c10::CppTypeToScalarType<T>::value;
+    TORCH_CHECK(t->is_cuda() && t->device() == dev && t->scalar_type() == dtype && t->is_contiguous() && want.fits(*t), op, ": ", name, " must be a contiguous ", dtype, " tensor ",
+                want.text(), " on ", dev, ", got ", t->scalar_type(), " ", t->sizes(), t->is_contiguous() ? "" : " (not contiguous)", " on ", t->device());
+    return t->data_ptr<T>();
+}
+// An entry of the tensor lists of prune_gather and grow_append: n rows of 4-byte elements of any dtype, moved as bits.
+void *words_arg(const char *op, const char *list, size_t k, const Tensor &t, c10::Device dev, int64_t n) {
+    TORCH_CHECK(t.defined() && t.is_cuda() && t.device() == dev && t.is_contiguous() && t.element_size() == 4 && t.dim() >= 1 && t.size(0) == n, op, ": ", list, "[", k,
+                "] must be a contiguous tensor of 4-byte elements with ", n, " rows on ", dev, " (contiguous GPU tensors of 4-byte elements with the same leading size are required)");
+    return t.data_ptr();
+}
+// The device of an op: that of the tensor that leads its arguments.
+c10::Device gpu_of(const char *op, const char *name, const Tensor &t) {
+    TORCH_CHECK(t.defined() && t.is_cuda(), op, ": ", name, " must be a GPU tensor (there is no CPU path)");
+    return t.device();
+}
 } // namespace
 
 // core/camera.h:43-77
@@ -203,21 +265,26 @@ struct GaussianDataHolder : torch::CustomClassHolder {
     Tensor dL_droughness = torch::empty({0}, F32()), dL_dopacity = torch::empty({0}, F32()), dL_dscale = torch::empty({0}, F32());
     Tensor dL_dmean = torch::empty({0}, F32()), dL_drotation = torch::empty({0}, F32()), total_weight = torch::empty({0}, F32());
 
+    // THE table of the eight parameters, in the export order of gaussian_raytracer.py:41-50 (the order of update_bvh_from's and import_into's tensors): name, width,
+    // where the gradient's window starts in the flat buffer (floats per Gaussian; the buffer is tensor-major in the holder's order, total_weight last at 21), the
+    // holder's parameter and gradient tensors and the same two in egr_gaussians.
+    struct Param { const char *name; int64_t width, grad_offset; Tensor GaussianDataHolder::*value, GaussianDataHolder::*grad; const float *egr_gaussians::*raw_value; float *egr_gaussians::*raw_grad; };
+    static const Param PARAMS[8];
+    static std::string param_names() {
+        std::string s;
+        for (const Param &p : PARAMS) s += (s.empty() ? "" : ", ") + std::string(p.name);
+        return s;
+    }
+
     void point_grads() {
-        int64_t off = 0;
-        auto win = [&](Tensor &t, int64_t c) {
-            t.set_(grad_flat.storage(), off, {count, c}, {c, 1}); // same TensorImpl, new window
-            off += count * c;
-        };
-        win(dL_drgb, 3), win(dL_dnormal, 3), win(dL_df0, 3), win(dL_droughness, 1), win(dL_dopacity, 1);
-        win(dL_dscale, 3), win(dL_dmean, 3), win(dL_drotation, 4), win(total_weight, 1);
+        auto win = [&](Tensor &t, int64_t offset, int64_t c) { t.set_(grad_flat.storage(), offset * count, {count, c}, {c, 1}); }; // same TensorImpl, new window
+        for (const Param &p : PARAMS) win(this->*p.grad, p.grad_offset, p.width);
+        win(total_weight, 21, 1);
     }
     GaussianDataHolder() {
         torch::NoGradGuard no_grad;
         point_grads();
-        rgb.mutable_grad() = dL_drgb, normal.mutable_grad() = dL_dnormal, f0.mutable_grad() = dL_df0;
-        roughness.mutable_grad() = dL_droughness, opacity.mutable_grad() = dL_dopacity, scale.mutable_grad() = dL_dscale;
-        mean.mutable_grad() = dL_dmean, rotation.mutable_grad() = dL_drotation;
+        for (const Param &p : PARAMS) (this->*p.value).mutable_grad() = this->*p.grad;
     }
     // Multi-GPU (not in the reference): with `use_delta` a grad launch STORES its gradients and weights in a [22N] buffer of its own
     // (grad_delta; egr_set_grad_overwrite: rows no ray touched read 0, nobody has to clear it) instead of adding them to the persistent
@@ -233,27 +300,23 @@ struct GaussianDataHolder : torch::CustomClassHolder {
     void resize(int64_t n) { // gaussians.h:64-86: resize_ keeps the first min(old, n) rows of every tensor; grown gradient memory is zeroed here
         torch::NoGradGuard no_grad;
         const int64_t keep = std::min(count, n);
-        Tensor old_rows[9] = {dL_drgb.narrow(0, 0, keep).clone(), dL_dnormal.narrow(0, 0, keep).clone(), dL_df0.narrow(0, 0, keep).clone(),
-                              dL_droughness.narrow(0, 0, keep).clone(), dL_dopacity.narrow(0, 0, keep).clone(), dL_dscale.narrow(0, 0, keep).clone(),
-                              dL_dmean.narrow(0, 0, keep).clone(), dL_drotation.narrow(0, 0, keep).clone(), total_weight.narrow(0, 0, keep).clone()};
+        std::vector<Tensor *> win{&total_weight};
+        for (const Param &p : PARAMS) win.push_back(&(this->*p.grad));
+        std::vector<Tensor> old_rows;
+        for (Tensor *w : win) old_rows.push_back(w->narrow(0, 0, keep).clone());
         count = n;
-        rgb.resize_({n, 3}), normal.resize_({n, 3}), f0.resize_({n, 3}), roughness.resize_({n, 1}), opacity.resize_({n, 1});
-        scale.resize_({n, 3}), mean.resize_({n, 3}), rotation.resize_({n, 4});
+        for (const Param &p : PARAMS) (this->*p.value).resize_({n, p.width});
         grad_flat = torch::zeros({22 * n}, F32());
         point_grads();
-        Tensor *win[9] = {&dL_drgb, &dL_dnormal, &dL_df0, &dL_droughness, &dL_dopacity, &dL_dscale, &dL_dmean, &dL_drotation, &total_weight};
-        for (int k = 0; k < 9 && keep > 0; k++) win[k]->narrow(0, 0, keep).copy_(old_rows[k]);
+        for (size_t k = 0; k < win.size() && keep > 0; k++) win[k]->narrow(0, 0, keep).copy_(old_rows[k]);
         if (use_delta) grad_delta = torch::zeros({22 * n}, F32());
     }
     egr_gaussians reify() {
         egr_gaussians g;
         g.count = (uint32_t)count;
-        g.rgb = ptr<float>(rgb), g.normal = ptr<float>(normal), g.f0 = ptr<float>(f0), g.roughness = ptr<float>(roughness);
-        g.opacity = ptr<float>(opacity), g.scale = ptr<float>(scale), g.mean = ptr<float>(mean), g.rotation = ptr<float>(rotation);
         float *base = use_delta ? ptr<float>(grad_delta) : ptr<float>(grad_flat); // same tensor-major layout as point_grads()
-        const size_t n = (size_t)count;
-        g.dL_drgb = base, g.dL_dnormal = base + 3 * n, g.dL_df0 = base + 6 * n, g.dL_droughness = base + 9 * n, g.dL_dopacity = base + 10 * n;
-        g.dL_dscale = base + 11 * n, g.dL_dmean = base + 14 * n, g.dL_drotation = base + 17 * n, g.total_weight = base + 21 * n;
+        for (const Param &p : PARAMS) g.*p.raw_value = ptr<float>(this->*p.value), g.*p.raw_grad = base + p.grad_offset * count;
+        g.total_weight = base + 21 * count;
         return g;
     }
     static void bind(torch::Library &m) {
@@ -278,6 +341,17 @@ struct GaussianDataHolder : torch::CustomClassHolder {
             .def_readonly("grad_flat", &GaussianDataHolder::grad_flat)    // addition: [22N] view of all of the above
             .def_readonly("grad_delta", &GaussianDataHolder::grad_delta); // addition: per-launch gradient buffer (empty unless use_grad_delta): stored by the first grad launch after grad_delta_consumed(), added to by further ones
     }
+};
+
+const GaussianDataHolder::Param GaussianDataHolder::PARAMS[8] = {
+    {"scale", 3, 11, &GaussianDataHolder::scale, &GaussianDataHolder::dL_dscale, &egr_gaussians::scale, &egr_gaussians::dL_dscale},
+    {"rotation", 4, 17, &GaussianDataHolder::rotation, &GaussianDataHolder::dL_drotation, &egr_gaussians::rotation, &egr_gaussians::dL_drotation},
+    {"mean", 3, 14, &GaussianDataHolder::mean, &GaussianDataHolder::dL_dmean, &egr_gaussians::mean, &egr_gaussians::dL_dmean},
+    {"opacity", 1, 10, &GaussianDataHolder::opacity, &GaussianDataHolder::dL_dopacity, &egr_gaussians::opacity, &egr_gaussians::dL_dopacity},
+    {"rgb", 3, 0, &GaussianDataHolder::rgb, &GaussianDataHolder::dL_drgb, &egr_gaussians::rgb, &egr_gaussians::dL_drgb},
+    {"normal", 3, 3, &GaussianDataHolder::normal, &GaussianDataHolder::dL_dnormal, &egr_gaussians::normal, &egr_gaussians::dL_dnormal},
+    {"roughness", 1, 9, &GaussianDataHolder::roughness, &GaussianDataHolder::dL_droughness, &egr_gaussians::roughness, &egr_gaussians::dL_droughness},
+    {"f0", 3, 6, &GaussianDataHolder::f0, &GaussianDataHolder::dL_df0, &egr_gaussians::f0, &egr_gaussians::dL_df0},
 };
 
 // core/metadata.h:12-39
@@ -348,6 +422,9 @@ struct Raytracer : torch::CustomClassHolder {
     c10::intrusive_ptr<MetaDataHolder> meta_data;
     c10::intrusive_ptr<StatsDataHolder> stats_data;
     c10::intrusive_ptr<PPLLDataHolder> ppll_forward_data, ppll_backward_data;
+    // The device of the holders' tensors and of the context: the one current at construction. A method may be called with any device current: each one that reads
+    // current_stream(), allocates a tensor or hands the library a stream takes a c10::DeviceGuard for `device` first.
+    const c10::Device device;
     egr_context *ctx = nullptr;
     Tensor pixel_mask; // debug_set_pixel_mask: the mask the context points at
     // raytrace(targets=...) read its images in place and left framebuffer.target_* BEHIND them. The images are remembered (referenced, not copied) until the next
@@ -378,10 +455,9 @@ struct Raytracer : torch::CustomClassHolder {
           gaussian_data(c10::make_intrusive<GaussianDataHolder>()), meta_data(c10::make_intrusive<MetaDataHolder>(width_, height_)),
           stats_data(c10::make_intrusive<StatsDataHolder>(width_, height_)),
           ppll_forward_data(c10::make_intrusive<PPLLDataHolder>(width_, height_, forward_ppl_size)),
-          ppll_backward_data(c10::make_intrusive<PPLLDataHolder>(width_, height_, backward_ppl_size)) {
+          ppll_backward_data(c10::make_intrusive<PPLLDataHolder>(width_, height_, backward_ppl_size)), device(camera_data->origin.device()) {
         if (num_gaussians > 0) gaussian_data->resize(num_gaussians);
-        int device = (int)camera_data->origin.get_device();
-        int rc = egr_create(&ctx, device, (int)width, (int)height, forward_ppl_size, backward_ppl_size);
+        int rc = egr_create(&ctx, (int)device.index(), (int)width, (int)height, forward_ppl_size, backward_ppl_size);
         if (rc != 0) throw std::runtime_error("raytracer: egr_create failed (no usable HIP device? there is no CPU fallback)");
         egr_camera cam = camera_data->reify();
         egr_config cfg = config_data->reify();
@@ -398,16 +474,19 @@ struct Raytracer : torch::CustomClassHolder {
         if (ctx) egr_destroy(ctx);
     }
 
-    // The caller's eight tensors of a fused export / import, in the export order of gaussian_raytracer.py:41-50 (scale, rotation, mean, opacity, rgb, normal,
-    // roughness, f0): each a contiguous fp32 tensor on the tracer's device with the shape of the holder's. Checked before anything is launched.
-    void check_like_holder(const char *who, const std::vector<Tensor> &t) {
-        const Tensor *like[8] = {&gaussian_data->scale, &gaussian_data->rotation, &gaussian_data->mean, &gaussian_data->opacity, &gaussian_data->rgb, &gaussian_data->normal,
-                                 &gaussian_data->roughness, &gaussian_data->f0};
-        static const char *const names[8] = {"scale", "rotation", "mean", "opacity", "rgb", "normal", "roughness", "f0"};
-        TORCH_CHECK(t.size() == 8, who, ": eight tensors expected (scale, rotation, mean, opacity, rgb, normal, roughness, f0), got ", t.size());
-        for (int k = 0; k < 8; k++)
-            TORCH_CHECK(t[k].defined() && t[k].device() == like[k]->device() && t[k].scalar_type() == torch::kFloat32 && t[k].is_contiguous() && t[k].sizes() == like[k]->sizes(), who,
-                        ": '", names[k], "' must be a contiguous fp32 tensor ", like[k]->sizes(), " on the tracer's device");
+    // The caller's eight tensors of a fused export (update_bvh_from: parameter values) or import (import_into: gradients), in the order of GaussianDataHolder::PARAMS: each a
+    // contiguous fp32 tensor on the tracer's device with the shape of the holder's. Checked before anything is launched; returns them as the library takes them.
+    egr_gaussians like_holder(const char *who, const std::vector<Tensor> &t, bool gradients) {
+        TORCH_CHECK(t.size() == 8, who, ": eight tensors expected (", GaussianDataHolder::param_names(), "), got ", t.size());
+        egr_gaussians g{};
+        g.count = (uint32_t)gaussian_data->count;
+        for (int k = 0; k < 8; k++) {
+            const auto &p = GaussianDataHolder::PARAMS[k];
+            float *data = tensor_arg<float>(who, std::string("'") + p.name + "'", t[k], device, Shape(((*gaussian_data).*p.value).sizes().vec()));
+            if (gradients) g.*p.raw_grad = data;
+            else g.*p.raw_value = data;
+        }
+        return g;
     }
     // import_into (addition; grad mode only): the caller's eight gradient tensors, in the order of update_bvh_from's parameters. The launch's gather adds what it
     // leaves in the holder's gradients to them - `t.grad += holder.grad` for the eight, bit for bit, without the extra pass (egr_raytrace_import).
@@ -415,6 +494,7 @@ struct Raytracer : torch::CustomClassHolder {
     // (absent = zeros) or a contiguous fp32 [C,H,W] tensor on the tracer's device. The launch reads them where they are - no upload, framebuffer.target_* is
     // neither read nor written (egr_raytrace_targets). The caller keeps them alive and unmodified until the launch has completed on the current stream.
     void raytrace(c10::optional<std::vector<Tensor>> import_into, c10::optional<std::vector<c10::optional<Tensor>>> targets) { // raytracer.cpp:81-94
+        const c10::DeviceGuard guard(device);
         const bool grads = torch::autograd::GradMode::is_enabled();
         if (grads && !targets.has_value()) upload_behind_targets(); // this launch reads framebuffer.target_*
         if (!import_into.has_value() && !targets.has_value()) {
@@ -424,53 +504,31 @@ struct Raytracer : torch::CustomClassHolder {
         TORCH_CHECK(grads || !import_into.has_value(), "raytrace: import_into needs grad mode (a no-grad launch has no gradients to import)");
         TORCH_CHECK(grads || !targets.has_value(), "raytrace: targets need grad mode (a no-grad launch reads no target)");
         egr_gaussians dst{};
-        if (import_into.has_value()) dst = import_target("raytrace", *import_into);
-        const float *planes[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        if (targets.has_value()) {
-            TORCH_CHECK(targets->size() == 6, "raytrace: six targets expected (diffuse, specular, depth, normal, roughness, f0; None = absent), got ", targets->size());
-            const auto dev = framebuffer_data->output_rgb.device();
-            for (int k = 0; k < 6; k++) {
-                if (!(*targets)[k].has_value() || !(*targets)[k]->defined()) continue;
-                const Tensor &t = *(*targets)[k];
-                const std::vector<int64_t> want{TARGETS[k].channels, height, width};
-                TORCH_CHECK(t.device() == dev && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.sizes() == torch::IntArrayRef(want), "raytrace: target '", TARGETS[k].name,
-                            "' must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " (channel-major) on the tracer's device, got ", t.sizes(), " ", t.scalar_type(), " on ", t.device());
-                planes[k] = t.data_ptr<float>();
-            }
-        }
+        if (import_into.has_value()) dst = like_holder("raytrace", *import_into, true);
+        const float *planes[6];
+        if (targets.has_value()) six_targets("raytrace", *targets, {}, false, nullptr, planes);
         check(egr_raytrace_targets(ctx, 1, import_into.has_value() ? &dst : nullptr, targets.has_value() ? planes : nullptr, current_stream()), "raytrace");
         if (targets.has_value()) {
             for (int k = 0; k < 6; k++) behind_targets[k] = (*targets)[k].has_value() ? *(*targets)[k] : Tensor();
             framebuffer_targets_behind = true;
         }
     }
-    egr_gaussians import_target(const char *who, const std::vector<Tensor> &t) {
-        check_like_holder(who, t);
-        egr_gaussians dst{};
-        dst.count = (uint32_t)gaussian_data->count;
-        dst.dL_dscale = ptr<float>(t[0]), dst.dL_drotation = ptr<float>(t[1]), dst.dL_dmean = ptr<float>(t[2]), dst.dL_dopacity = ptr<float>(t[3]);
-        dst.dL_drgb = ptr<float>(t[4]), dst.dL_dnormal = ptr<float>(t[5]), dst.dL_droughness = ptr<float>(t[6]), dst.dL_df0 = ptr<float>(t[7]);
-        return dst;
-    }
-    void denoise() { check(egr_denoise(ctx, current_stream()), "denoise"); }
+    void denoise() { const c10::DeviceGuard guard(device); check(egr_denoise(ctx, current_stream()), "denoise"); }
     void reset_accumulators() { framebuffer_data->reset_accumulators(); }
     // fuse_live (addition; default = the reference's update_bvh()): the pass also writes the live per-gaussian records and the NEXT raytrace()
     // skips its own pass over the cloud - for callers that run update_bvh() and raytrace() back to back (egr_update_bvh_ex)
-    void update_bvh(bool fuse_live) { check(egr_update_bvh_ex(ctx, fuse_live ? EGR_UPDATE_FUSE_LIVE : 0u, current_stream()), "update_bvh"); }
+    void update_bvh(bool fuse_live) { const c10::DeviceGuard guard(device); check(egr_update_bvh_ex(ctx, fuse_live ? EGR_UPDATE_FUSE_LIVE : 0u, current_stream()), "update_bvh"); }
     // export + update_bvh(fuse_live) in one pass over the cloud (egr_update_bvh_from): the eight tensors hold the caller's current parameter values; the
     // holder's tensors then hold them too, as after the eight copy_ calls of gaussian_raytracer.py:41-50
     void update_bvh_from(Tensor scale, Tensor rotation, Tensor mean, Tensor opacity, Tensor rgb, Tensor normal, Tensor roughness, Tensor f0, bool fuse_live) {
-        const std::vector<Tensor> t{scale, rotation, mean, opacity, rgb, normal, roughness, f0};
-        check_like_holder("update_bvh_from", t);
+        const c10::DeviceGuard guard(device);
+        const egr_gaussians src = like_holder("update_bvh_from", {scale, rotation, mean, opacity, rgb, normal, roughness, f0}, false);
         TORCH_CHECK((reinterpret_cast<uintptr_t>(rotation.data_ptr()) & 15u) == 0, "update_bvh_from: 'rotation' must be 16-byte aligned");
-        egr_gaussians src{};
-        src.count = (uint32_t)gaussian_data->count;
-        src.scale = ptr<float>(scale), src.rotation = ptr<float>(rotation), src.mean = ptr<float>(mean), src.opacity = ptr<float>(opacity);
-        src.rgb = ptr<float>(rgb), src.normal = ptr<float>(normal), src.roughness = ptr<float>(roughness), src.f0 = ptr<float>(f0);
         check(egr_update_bvh_from(ctx, &src, fuse_live ? EGR_UPDATE_FUSE_LIVE : 0u, current_stream()), "update_bvh_from");
     }
-    void rebuild_bvh() { check(egr_rebuild_bvh(ctx, current_stream()), "rebuild_bvh"); }
+    void rebuild_bvh() { const c10::DeviceGuard guard(device); check(egr_rebuild_bvh(ctx, current_stream()), "rebuild_bvh"); }
     void resize(int64_t n) { // raytracer.cpp:112-120
+        const c10::DeviceGuard guard(device);
         gaussian_data->resize(n);
         egr_gaussians g = gaussian_data->reify();
         check(egr_set_gaussians(ctx, &g), "resize");
@@ -478,6 +536,7 @@ struct Raytracer : torch::CustomClassHolder {
     // ---- additions (not in the reference) ----
     void set_partition(int64_t rank, int64_t world) { check(egr_set_partition(ctx, (int)rank, (int)world), "set_partition"); }
     void use_grad_delta(bool on) { // see GaussianDataHolder::grad_delta
+        const c10::DeviceGuard guard(device);
         gaussian_data->set_use_delta(on);
         egr_gaussians g = gaussian_data->reify();
         check(egr_set_gaussians(ctx, &g), "use_grad_delta");
@@ -504,82 +563,86 @@ struct Raytracer : torch::CustomClassHolder {
         // tensor - a dataset's numpy pose - is converted on the host and its values go to the launch BY VALUE: the upload of a pageable tensor would wait for
         // the stream, once per training iteration)
         TORCH_CHECK(R.dim() == 2 && R.size(0) == 3 && R.size(1) == 3 && centre.numel() == 3, "set_camera: tensors [3,3] and [3] expected");
-        const auto dev = framebuffer_data->output_rgb.device();
-        const auto here = [&](const Tensor &t) { return t.is_cpu() ? t.to(torch::kFloat32).contiguous() : t.to(dev, torch::kFloat32).contiguous(); };
+        const c10::DeviceGuard guard(device);
+        const auto here = [&](const Tensor &t) { return t.is_cpu() ? t.to(torch::kFloat32).contiguous() : t.to(device, torch::kFloat32).contiguous(); };
         Tensor r = here(R), cc = here(centre);
         const unsigned flags = (r.is_cpu() ? EGR_CAMERA_ROTATION_ON_HOST : 0u) | (cc.is_cpu() ? EGR_CAMERA_CENTER_ON_HOST : 0u);
         check(egr_set_camera_from_dataset_ex(ctx, r.data_ptr<float>(), cc.data_ptr<float>(), (float)fov, (float)znear, (float)zfar, flags, current_stream()), "set_camera");
     }
     static constexpr struct { const char *name; int64_t channels; } TARGETS[6] = {{"diffuse", 3}, {"specular", 3}, {"depth", 1}, {"normal", 3}, {"roughness", 1}, {"f0", 3}}; // (the order of the C ABI's six target pointers)
-    // the six target images of a training view, channel-major ([C,H,W] contiguous fp32 CUDA tensors; an undefined / empty tensor = absent = zeros), written into
+    // THE walk over the six optional targets of a launch (`in`, in TARGETS' order): out[k] = the data of a contiguous fp32 [lead..., C, H, W] tensor on the tracer's device, or
+    // NULL for an absent one (None or undefined; with `empty_is_absent` an empty tensor too). With `converted` (set_targets_chw) only the shape is the caller's business: the
+    // tensor is moved to the tracer's device as fp32 and kept alive there.
+    void six_targets(const char *op, const std::vector<c10::optional<Tensor>> &in, const std::vector<int64_t> &lead, bool empty_is_absent, Tensor *converted, const float *out[6]) {
+        TORCH_CHECK(in.size() == 6, op, ": six targets expected (diffuse, specular, depth, normal, roughness, f0; None = absent), got ", in.size());
+        for (int k = 0; k < 6; k++) {
+            out[k] = nullptr;
+            if (!given(in[k]) || (empty_is_absent && in[k]->numel() == 0)) continue;
+            std::vector<int64_t> dims = lead;
+            dims.insert(dims.end(), {TARGETS[k].channels, height, width});
+            const Shape want(std::move(dims));
+            const std::string name = std::string("target '") + TARGETS[k].name + "' (channel-major)";
+            if (converted) { // (the reference's `buf.copy_(val.moveaxis(0, -1))` raises on any other shape and accepts any device: same here - a [H,W,C] tensor must not be read as [C,H,W])
+                TORCH_CHECK(want.fits(*in[k]), op, ": ", name, " must be a tensor ", want.text(), ", got ", in[k]->sizes());
+                converted[k] = in[k]->to(device, torch::kFloat32).contiguous();
+            }
+            out[k] = tensor_arg<float>(op, name, converted ? converted[k] : *in[k], device, want);
+        }
+    }
+    // the six target images of a training view, channel-major ([C,H,W] tensors of any device and float dtype; an undefined / empty tensor = absent = zeros), written into
     // the framebuffer's pixel-major target buffers for this context's own tiles in one launch (egr_set_targets_chw)
     void set_targets_chw(c10::optional<Tensor> diffuse, c10::optional<Tensor> specular, c10::optional<Tensor> depth, c10::optional<Tensor> normal, c10::optional<Tensor> roughness,
                          c10::optional<Tensor> f0) {
-        const c10::optional<Tensor> *in[6] = {&diffuse, &specular, &depth, &normal, &roughness, &f0};
+        const c10::DeviceGuard guard(device);
         Tensor keep[6];
         const float *p[6];
-        for (int b = 0; b < 6; b++) {
-            p[b] = nullptr;
-            if (!in[b]->has_value() || (*in[b])->numel() == 0) continue;
-            // (the reference's `buf.copy_(val.moveaxis(0, -1))` raises on any other shape and accepts any device: same here - a [H,W,C] tensor must not be read as [C,H,W])
-            const Tensor &t = **in[b];
-            TORCH_CHECK(t.dim() == 3 && t.size(0) == TARGETS[b].channels && t.size(1) == height && t.size(2) == width, "set_targets_chw: target ", b, " must be a [", TARGETS[b].channels, ",", height, ",", width, "] tensor (channel-major), got ", t.sizes());
-            keep[b] = t.to(framebuffer_data->output_rgb.device(), torch::kFloat32).contiguous();
-            p[b] = keep[b].data_ptr<float>();
-        }
+        six_targets("set_targets_chw", {diffuse, specular, depth, normal, roughness, f0}, {}, true, keep, p);
         check(egr_set_targets_chw(ctx, p[0], p[1], p[2], p[3], p[4], p[5], current_stream()), "set_targets_chw");
         forget_behind_targets(); // the framebuffer's targets are what the caller says again
     }
     // batched no-grad render (egr_render_views): R [V,3,3] (dataset c2w rotations), centers [V,3], fovy [V] (any device, moved like set_camera's),
-    // `outputs` = names among final / rgb / depth / normal / f0 / roughness. render_views allocates them (zeros) in the framebuffer's HWC layout with a
-    // leading V - final [V,H,W,3], the others [V,3,H,W,c] - and returns them in the order asked; render_views_into writes the caller's tensors instead.
-    static int64_t view_output_channels(const std::string &name) {
-        if (name == "final" || name == "rgb" || name == "normal" || name == "f0") return 3;
-        if (name == "depth" || name == "roughness") return 1;
-        return 0;
+    // `outputs` = names among VIEW_OUTPUTS. render_views allocates them (zeros) in the framebuffer's HWC layout with a leading V - final [V,H,W,3], the
+    // others [V,3,H,W,c] - and returns them in the order asked; render_views_into writes the caller's tensors instead.
+    struct ViewOutput { const char *name; int64_t channels; float *egr_view_batch::*slot; };
+    static constexpr ViewOutput VIEW_OUTPUTS[6] = {{"final", 3, &egr_view_batch::final},   {"rgb", 3, &egr_view_batch::rgb}, {"depth", 1, &egr_view_batch::depth},
+                                                   {"normal", 3, &egr_view_batch::normal}, {"f0", 3, &egr_view_batch::f0},   {"roughness", 1, &egr_view_batch::roughness}};
+    // (the table's entry of a name, and the shape of its buffer for V views: only the final image has no bounce steps)
+    std::pair<const ViewOutput *, std::vector<int64_t>> view_output(const std::string &name, int64_t V) const {
+        for (const ViewOutput &o : VIEW_OUTPUTS)
+            if (name == o.name) return {&o, o.slot == &egr_view_batch::final ? std::vector<int64_t>{V, height, width, o.channels} : std::vector<int64_t>{V, EGR_NUM_STEPS, height, width, o.channels}};
+        TORCH_CHECK(false, "render_views: unknown output '", name, "' (final, rgb, depth, normal, f0, roughness)");
     }
     // The three camera tensors of a batch, validated (`who` = the caller's name in the messages): (R, centers, fovy) as contiguous fp32 tensors on the tracer's device, and V.
     std::tuple<Tensor, Tensor, Tensor, int64_t> batch_cameras(const char *who, const Tensor &R, const Tensor &centers, const Tensor &fovy) {
         TORCH_CHECK(R.dim() == 3 && R.size(1) == 3 && R.size(2) == 3, who, ": R must be [V,3,3], got ", R.sizes());
         const int64_t V = R.size(0);
-        TORCH_CHECK(centers.dim() == 2 && centers.size(0) == V && centers.size(1) == 3, who, ": centers must be [V,3] = [", V, ",3], got ", centers.sizes());
-        TORCH_CHECK(fovy.dim() == 1 && fovy.size(0) == V, who, ": fovy must be [V] = [", V, "], got ", fovy.sizes());
-        const auto dev = framebuffer_data->output_rgb.device();
-        return {R.to(dev, torch::kFloat32).contiguous(), centers.to(dev, torch::kFloat32).contiguous(), fovy.to(dev, torch::kFloat32).contiguous(), V};
+        TORCH_CHECK(Shape({V, 3}).fits(centers), who, ": centers must be [V,3] = ", Shape({V, 3}).text(), ", got ", centers.sizes());
+        TORCH_CHECK(Shape({V}).fits(fovy), who, ": fovy must be [V] = ", Shape({V}).text(), ", got ", fovy.sizes());
+        return {R.to(device, torch::kFloat32).contiguous(), centers.to(device, torch::kFloat32).contiguous(), fovy.to(device, torch::kFloat32).contiguous(), V};
     }
     std::vector<Tensor> render_views(Tensor R, Tensor centers, Tensor fovy, double znear, double zfar, int64_t samples_per_view, std::vector<std::string> outputs) {
-        const auto opts = framebuffer_data->output_rgb.options();
+        const c10::DeviceGuard guard(device);
         const int64_t V = R.dim() == 3 ? R.size(0) : 0;
         std::vector<Tensor> bufs;
-        for (const auto &name : outputs) {
-            const int64_t ch = view_output_channels(name);
-            TORCH_CHECK(ch != 0, "render_views: unknown output '", name, "' (final, rgb, depth, normal, f0, roughness)");
-            bufs.push_back(name == "final" ? torch::zeros({V, height, width, 3}, opts) : torch::zeros({V, EGR_NUM_STEPS, height, width, ch}, opts));
-        }
+        for (const auto &name : outputs) bufs.push_back(torch::zeros(view_output(name, V).second, framebuffer_data->output_rgb.options()));
         render_views_into(R, centers, fovy, znear, zfar, samples_per_view, outputs, bufs);
         return bufs;
     }
     void render_views_into(Tensor R, Tensor centers, Tensor fovy, double znear, double zfar, int64_t samples_per_view, std::vector<std::string> outputs,
                            std::vector<Tensor> buffers) {
+        const c10::DeviceGuard guard(device);
         const auto [r, cc, fv, V] = batch_cameras("render_views", R, centers, fovy);
         TORCH_CHECK(samples_per_view >= 0 && samples_per_view <= 0x7FFFFFFF, "render_views: samples_per_view out of range");
         TORCH_CHECK(outputs.size() == buffers.size(), "render_views_into: one buffer per output name expected");
-        const auto dev = framebuffer_data->output_rgb.device();
         egr_view_batch b{};
         b.num_views = (uint32_t)V, b.samples_per_view = (uint32_t)samples_per_view;
         b.rotation_c2w_dataset = r.data_ptr<float>(), b.camera_center = cc.data_ptr<float>(), b.vertical_fov_radians = fv.data_ptr<float>();
         b.znear = (float)znear, b.zfar = (float)zfar;
         for (size_t i = 0; i < outputs.size(); i++) {
-            const std::string &name = outputs[i];
-            const int64_t ch = view_output_channels(name);
-            TORCH_CHECK(ch != 0, "render_views: unknown output '", name, "' (final, rgb, depth, normal, f0, roughness)");
-            const Tensor &t = buffers[i];
-            const std::vector<int64_t> want = name == "final" ? std::vector<int64_t>{V, height, width, 3} : std::vector<int64_t>{V, EGR_NUM_STEPS, height, width, ch};
-            TORCH_CHECK(t.device() == dev && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.sizes() == torch::IntArrayRef(want), "render_views: output '", name,
-                        "' must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " on the tracer's device, got ", t.sizes());
-            float **slot = name == "final" ? &b.final : name == "rgb" ? &b.rgb : name == "depth" ? &b.depth : name == "normal" ? &b.normal : name == "f0" ? &b.f0 : &b.roughness;
-            TORCH_CHECK(*slot == nullptr, "render_views: output '", name, "' requested twice");
-            *slot = t.data_ptr<float>();
+            const auto [o, shape] = view_output(outputs[i], V);
+            float *data = tensor_arg<float>("render_views", "output '" + outputs[i] + "'", buffers[i], device, Shape(shape));
+            TORCH_CHECK(b.*o->slot == nullptr, "render_views: output '", outputs[i], "' requested twice");
+            b.*o->slot = data;
         }
         check(egr_render_views(ctx, &b, current_stream()), "render_views");
     }
@@ -587,11 +650,10 @@ struct Raytracer : torch::CustomClassHolder {
     // tracer's device (editing.EditableGaussians.selection_mask), bits = the requested selection bits in output order. Returns (masks [K,H,W] fp32,
     // hit int32 [H,W] - bit j = masks[j] != 0, output index 31 is the sign bit -, top int32 [H,W]). A query: nothing else of the tracer changes.
     std::tuple<Tensor, Tensor, Tensor> object_masks(Tensor R, Tensor center, double fovy, double znear, double zfar, Tensor row_bits, std::vector<int64_t> bits) {
+        const c10::DeviceGuard guard(device);
         TORCH_CHECK(R.dim() == 2 && R.size(0) == 3 && R.size(1) == 3 && center.numel() == 3, "object_masks: R [3,3] and center [3] expected");
-        const auto dev = framebuffer_data->output_rgb.device();
-        TORCH_CHECK(row_bits.device() == dev && row_bits.scalar_type() == torch::kInt32 && row_bits.dim() == 1 && row_bits.is_contiguous() &&
-                        row_bits.size(0) == gaussian_data->mean.size(0),
-                    "object_masks: row_bits must be a contiguous int32 tensor [", gaussian_data->mean.size(0), "] on the tracer's device, got ", row_bits.sizes(), " ", row_bits.scalar_type(), " on ", row_bits.device());
+        egr_object_mask_query q{};
+        q.row_bits = reinterpret_cast<const uint32_t *>(tensor_arg<int32_t>("object_masks", "row_bits", row_bits, device, {gaussian_data->mean.size(0)}));
         TORCH_CHECK(!bits.empty() && bits.size() <= EGR_MAX_EDIT_OBJECTS, "object_masks: 1 .. ", EGR_MAX_EDIT_OBJECTS, " bits expected, got ", bits.size());
         uint8_t b8[EGR_MAX_EDIT_OBJECTS];
         for (size_t j = 0; j < bits.size(); j++) {
@@ -603,10 +665,8 @@ struct Raytracer : torch::CustomClassHolder {
         const auto fopts = framebuffer_data->output_rgb.options();
         Tensor masks = torch::zeros({(int64_t)bits.size(), height, width}, fopts);
         Tensor hit = torch::zeros({height, width}, fopts.dtype(torch::kInt32)), top = torch::full({height, width}, -1, fopts.dtype(torch::kInt32));
-        egr_object_mask_query q{};
         q.rotation_c2w_dataset = r.data_ptr<float>(), q.camera_center = cc.data_ptr<float>(), q.vertical_fov_radians = fv.data_ptr<float>();
         q.znear = (float)znear, q.zfar = (float)zfar;
-        q.row_bits = reinterpret_cast<const uint32_t *>(row_bits.data_ptr<int32_t>());
         q.bits = b8, q.num_bits = (uint32_t)bits.size();
         q.masks = masks.data_ptr<float>(), q.hit = reinterpret_cast<uint32_t *>(hit.data_ptr<int32_t>()), q.top = top.data_ptr<int32_t>();
         check(egr_object_masks(ctx, &q, current_stream()), "object_masks");
@@ -623,24 +683,17 @@ struct Raytracer : torch::CustomClassHolder {
     void train_views_import(Tensor R, Tensor centers, Tensor fovy, double znear, double zfar, c10::optional<Tensor> diffuse, c10::optional<Tensor> specular,
                             c10::optional<Tensor> depth, c10::optional<Tensor> normal, c10::optional<Tensor> roughness, c10::optional<Tensor> f0,
                             c10::optional<std::vector<Tensor>> import_into) {
+        const c10::DeviceGuard guard(device);
         const auto [r, cc, fv, V] = batch_cameras("train_views", R, centers, fovy);
-        const auto dev = framebuffer_data->output_rgb.device();
         egr_train_batch b{};
         b.num_views = (uint32_t)V;
         b.rotation_c2w_dataset = r.data_ptr<float>(), b.camera_center = cc.data_ptr<float>(), b.vertical_fov_radians = fv.data_ptr<float>();
         b.znear = (float)znear, b.zfar = (float)zfar;
-        const c10::optional<Tensor> *in[6] = {&diffuse, &specular, &depth, &normal, &roughness, &f0};
-        const float **slot[6] = {&b.target_diffuse, &b.target_specular, &b.target_depth, &b.target_normal, &b.target_roughness, &b.target_f0};
-        for (int k = 0; k < 6; k++) {
-            if (!in[k]->has_value() || !(*in[k])->defined() || (*in[k])->numel() == 0) continue;
-            const Tensor &t = **in[k];
-            const std::vector<int64_t> want{V, TARGETS[k].channels, height, width};
-            TORCH_CHECK(t.device() == dev && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.sizes() == torch::IntArrayRef(want), "train_views: target '", TARGETS[k].name,
-                        "' must be a contiguous fp32 tensor ", torch::IntArrayRef(want), " (channel-major) on the tracer's device, got ", t.sizes(), " ", t.scalar_type(), " on ", t.device());
-            *slot[k] = t.data_ptr<float>();
-        }
+        const float *p[6];
+        six_targets("train_views", {diffuse, specular, depth, normal, roughness, f0}, {V}, true, nullptr, p);
+        b.target_diffuse = p[0], b.target_specular = p[1], b.target_depth = p[2], b.target_normal = p[3], b.target_roughness = p[4], b.target_f0 = p[5];
         if (import_into.has_value()) {
-            const egr_gaussians dst = import_target("train_views", *import_into);
+            const egr_gaussians dst = like_holder("train_views", *import_into, true);
             check(egr_train_views_import(ctx, &b, &dst, current_stream()), "train_views");
         } else {
             check(egr_train_views(ctx, &b, current_stream()), "train_views");
@@ -650,19 +703,14 @@ struct Raytracer : torch::CustomClassHolder {
     // as contiguous fp32 tensors on the tracer's device. Returns a new [V,H,W,3] tensor; each view is bit-equal to denoise() on a framebuffer that holds the same
     // final / normal. The framebuffer is not touched.
     Tensor denoise_views(Tensor final, Tensor normal) {
-        const auto dev = framebuffer_data->output_rgb.device();
-        TORCH_CHECK(final.dim() == 4 && final.size(1) == height && final.size(2) == width && final.size(3) == 3, "denoise_views: final must be [V,", height, ",", width, ",3], got ", final.sizes());
+        const c10::DeviceGuard guard(device);
+        const float *image = tensor_arg<float>("denoise_views", "final", final, device, {-1, height, width, 3});
         const int64_t V = final.size(0);
-        const bool steps = normal.dim() == 5;
-        const std::vector<int64_t> want = steps ? std::vector<int64_t>{V, EGR_NUM_STEPS, height, width, 3} : std::vector<int64_t>{V, height, width, 3};
-        TORCH_CHECK(normal.sizes() == torch::IntArrayRef(want), "denoise_views: normal must be [V,3,H,W,3] or [V,H,W,3] with V = ", V, ", got ", normal.sizes());
-        for (const Tensor *t : {&final, &normal})
-            TORCH_CHECK(t->device() == dev && t->scalar_type() == torch::kFloat32 && t->is_contiguous(), "denoise_views: contiguous fp32 tensors on the tracer's device expected");
+        const bool steps = normal.dim() == 5; // ([V,3,H,W,3], or the packed [V,H,W,3])
+        const float *guide = tensor_arg<float>("denoise_views", "normal", normal, device, steps ? Shape{V, EGR_NUM_STEPS, height, width, 3} : Shape{V, height, width, 3});
         Tensor out = torch::empty_like(final);
         if (V == 0) return out;
-        check(egr_denoise_views(ctx, (uint32_t)V, final.data_ptr<float>(), normal.data_ptr<float>(), (size_t)((steps ? EGR_NUM_STEPS : 1) * height * width * 3), out.data_ptr<float>(),
-                                current_stream()),
-              "denoise_views");
+        check(egr_denoise_views(ctx, (uint32_t)V, image, guide, (size_t)((steps ? EGR_NUM_STEPS : 1) * height * width * 3), out.data_ptr<float>(), current_stream()), "denoise_views");
         return out;
     }
     void set_batch_frames(int64_t n) { TORCH_CHECK(n >= 1 && n <= 0x7FFFFFFF && egr_set_batch_frames(ctx, (int)n) == 0, "set_batch_frames: a frame count >= 1 expected"); }
@@ -671,6 +719,7 @@ struct Raytracer : torch::CustomClassHolder {
     void set_team_help_auto() { TORCH_CHECK(egr_set_team_help(ctx, -1) == 0, "set_team_help_auto failed"); } // on for under-filled ranks of a partition only (egr_set_team_help(-1))
     void set_strands(int64_t n) { TORCH_CHECK(egr_set_strands(ctx, (int)n) == 0, "set_strands: only 1 is accepted (strands were removed; every launch runs on the caller's stream)"); }
     std::vector<int64_t> get_counters() { // synchronises
+        const c10::DeviceGuard guard(device);
         egr_counters c{};
         check(egr_get_counters(ctx, &c, current_stream()), "get_counters");
         // [rays0..2, candidates0..2, composited0..2, lifetime_rays, lifetime_launches, status, bvh_depth, bucket_records, device_bytes, arena_blocks_used, arena_blocks_cap,
@@ -681,7 +730,7 @@ struct Raytracer : torch::CustomClassHolder {
                 (int64_t)c.device_bytes, (int64_t)c.arena_blocks_used, (int64_t)c.arena_blocks_cap, (int64_t)c.ext_blocks_used, (int64_t)c.ext_blocks_cap,
                 (int64_t)c.accepted[0], (int64_t)c.accepted[1], (int64_t)c.accepted[2]};
     }
-    void reset_lifetime_counters() { check(egr_reset_lifetime_counters(ctx, current_stream()), "reset_lifetime_counters"); }
+    void reset_lifetime_counters() { const c10::DeviceGuard guard(device); check(egr_reset_lifetime_counters(ctx, current_stream()), "reset_lifetime_counters"); }
     void enable_timing(bool on) { egr_enable_timing(ctx, on ? 1 : 0); }
     double last_raytrace_ms() { return egr_last_raytrace_ms(ctx); }
     double last_update_bvh_ms() { return egr_last_update_bvh_ms(ctx); }
@@ -694,24 +743,28 @@ struct Raytracer : torch::CustomClassHolder {
         return out;
     }
     Tensor debug_step_hits() { // [3,H,W] int32 on the host: composited hits per bounce step of the last grad launch
+        const c10::DeviceGuard guard(device);
         Tensor t = torch::zeros({EGR_NUM_STEPS, height, width}, torch::kInt32);
         check(egr_debug_get_step_hits(ctx, t.data_ptr<int32_t>(), current_stream()), "debug_step_hits");
         return t;
     }
     Tensor debug_hit_sequence_hash() { // [3,H,W] int64 (the bits of the uint64 hashes) on the host: ordered composited gaussian ids per pixel and step of the last grad launch
+        const c10::DeviceGuard guard(device);
         Tensor t = torch::zeros({EGR_NUM_STEPS, height, width}, torch::kInt64);
         check(egr_debug_get_hit_sequence_hash(ctx, reinterpret_cast<uint64_t *>(t.data_ptr<int64_t>()), current_stream()), "debug_hit_sequence_hash");
         return t;
     }
-    int64_t check_bvh() { return egr_debug_check_bvh(ctx, current_stream()); }
+    int64_t check_bvh() { const c10::DeviceGuard guard(device); return egr_debug_check_bvh(ctx, current_stream()); }
     std::string last_error() { return egr_last_error(ctx); }
     std::vector<Tensor> debug_instances() {
+        const c10::DeviceGuard guard(device);
         int64_t n = gaussian_data->count;
         Tensor M = torch::zeros({n, 3, 4}, torch::kFloat32), W = torch::zeros({n, 3, 4}, torch::kFloat32), A = torch::zeros({n, 6}, torch::kFloat32);
         check(egr_debug_get_instances(ctx, M.data_ptr<float>(), W.data_ptr<float>(), A.data_ptr<float>(), current_stream()), "debug_instances");
         return {M, W, A};
     }
     Tensor debug_backward_records() { // [n,4,4] float32 on the host, by gaussian id (egr_debug_get_backward_records)
+        const c10::DeviceGuard guard(device);
         float frame[6];
         uint32_t info[4] = {0u, 0u, 0u, 0u}; // (info[3]: the count the tree was built for - the rows the library copies, whatever the holder was resized to since)
         check(egr_debug_get_bvh_state(ctx, frame, info, current_stream()), "debug_backward_records");
@@ -720,6 +773,7 @@ struct Raytracer : torch::CustomClassHolder {
         return t;
     }
     std::tuple<Tensor, Tensor> debug_bvh_state() { // (float32[6]: the build frame's origin xyz and cells per world unit xyz; int64[4]: out_of_frame flag, wide nodes, depth, n built) on the host
+        const c10::DeviceGuard guard(device);
         Tensor f = torch::zeros({6}, torch::kFloat32), i = torch::zeros({4}, torch::kInt64);
         uint32_t info[4] = {0u, 0u, 0u, 0u};
         check(egr_debug_get_bvh_state(ctx, f.data_ptr<float>(), info, current_stream()), "debug_bvh_state");
@@ -729,6 +783,7 @@ struct Raytracer : torch::CustomClassHolder {
     // The built tree on the host (egr_debug_get_tree), in this order: keys int64 [n] (the bits of the uint64 keys), gid_of_pos int32 [n], pos_of_gid int32 [n],
     // left int32 [n-1], right int32 [n-1], dp float32 [n-1,16], wnodes int32 [nw,8,4] (the bits of the uint32 words), bsph float32 [n,4], level_start int32 [depth+1]
     std::vector<Tensor> debug_tree() {
+        const c10::DeviceGuard guard(device);
         float frame[6];
         uint32_t info[4] = {0u, 0u, 0u, 0u};
         check(egr_debug_get_bvh_state(ctx, frame, info, current_stream()), "debug_tree");
@@ -833,68 +888,6 @@ struct Raytracer : torch::CustomClassHolder {
 // ---- The context-free ops (torch.ops.egr.*, torch.ops.simple_knn.distCUDA2): tensors in, one library call each. Every op checks its tensor arguments through
 // tensor_arg (words_arg for the lists of 4-byte rows) and takes a c10::DeviceGuard for the tensors' device BEFORE it allocates an output or reads
 // current_stream(): the tensors need not live on the current device, and the library is handed the stream of the device it is told to run on.
-namespace {
-bool given(const c10::optional<Tensor> &t) { return t.has_value() && t->defined(); }
-// (a Tensor[] cannot hold None: there an undefined or empty tensor is an absent entry)
-c10::optional<Tensor> unless_empty(const Tensor &t) { return t.defined() && t.numel() ? c10::optional<Tensor>(t) : c10::nullopt; }
-
-// What a tensor argument must measure: a full shape (-1: any size in that dimension), at least so many rows of a trailing shape, or a number of elements in any shape.
-struct Shape {
-    std::vector<int64_t> dims;
-    int64_t min_rows = 0, numel = -1;
-    Shape(std::initializer_list<int64_t> d) : dims(d) {}
-    Shape(std::vector<int64_t> d) : dims(std::move(d)) {}
-    static Shape at_least(int64_t rows, std::vector<int64_t> trailing) {
-        trailing.insert(trailing.begin(), -1);
-        Shape s(std::move(trailing));
-        s.min_rows = rows;
-        return s;
-    }
-    static Shape elements(int64_t n) {
-        Shape s(std::vector<int64_t>{});
-        s.numel = n;
-        return s;
-    }
-    bool fits(const Tensor &t) const {
-        if (numel >= 0) return t.numel() == numel;
-        if (t.dim() != (int64_t)dims.size() || (min_rows > 0 && t.size(0) < min_rows)) return false;
-        for (size_t d = 0; d < dims.size(); d++)
-            if (dims[d] >= 0 && t.size((int64_t)d) != dims[d]) return false;
-        return true;
-    }
-    std::string text() const {
-        if (numel >= 0) return "of " + std::to_string(numel) + " elements";
-        std::string s = "[";
-        for (size_t d = 0; d < dims.size(); d++)
-            s += (d ? ", " : "") + (dims[d] >= 0 ? std::to_string(dims[d]) : d == 0 && min_rows > 0 ? ">= " + std::to_string(min_rows) : std::string("*"));
-        return s + "]";
-    }
-};
-
-// THE argument check: a tensor of T's dtype, contiguous, on `dev`, of the wanted shape -> its data pointer. An absent one (None, or undefined) -> NULL if it is
-// optional, an error if it is required. Errors carry the op's and the argument's name.
-template <class T> T *tensor_arg(const char *op, const std::string &name, const c10::optional<Tensor> &t, c10::Device dev, const Shape &want, bool required = true) {
-    if (!given(t)) {
-        TORCH_CHECK(!required, op, ": ", name, " is required");
-        return nullptr;
-    }
-    constexpr c10::ScalarType dtype = c10::CppTypeToScalarType<T>::value;
-    TORCH_CHECK(t->is_cuda() && t->device() == dev && t->scalar_type() == dtype && t->is_contiguous() && want.fits(*t), op, ": ", name, " must be a contiguous ", dtype, " tensor ",
-                want.text(), " on ", dev, ", got ", t->scalar_type(), " ", t->sizes(), t->is_contiguous() ? "" : " (not contiguous)", " on ", t->device());
-    return t->data_ptr<T>();
-}
-// An entry of the tensor lists of prune_gather and grow_append: n rows of 4-byte elements of any dtype, moved as bits.
-void *words_arg(const char *op, const char *list, size_t k, const Tensor &t, c10::Device dev, int64_t n) {
-    TORCH_CHECK(t.defined() && t.is_cuda() && t.device() == dev && t.is_contiguous() && t.element_size() == 4 && t.dim() >= 1 && t.size(0) == n, op, ": ", list, "[", k,
-                "] must be a contiguous tensor of 4-byte elements with ", n, " rows on ", dev, " (contiguous GPU tensors of 4-byte elements with the same leading size are required)");
-    return t.data_ptr();
-}
-// The device of an op: that of the tensor that leads its arguments.
-c10::Device gpu_of(const char *op, const char *name, const Tensor &t) {
-    TORCH_CHECK(t.defined() && t.is_cuda(), op, ": ", name, " must be a GPU tensor (there is no CPU path)");
-    return t.device();
-}
-} // namespace
 
 // simple_knn._C.distCUDA2 (gaussian_model.py:17): float CUDA(HIP) tensor [N,3] -> [N] mean squared distance to the 3 nearest
 // neighbours. Registered as torch.ops.simple_knn.distCUDA2; the package's simple_knn.py re-exports it under the reference's name.

@@ -105,6 +105,7 @@ class GaussianRaytracer:
             kw["ppll_backward_size"] = int(ppll_backward_size)
         n = pc.get_scaling.shape[0]
         self.cuda_module = make_raytracer(image_width, image_height, n, **kw)
+        self.device = self.cuda_module.get_framebuffer().output_rgb.device  # the tracer's: it may be called with any device current
         if self.cuda_module.get_gaussians().mean.shape[0] != n:  # n == 0: the native holder starts with count = 1 (core/gaussians.h:31)
             self.cuda_module.resize(n)
         self.rank, self.world_size = rank, world_size
@@ -305,12 +306,12 @@ def render(camera, raytracer: GaussianRaytracer, targets_available=True, force_u
 VIEW_OUTPUTS = ("final", "rgb", "depth", "normal", "roughness", "f0")
 
 
-def _stack_cameras(cameras):
-    """The cameras of a batch as the tensors the batch launches take: R [V,3,3] (dataset c2w rotations), centers [V,3], fovy [V]."""
+def _stack_cameras(cameras, device):
+    """The cameras of a batch as the tensors the batch launches take, on `device`: R [V,3,3] (dataset c2w rotations), centers [V,3], fovy [V]."""
     as_t = lambda x: torch.from_numpy(np.asarray(x)).float() if isinstance(x, np.ndarray) else torch.as_tensor(x).float()
-    R = torch.stack([as_t(c.R).cuda() for c in cameras]) if cameras else torch.zeros((0, 3, 3), device="cuda")
-    centers = torch.stack([as_t(c.camera_center).cuda() for c in cameras]) if cameras else torch.zeros((0, 3), device="cuda")
-    fovy = torch.tensor([float(c.FoVy) for c in cameras], dtype=torch.float32, device="cuda")
+    R = torch.stack([as_t(c.R).to(device) for c in cameras]) if cameras else torch.zeros((0, 3, 3), device=device)
+    centers = torch.stack([as_t(c.camera_center).to(device) for c in cameras]) if cameras else torch.zeros((0, 3), device=device)
+    fovy = torch.tensor([float(c.FoVy) for c in cameras], dtype=torch.float32, device=device)
     return R, centers, fovy
 
 
@@ -323,7 +324,7 @@ def render_views_raw(cameras, raytracer: GaussianRaytracer, spp=1, outputs=VIEW_
         outputs = ("final",) + outputs  # (the library always writes it)
     m = raytracer.cuda_module
     with torch.no_grad():
-        R, centers, fovy = _stack_cameras(cameras)
+        R, centers, fovy = _stack_cameras(cameras, raytracer.device)
         raytracer._export_param_values()
         if force_update_bvh:
             m.update_bvh(True)
@@ -366,15 +367,15 @@ def train_views(cameras, raytracer: GaussianRaytracer, targets_available=True, z
     cameras = list(cameras)
     W, H = raytracer.image_width, raytracer.image_height
     with torch.no_grad():
-        R, centers, fovy = _stack_cameras(cameras)
+        R, centers, fovy = _stack_cameras(cameras, raytracer.device)
         targets = []
         for _, attr, ch in TRAIN_TARGETS:
             imgs = [getattr(c, attr, None) if targets_available else None for c in cameras]
             if all(t is None for t in imgs):
                 targets.append(None)  # absent for every view: the library reads zeros
                 continue
-            zeros = torch.zeros((ch, H, W), dtype=torch.float32, device="cuda")
-            targets.append(torch.stack([zeros if t is None else torch.as_tensor(t).to("cuda", torch.float32) for t in imgs]).contiguous())
+            zeros = torch.zeros((ch, H, W), dtype=torch.float32, device=raytracer.device)
+            targets.append(torch.stack([zeros if t is None else torch.as_tensor(t).to(raytracer.device, torch.float32) for t in imgs]).contiguous())
     train_stacked_views(raytracer, R, centers, fovy, targets, znear, zfar)
 
 

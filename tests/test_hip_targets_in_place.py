@@ -123,7 +123,8 @@ def test_the_binding_refuses_what_it_cannot_read_in_place(ren, syn):
     before = int(m.get_metadata().total_num_calls)
     m.update_bvh(True)
     with torch.enable_grad():
-        for k, bad, words in ((0, imgs[0].cpu(), "tracer's device"), (3, imgs[3].double(), "contiguous fp32"), (5, imgs[5].moveaxis(0, -1).contiguous().moveaxis(-1, 0), "contiguous fp32"),
+        for k, bad, words in ((0, imgs[0].cpu(), r"raytrace: target 'diffuse' .* on cuda:\d+, got .* on cpu"), (3, imgs[3].double(), "raytrace: target 'normal' .* contiguous Float tensor .*, got Double"),
+                              (5, imgs[5].moveaxis(0, -1).contiguous().moveaxis(-1, 0), r"raytrace: target 'f0' .* contiguous Float tensor .*\(not contiguous\)"),
                               (2, imgs[0], "channel-major"), (4, imgs[4][:, :, : W - 1].contiguous(), "channel-major")):
             with pytest.raises(RuntimeError, match=words):
                 m.raytrace(None, imgs[:k] + [bad] + imgs[k + 1:])

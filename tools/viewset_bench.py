@@ -171,7 +171,7 @@ def bench_gather_and_step(a, result, parts):
         cpu_cams.append(CpuHalfCamera(ren.camera_from_RT(i.R, i.T, i.FovY), halfs))
 
     def stack_today(cams):
-        R, centers, fovy = ren._stack_cameras(cams)
+        R, centers, fovy = ren._stack_cameras(cams, "cuda")
         return [torch.stack([getattr(c, attr) for c in cams]).contiguous() for _, attr, _ in ren.TRAIN_TARGETS], R, centers, fovy
 
     if "gather" in parts:
