@@ -5,7 +5,7 @@
 //
 // Included by trace.hip once, inside its anonymous namespace. From the definitions above the include it uses: wave_next_task, wave_max_u32, uniform_u32,
 // ChainTask / decode_task, primary_ray, wave_sync (EGR_BWD_SYNC), lds_peek, lds_poke, the table and record constants (EGR_GT_*, EGR_REC*, PC_*),
-// wide_add_wave, grad_table_flush, primary_presum, primary_table_add, hit_geometry_fn, bounce_batch, BwdTeamShared and bwd_team_help; from
+// wide_add_wave, grad_table_flush, primary_table_add, hit_geometry_fn, bounce_batch, BwdTeamShared and bwd_team_help; from
 // egr_state.hpp task_geom and state_of; from egr_diag.hpp the EGR_STATS / EGR_TIMES statement macros.
 #pragma once
 
@@ -19,7 +19,7 @@ template <int TEAM> struct BwdWave {
     int lane, wv;
     uint32_t *gt_keys; // the primary step's table of this wave (trace.hip: primary_table_add)
     float *gt_vals;
-    uint32_t *gt_claim; // which lane adds to a slot in this round
+    uint32_t *gt_claim; // per slot: the last lane of the current row that came to it (empty between rows)
     float4 *stage;      // records on their way out (wide_add_wave)
     BwdTeamShared<TEAM> &bteam;
     uint4 *bitems; // [4 x 64] bounce steps: (ray, dL/dalpha, record, weight) of the hits of a chunk of four rows
@@ -218,6 +218,7 @@ template <int TEAM> EGR_DI uint32_t primary_hits(const DeviceView &v, BwdWave<TE
     float prev_rough = 0, w_rough = 0, prev_depth = 0, w_depth = 0;
     const uint32_t nblocks = (max_hits + EGR_HIT_BLOCK_ROWS - 1) / EGR_HIT_BLOCK_ROWS;
     EGR_STATS(unsigned long long bt_math = 0ull, bt_table = 0ull, bt_wide = 0ull, bt_rows = 0ull;) // s_memtime per phase of a hit row: [math, neighbour combine + LDS table, wide adds] + the tile's table flush
+    EGR_STATS(unsigned long long bt_lanes = 0ull, bt_steps = 0ull, bt_leaders = 0ull;) // of the rows' groups (trace.hip: primary_table_add): lanes with a hit, pointer-jumping steps, leaders
     for (uint32_t b = nblocks; b-- > 0;) {
         const float4 *rows = v.hit_arena + (size_t)blk * (EGR_HIT_BLOCK_ROWS + 1) * EGR_WAVE;
         int pf_row = -1; // the row of this block whose arena entry `rec_pf` holds (requested while the row before it was worked off)
@@ -226,7 +227,7 @@ template <int TEAM> EGR_DI uint32_t primary_hits(const DeviceView &v, BwdWave<TE
             const uint32_t it = b * EGR_HIT_BLOCK_ROWS + (uint32_t)row;
             if (it >= max_hits) continue;
             // a hit without a table slot leaves the divergent block with its gradients in `gx`: the wide add that follows is a wave-level operation
-            bool direct = false, want = false; // want: this lane's contribution looks for a slot of the table
+            bool direct = false, want = false; // want: this lane holds a hit of this row
             uint32_t dpos = 0;
             float gx[EGR_GT_COMPS]; // this hit's gradient components, PC_* order (what leaves the lane when `direct`: a primary hit without a table slot)
             EGR_STATS(const unsigned long long bt0 = __builtin_amdgcn_s_memtime(); unsigned long long bt1 = bt0; bt_rows++;)
@@ -290,13 +291,15 @@ template <int TEAM> EGR_DI uint32_t primary_hits(const DeviceView &v, BwdWave<TE
                 gx[PC_NORMAL] = d_n.x, gx[PC_NORMAL + 1] = d_n.y, gx[PC_NORMAL + 2] = d_n.z;
                 gx[PC_F0] = d_f0.x, gx[PC_F0 + 1] = d_f0.y, gx[PC_F0 + 2] = d_f0.z, gx[PC_ROUGH] = d_rough;
                 EGR_STATS(bt1 = __builtin_amdgcn_s_memtime();)
-                // primary hits go through the wave's LDS table (trace.hip: primary_presum here, primary_table_add below, outside this divergent
-                // block: a full table is emptied by the whole wave). (Bounce tiles are incoherent - an LDS table removed only 25 % of the
+                // primary hits go through the wave's LDS table (trace.hip: primary_table_add below, outside this divergent block: the row's sums pull
+                // across the wave, and a full table is emptied by the whole wave). (Bounce tiles are incoherent - an LDS table removed only 25 % of the
                 // contributions at 15 ds_add_f32 per hit: bounce_batch sends a hit's 14 components straight to the gradient row as one record.)
                 dpos = pos;
-                want = primary_presum(pos, gx, lane);
+                want = true;
             }
-            direct = primary_table_add(v, want, dpos, gx, gt_keys, gt_vals, gt_claim, stage, lane, records);
+            uint32_t jump_steps, row_leaders;
+            direct = primary_table_add(v, want, dpos, gx, gt_keys, gt_vals, gt_claim, stage, lane, records, jump_steps, row_leaders);
+            EGR_STATS(bt_lanes += (unsigned long long)__popcll(__ballot(want)); bt_steps += jump_steps; bt_leaders += row_leaders;)
             EGR_STATS(const unsigned long long bt2 = __builtin_amdgcn_s_memtime(); bt_math += bt1 - bt0; bt_table += bt2 - bt1;)
             if (__ballot(direct) != 0ull) {
                 float lo[EGR_REC0_COMPS], hi[EGR_REC1_COMPS]; // one record per segment of the row, like a flushed slot
@@ -317,6 +320,8 @@ template <int TEAM> EGR_DI uint32_t primary_hits(const DeviceView &v, BwdWave<TE
     EGR_STATS(if (lane == 0) {
         unsigned long long *d = diag64(v.control, DG_BWD_MATH_CYC);
         atomicAdd(d, bt_math), atomicAdd(d + 1, bt_table), atomicAdd(d + 2, bt_wide), atomicAdd(d + 3, __builtin_amdgcn_s_memtime() - bt3), atomicAdd(d + 4, bt_rows);
+        unsigned long long *r = diag64(v.control, DG_BWD_ROW_GROUPS);
+        atomicAdd(r, bt_lanes), atomicAdd(r + 1, bt_steps), atomicAdd(r + 2, bt_leaders);
     })
     return records;
 }
@@ -353,7 +358,7 @@ template <int TEAM, bool BATCH> EGR_DI void backward_chain(const DeviceView v) {
     if (threadIdx.x < TEAM) bteam.ticket[threadIdx.x] = 0u, bteam.nitems[threadIdx.x] = 0u, bteam.finished[threadIdx.x] = 0u;
     uint32_t *const gt_keys = gt_keys_all[wv];
     float *const gt_vals = gt_vals_all[wv];
-    for (int s = lane; s < EGR_GT_SLOTS; s += EGR_WAVE) gt_keys[s] = EGR_GT_EMPTY;
+    for (int s = lane; s < EGR_GT_SLOTS; s += EGR_WAVE) gt_keys[s] = EGR_GT_EMPTY, gt_claim_all[wv][s] = EGR_GT_EMPTY;
     for (int s = lane; s < EGR_GT_STRIDE * EGR_GT_SLOTS; s += EGR_WAVE) gt_vals[s] = 0.0f;
     __syncthreads(); // the kernel's only workgroup barrier (a team's waves run independently from here on)
     const float exp_power = *v.cfg.exp_power;

@@ -38,7 +38,7 @@ enum DiagSlot : int {
     DG_BEGIN = 32, // per step class, 64-bit: primary at the slot, bounce DG_CLASS_STRIDE words on (56 .. 79); the backward's five words are added through one pointer (backward_chain.hpp: primary_hits)
     DG_VISITS = 32, DG_LEAF_HITS = 34, DG_WALK_ITERS = 36, DG_EVAL_ROUNDS = 38, DG_TRAVERSAL_CYC = 40, DG_COMPOSITE_CYC = 42, DG_LEAF_EVAL_CYC = 44, DG_BWD_MATH_CYC = 46 /* x 5 */, DG_CLASS_STRIDE = 24,
     DG_EPILOGUE_CYC = 80, DG_CHAIN_CYC = 82, DG_FILTER_CYC = 84, DG_FILTER_LEAVES = 86, DG_COMP_SCAN_CYC = 88 /* x 5, one pointer again (forward_task.inc) */, // once per launch, 64-bit
-    DG_LIST_HIST = 98 /* x 7 */, DG_TEAM_OFFERS = 124, DG_TEAM_HELPED = 125, DG_TEAM_HELP_ITERS = 126, DG_TEAM_TALL = 127, // once per launch, 32-bit
+    DG_LIST_HIST = 98 /* x 7 */, DG_BWD_ROW_GROUPS = 106 /* x 3, 64-bit, one pointer (backward_chain.hpp: primary_hits) */, DG_TEAM_OFFERS = 124, DG_TEAM_HELPED = 125, DG_TEAM_HELP_ITERS = 126, DG_TEAM_TALL = 127, // once per launch, 32-bit
     DG_STEP_EXIT = 112, // 32-bit x 12: min / max seeds of a per-step wave exit time that no kernel records any more; the prologue still writes them
     DG_END = 128
 };
@@ -77,6 +77,9 @@ constexpr DiagEntry EGR_DIAG_TABLE[] = {
     {DG_LIST_HIST + 4, 32, DK_COUNT, false, "primary lists", "<=48"},
     {DG_LIST_HIST + 5, 32, DK_COUNT, false, "primary lists", "<=64"},
     {DG_LIST_HIST + 6, 32, DK_COUNT, false, "primary lists", "longer"},
+    {DG_BWD_ROW_GROUPS, 64, DK_COUNT, false, "backward primary", "lanes with a hit"},
+    {DG_BWD_ROW_GROUPS + 2, 64, DK_COUNT, false, "backward primary", "pointer-jumping steps"},
+    {DG_BWD_ROW_GROUPS + 4, 64, DK_COUNT, false, "backward primary", "leaders"},
     {DG_TEAM_OFFERS, 32, DK_COUNT, false, "team", "offers made"},
     {DG_TEAM_HELPED, 32, DK_COUNT, false, "team", "offers walked by helpers"},
     {DG_TEAM_HELP_ITERS, 32, DK_COUNT, false, "team", "their walk iterations"},

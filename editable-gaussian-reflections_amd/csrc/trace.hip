@@ -917,52 +917,32 @@ EGR_DI uint32_t grad_table_flush(const DeviceView &v, uint32_t *gt_keys, float *
     return sent;
 }
 
-// The 21 gradient components of the PRIMARY hits of one hit row (one per lane; `pos` = record index) on their way into the wave's LDS table, in two
-// calls: primary_presum (1), then primary_table_add (2, 3), which returns true for a lane whose contribution found no slot and has to leave
-// as two records of its own.
-//  (1) Primary tiles are coherent: the pixel to the right / below very often composites the SAME gaussian at the same hit index, so equal
-//      neighbours are summed in registers first (two DPP levels: x neighbour, then y neighbour) and only the surviving lane touches the table.
-//  (2) The table, keyed by record index. LDS float atomics retire about ONE LANE PER CLOCK PER CU, shared by all resident waves: 22
-//      ds_add_f32 per hit row (1408 lane-operations) made the table half of the backward chain (round 3, per-phase stamps: 12k of 23k
-//      wave-cycles per row on the dense-init cloud). The table is private to this wave, so only lanes of the SAME row can collide, and only
-//      on the same gaussian: a lane finds its slot with plain reads (one CAS when it has to create it), the lanes of a slot elect one of them
-//      per round through a claim word, and the winner adds its 21 components with plain ds_read / ds_write (conflict-free: odd slot stride)
-//      - the others follow in the next round (after the register-level pre-sums few slots see more than one lane).
-//  (3) A hit that finds no slot within 8 probes: the table is (as good as) full. A tile of the dense-init cloud composites more gaussians
+// The 21 gradient components of the PRIMARY hits of one hit row (one per lane; `pos` = record index) on their way into the wave's LDS table
+// (primary_table_add; it returns true for a lane whose contribution found no slot and has to leave as two records of its own). A row's sums need
+// neither an order nor the table: the lanes of a row that hold the SAME gaussian are summed in registers, and one lane per gaussian - the leader -
+// takes the sum to the table in a single pass.
+//  (1) The table, keyed by record index, private to this wave. Every lane with a hit finds its gaussian's slot with plain reads (one CAS when it has
+//      to create it: lanes with different keys can meet on one empty slot). LDS float atomics retire about ONE LANE PER CLOCK PER CU, shared by all
+//      resident waves (22 ds_add_f32 per hit row made the table half of the backward chain in round 3), so a slot is updated with plain
+//      ds_read / ds_write (conflict-free: odd slot stride) - by ONE lane.
+//  (2) The lanes of a slot link up: each swaps its lane id into the slot's claim word and gets the lane that came before it (ds_wrxchg_rtn: one LDS
+//      instruction for the whole row), the last one finds its own id there, leads, and empties the word again. Then pointer jumping: while any lane has
+//      a predecessor, every lane pulls its predecessor's 21 components (ds_bpermute: independent pulls, no LDS memory) and adds them, and takes over
+//      its predecessor's predecessor. A lane pulled from holds the sum of the list behind it, so after ceil(log2(largest group)) steps the leader holds
+//      the group's sum - 3.3 steps per row on the dense-init cloud (55 active lanes, 17 gaussians per row: tools/primary_row_groups.py).
+//      Until round 21 equal x / y neighbours were summed first (two DPP levels, primary_presum), every lane that was left (41 per row) came to the table,
+//      and the lanes of a slot were served one per round through the claim word: 6.1 serialised read-modify-write rounds per row, counted on the GPU.
+//      Also measured and not kept (profiles/HISTORY.md, profiles/r21/): the same tree behind a scalar loop that matches the lanes by record index
+//      (readlane + ballot per distinct gaussian: 17 iterations per row, slower than the rounds), and the DPP levels in front of the list (no gain).
+//  (3) A lane that finds no slot within 8 probes: the table is (as good as) full. A tile of the dense-init cloud composites more gaussians
 //      (~ 100-130) than the table holds, and every hit of a gaussian without a slot used to leave the wave as two 64-B records of its own -
 //      a resident gaussian costs two per TILE. The hits of a tile arrive far to near, layer by layer, so what a full table holds is mostly
 //      done with: the wave empties it (two records per used slot, counted in `records`) and looks its hits up again.
-// (1): called by the lanes that hold a hit (inside their divergent block: `__ballot(true)` is the set of them); returns whether this lane still owns a contribution.
-EGR_DI bool primary_presum(const uint32_t pos, float (&gx)[EGR_GT_COMPS], const int lane) {
-#pragma clang fp contract(off) // a gx[c] that is a product would otherwise be contracted with the add below into an fma on the FETCHED value: the product then has two uses, and the fetch stays a v_mov_b32_dpp
-    bool mine = true;
-    {
-        const unsigned long long em = __ballot(true);
-#define EGR_FETCH_DPP(x, ctrl) __builtin_amdgcn_update_dpp(0, (int)(x), ctrl, 0xF, 0xF, false)
-// The fetch is an operand of the ADD and the select picks sum or old value: the compiler folds the fetch into v_add_f32_dpp (one instruction, then one
-// v_cndmask). Selecting the fetched value first (gx += take ? o : 0) leaves v_mov_b32_dpp + v_cndmask + v_add, and costs 84 VALU instructions more per row.
-#define EGR_COMBINE(d, FETCH, arg)                                                                            \
-    {                                                                                                          \
-        const bool pact = ((em >> ((uint32_t)lane ^ (d))) & 1ull) != 0ull;                                     \
-        const uint32_t ppos = (uint32_t)FETCH(pos, arg), pmine = (uint32_t)FETCH(mine ? 1 : 0, arg);           \
-        const bool same = pact && pmine != 0u && mine && ppos == pos;                                          \
-        const bool take = same && ((uint32_t)lane & (d)) == 0u;                                                \
-        _Pragma("unroll") for (int c = 0; c < EGR_GT_COMPS; c++) {                                             \
-            const float s = gx[c] + __int_as_float(FETCH(__float_as_int(gx[c]), arg));                         \
-            gx[c] = take ? s : gx[c];                                                                          \
-        }                                                                                                      \
-        if (same && !take) mine = false;                                                                       \
-    }
-        EGR_COMBINE(1u, EGR_FETCH_DPP, 0xB1)  // quad_perm [1,0,3,2]: lane ^ 1
-        EGR_COMBINE(8u, EGR_FETCH_DPP, 0x128) // row_ror 8: lane ^ 8
-#undef EGR_COMBINE
-#undef EGR_FETCH_DPP
-    }
-    return mine;
-}
-// (2), (3): wave-level; `want` = this lane holds a contribution (primary_presum) that looks for a table slot.
-EGR_DI bool primary_table_add(const DeviceView &v, const bool want, const uint32_t pos, const float (&gx)[EGR_GT_COMPS], uint32_t *gt_keys, float *gt_vals, uint32_t *gt_claim, float4 *stage,
-                              const int lane, uint32_t &records) {
+// Wave-level; `want` = this lane holds a hit. `gx` of a leader ends as its group's sum (of any other lane: a partial sum nobody reads).
+// `steps`, `leaders`: pointer-jumping steps and leaders of this row (wave-uniform; read by the EGR_TRAVERSAL_STATS build only).
+EGR_DI bool primary_table_add(const DeviceView &v, const bool want, const uint32_t pos, float (&gx)[EGR_GT_COMPS], uint32_t *gt_keys, float *gt_vals, uint32_t *gt_claim, float4 *stage,
+                              const int lane, uint32_t &records, uint32_t &steps, uint32_t &leaders) {
+#pragma clang fp contract(off) // (a gx[c] that is a product stays a product: the add below is an add of the PULLED value)
     bool found = false;
     uint32_t slot = 0u;
     auto probe = [&]() {
@@ -970,7 +950,7 @@ EGR_DI bool primary_table_add(const DeviceView &v, const bool want, const uint32
         found = false;
 #pragma unroll 1
         for (int pr = 0; pr < (want ? 8 : 0); pr++) {
-            uint32_t key = *reinterpret_cast<volatile uint32_t *>(&gt_keys[slot]);
+            uint32_t key = lds_peek(&gt_keys[slot]);
             if (key == EGR_GT_EMPTY) key = atomicCAS(&gt_keys[slot], EGR_GT_EMPTY, pos), key = key == EGR_GT_EMPTY ? pos : key; // (another lane of this row may have taken it meanwhile)
             if (key == pos) { found = true; break; }
             slot = slot + 1u == (uint32_t)EGR_GT_SLOTS ? 0u : slot + 1u;
@@ -981,22 +961,43 @@ EGR_DI bool primary_table_add(const DeviceView &v, const bool want, const uint32
         records += grad_table_flush(v, gt_keys, gt_vals, stage, lane);
         probe();
     }
-    bool pending = found; // this lane's contribution still has to be added to its table slot
-    while (__ballot(pending) != 0ull) { // the rounds of the table update (wave-uniform loop)
-        if (pending) gt_claim[slot] = (uint32_t)lane;
-        EGR_BWD_SYNC();
-        const bool win = pending && gt_claim[slot] == (uint32_t)lane;
-        if (win) {
-            float *cell = gt_vals + slot * EGR_GT_STRIDE;
-            float cur[EGR_GT_COMPS];
-#pragma unroll
-            for (int c = 0; c < EGR_GT_COMPS; c++) cur[c] = cell[c];
-#pragma unroll
-            for (int c = 0; c < EGR_GT_COMPS; c++) cell[c] = cur[c] + gx[c];
-            pending = false;
-        }
-        EGR_BWD_SYNC();
+    // (2) the lanes of a slot as a list: `prev` = the lane that came before this one, this lane itself: none
+    uint32_t prev = (uint32_t)lane;
+    if (found) {
+        const uint32_t before = atomicExch(&gt_claim[slot], (uint32_t)lane);
+        prev = before == EGR_GT_EMPTY ? (uint32_t)lane : before;
     }
+    EGR_BWD_SYNC();
+    const bool leader = found && lds_peek(&gt_claim[slot]) == (uint32_t)lane; // the last lane of its slot
+    if (leader) lds_poke(&gt_claim[slot], EGR_GT_EMPTY); // (the word is empty between rows)
+    steps = 0u, leaders = (uint32_t)__popcll(__ballot(leader));
+    unsigned long long more = __ballot(prev != (uint32_t)lane);
+#pragma unroll 1
+    while (more != 0ull) { // wave-uniform: the pulls read every lane
+        const bool take = prev != (uint32_t)lane;
+        const int from = (int)(prev << 2);
+        float o[EGR_GT_COMPS];
+#pragma unroll
+        for (int c = 0; c < EGR_GT_COMPS; c++) o[c] = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(gx[c])));
+        const uint32_t p2 = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)prev);
+#pragma unroll
+        for (int c = 0; c < EGR_GT_COMPS; c++) { // add, then select (as `if (take) gx[c] += o[c]` the compiler keeps two copies of gx and moves between them: 0.2-0.4 ms)
+            const float s = gx[c] + o[c];
+            gx[c] = take ? s : gx[c];
+        }
+        prev = p2 == prev ? (uint32_t)lane : p2; // (the lane pulled from has none before it - it names itself -, or this lane pulled from itself: none)
+        more = __ballot(prev != (uint32_t)lane);
+        steps++;
+    }
+    if (leader) { // (1) the one pass: a slot is its leader's
+        float *cell = gt_vals + slot * EGR_GT_STRIDE;
+        float cur[EGR_GT_COMPS];
+#pragma unroll
+        for (int c = 0; c < EGR_GT_COMPS; c++) cur[c] = cell[c];
+#pragma unroll
+        for (int c = 0; c < EGR_GT_COMPS; c++) cell[c] = cur[c] + gx[c];
+    }
+    EGR_BWD_SYNC(); // (the next row's leader of this gaussian may be another lane)
     return want && !found; // (still no slot: the 21 components leave as two 16-lane records, like a flushed slot)
 }
 
